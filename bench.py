@@ -18,9 +18,16 @@ Workload
           all-gather) -- strong scaling: the total work does not depend on N.  `--size` overrides the size.
 One step = one VCycle(0, 2, 2) through the C host layer (include/mg_multigrid.h), inputs resident in HBM.
     MLUPS = (v1+v2) * sum_levels (n_l - 2)^3 * steps / seconds          
-    The K steps are timed BATCHES times (default 5; each batch = exactly K steps between a barrier + sync on both sides,
-    maximum over ranks); `value` / `ms_per_step` are the MEDIAN batch, `batches` lists them all.  W untimed cycles come first
-    (default 150 = 0.5 s at 513^3: the GPU needs ~100 cycles to reach its steady state, the first ones run 2-3 % slower).
+    Exactly K steps are timed, split into BATCHES consecutive batches of near-equal size (default 5, at most K), queued
+    back to back after one barrier + sync and each timed by the wall clock up to its end (maximum over ranks); `value` /
+    `ms_per_step` are the MEDIAN batch's time per step, `batches` lists them all.  W untimed cycles come first (default
+    150 = 0.5 s at 513^3: the GPU needs ~100 cycles to reach its steady state, the first ones run 2-3 % slower), then one
+    more that counts the exchanges of a cycle.
+--dump-outputs DIR: after the timed steps, the finest v as the last timed step left it (the array a caller of VCycle
+    receives: v after W + 1 + K cycles from v = 0), in its own dtype, 64 MB at most: DIR/v.npy when v fits, else
+    DIR/v_sample.npy (its values at up to 2^22 fixed, seeded positions, dump_sample_index) and, where it fits as well,
+    DIR/v_centre_plane.npy (the plane z = n / 2 in full).  The inputs do not change from run to run, so two builds can be
+    compared file for file.
 secondary (N = 1, default size only): BASELINE configs[1] (2D Lyapunov 1025^2, 7 levels, fp64), configs[2] (3D 257^3, 6
     levels, fp64) and the headline workload in the reference's own precision (513^3 fp32), each timed the same way and
     checked against its committed known answer; and the reference's two PUBLISHED GPU workloads with their own parameters
@@ -53,6 +60,9 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_BPS = 8.0e12  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8 TB/s; about 6.3 TB/s achievable)
 R3 = [0, 1, 0, 1, 0, 1]
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this much in all (4 KB of it kept for the .npy headers)
+DUMP_SAMPLE = 1 << 22  # positions drawn for the sample of a larger v
+DUMP_SEED = 513
 
 
 def level_sizes(n, nlevels):
@@ -87,6 +97,44 @@ def known_answer(n, nlev, dtype):
         return None
     with open(path) as fh:
         return json.load(fh).get("3d_n%d_vcycle22_%dlev_%s" % (n, nlev, dtype))
+
+
+def dump_sample_index(n):
+    """the fixed, seeded sample of an n^3 output: sorted flat indices in memory order (x fastest), without repeats"""
+    import numpy as np
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n ** 3, DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(path, v, z0, n, rank, world, rdzv):
+    """--dump-outputs (module docstring): `v` holds the planes z0, z0 + 1, ... of the finest n^3 v (all of them with one
+    rank).  With more ranks every rank writes its part into `path` and rank 0 joins the parts in z order."""
+    import numpy as np
+    first, flat = z0 * n * n, v.reshape(-1)
+    if v.itemsize * n ** 3 <= DUMP_BYTES - 4096:
+        parts = {"v": v}
+    else:
+        idx = dump_sample_index(n)
+        idx = idx[(idx >= first) & (idx < first + flat.size)]
+        parts = {"v_sample": flat[idx - first]}
+        if z0 <= n // 2 < z0 + v.shape[0] and v.itemsize * (DUMP_SAMPLE + n * n) <= DUMP_BYTES - 4096:
+            parts["v_centre_plane"] = v[n // 2 - z0]
+    os.makedirs(path, exist_ok=True)
+    if world == 1:
+        for name, a in parts.items():
+            np.save(os.path.join(path, name + ".npy"), a)
+        return
+    part = lambda r, name: os.path.join(path, ".rank%d.%s.npy" % (r, name))  # noqa: E731
+    for name, a in parts.items():
+        np.save(part(rank, name), a)
+    z0s = rdzv.all_gather(z0)
+    if rank == 0:
+        for name in ("v", "v_sample", "v_centre_plane"):
+            files = [part(r, name) for r in sorted(range(world), key=lambda r: z0s[r]) if os.path.exists(part(r, name))]
+            if files:
+                np.save(os.path.join(path, name + ".npy"), np.concatenate([np.load(f) for f in files]))
+                for f in files:
+                    os.unlink(f)
+    rdzv.barrier()
 
 
 def load_launch():
@@ -259,12 +307,18 @@ def main():
     ap.add_argument("--min-planes", type=int, default=32,
                     help="N>1: a level stays distributed while every GPU owns this many planes; coarser levels are replicated "
                          "(below about 32 planes per GPU the ghost exchanges are pure latency)")
-    ap.add_argument("--batches", type=int, default=5, help="the K timed steps are repeated this many times; the median batch is reported")
+    ap.add_argument("--batches", type=int, default=5,
+                    help="the K timed steps are split into this many consecutive batches (at most K); the median batch is reported")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configurations (N = 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip the result check against the committed known answer")
     ap.add_argument("--no-one-gpu-leg", action="store_true", help="N>1: skip rank 0's single-GPU run of the same problem")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the finest v of the last one into DIR: v.npy, or when v exceeds 64 MB a "
+                         "fixed, seeded sample (v_sample.npy) and the centre plane (v_centre_plane.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
@@ -329,16 +383,27 @@ def main():
             rdzv.barrier()
 
     def timed_batches(cycle, steps, batches):
-        """seconds of `steps` cycles, `batches` times: each batch between barrier + sync on both sides, max over ranks"""
-        out = []
-        for _ in range(batches):
-            barrier()
-            t0 = time.perf_counter()
-            for _ in range(steps):
+        """`steps` cycles in all, in `batches` consecutive batches of near-equal size (at most `steps`) queued back to back
+        after one barrier + sync: the host waits for the end of batch b (an event) only once batch b + 1 is queued, so the
+        GPU does not idle between batches, and reads the clock when the wait returns.  Seconds per step of every batch, max
+        over ranks"""
+        nb = max(1, min(batches, steps))
+        ks = [steps // nb + (1 if b < steps % nb else 0) for b in range(nb)]
+        ends = [ctx.event() for _ in range(nb)]
+        barrier()
+        t = [time.perf_counter()]
+        for b in range(nb):
+            for _ in range(ks[b]):
                 cycle()
-            ctx.sync()
-            dt = time.perf_counter() - t0
-            out.append(rdzv.max(dt) if rdzv is not None else dt)
+            ctx.record(ends[b])
+            if b > 0:
+                ctx.elapsed_ms(ends[b - 1], ends[b - 1])  # waits for the end of batch b - 1
+                t.append(time.perf_counter())
+        ctx.sync()
+        t.append(time.perf_counter())
+        out = [(t[b + 1] - t[b]) / ks[b] for b in range(nb)]
+        if rdzv is not None:
+            out = [max(x) for x in zip(*rdzv.all_gather(out))]
         barrier()
         return out
 
@@ -350,9 +415,13 @@ def main():
         ex0 = mg.n_exchanges if slabbed else 0
         mg.VCycle(0, args.v1, args.v2)
         exch = (mg.n_exchanges - ex0) if slabbed else None  # halo exchanges + collectives this rank enqueues per cycle
-        bs = timed_batches(lambda: mg.VCycle(0, args.v1, args.v2), args.steps, max(1, args.batches))
-        el = sorted(bs)[len(bs) // 2]  # the median batch
-        return bs, el, lups_per_cycle * args.steps / el / 1e6, exch  # one shared problem: whole-job rate
+        bs = timed_batches(lambda: mg.VCycle(0, args.v1, args.v2), args.steps, args.batches)
+        if args.dump_outputs:
+            got, z0 = (mg.download_owned(0), mg.plan(0).zlo) if slabbed else (mg.download_v(0), 0)
+            dump_outputs(args.dump_outputs, got, z0, n, rank, world, rdzv)
+            del got
+        el = sorted(bs)[len(bs) // 2]  # the median batch, seconds per step
+        return bs, el, lups_per_cycle / el / 1e6, exch  # one shared problem: whole-job rate
 
     batch_s, elapsed, mlups, exchanges = throughput()
 
@@ -524,9 +593,9 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "batches": {"count": len(batch_s), "ms_per_step": [round(b / args.steps * 1e3, 4) for b in batch_s],
-                        "min": round(min(batch_s) / args.steps * 1e3, 4), "median": round(elapsed / args.steps * 1e3, 4)},
+            "ms_per_step": round(elapsed * 1e3, 4),
+            "batches": {"count": len(batch_s), "ms_per_step": [round(b * 1e3, 4) for b in batch_s],
+                        "min": round(min(batch_s) * 1e3, 4), "median": round(elapsed * 1e3, 4)},
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -561,7 +630,7 @@ def main():
         if down is not None:
             out["roofline_down"] = down
         if one_gpu is not None:
-            one_gpu = dict(one_gpu, speedup=round(one_gpu["ms_per_step"] / (elapsed / args.steps * 1e3), 3))
+            one_gpu = dict(one_gpu, speedup=round(one_gpu["ms_per_step"] / (elapsed * 1e3), 3))
             out["config"]["one_gpu_same_problem"] = one_gpu
         if slabbed:
             out["config"]["schedule"] = schedule
@@ -592,7 +661,7 @@ def main():
     if two_legs:
         # ---- the default schedule, under a watchdog: if it does not come back, rank 0 reports the conservative leg ----
         import threading
-        legA = {"ms_per_step": round(elapsed / args.steps * 1e3, 4), "value": round(mlups, 1), "exchanges_per_cycle": exchanges,
+        legA = {"ms_per_step": round(elapsed * 1e3, 4), "value": round(mlups, 1), "exchanges_per_cycle": exchanges,
                 "result_check": (check or {}).get("status"), "what": "every exchange on the comm stream, one per colour pass (inline_bytes = 0, ca_min_planes = 0)"}
         deadline = float(os.environ.get("MGX_BENCH_LEG_TIMEOUT", "0")) or max(180.0, 30.0 * (time.perf_counter() - t_start))
 
@@ -611,7 +680,7 @@ def main():
         batch_s, elapsed, mlups, exchanges = throughput()
         check, failed = result_check()
         dog.cancel()
-        legB = {"ms_per_step": round(elapsed / args.steps * 1e3, 4), "value": round(mlups, 1), "exchanges_per_cycle": exchanges,
+        legB = {"ms_per_step": round(elapsed * 1e3, 4), "value": round(mlups, 1), "exchanges_per_cycle": exchanges,
                 "result_check": (check or {}).get("status"),
                 "what": "library defaults: communication-avoiding exchanges (one per Relax call) on slabs of >= 16 planes, levels of <= 96 MB per slab inline on the compute stream"}
         if rank == 0:

@@ -48,3 +48,38 @@ def test_default_line_contract_and_secondary_configs():
     assert len(sec) == 5 and all(c["result_check"] == "ok" for c in sec.values()), sec  # configs[1], [2], fp32, the two published workloads
     pub = [c for k, c in sec.items() if k.startswith("published workload")][0]
     assert 0.05 < pub["seconds"] < 5.0 and pub["known_answer"] == "3d_n129_fmg_2_3000_3000_f32"
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("n", [65, 513])
+def test_dump_outputs_are_the_last_timed_step(tmp_path, n):
+    """--dump-outputs: the finest v after W + 1 + K cycles from v = 0 (v.npy whole when it fits into 64 MB, else the
+    seeded sample and the centre plane), bit for bit what the same cycles give in this process; --steps K times K steps"""
+    import numpy as np
+
+    import bench
+    import pde_multigrid_amd as P
+
+    w, k = 2, 3
+    out = _bench(["--size", str(n), "--steps", str(k), "--warmup", str(w), "--batches", "2", "--no-secondary", "--no-cpu-baseline",
+                  "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == k and len(out["batches"]["ms_per_step"]) == 2
+    files = sorted(os.listdir(tmp_path))
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64_000_000
+    ctx = P.Context(0)
+    mg = P.MultiGrid3D(ctx, [n] * 3, [0, 1, 0, 1, 0, 1], np.float64)
+    mg.setToValue_v(0, 0.0, True)
+    for _ in range(w + 1 + k):
+        mg.VCycle(0, 2, 2)
+    want = mg.download_v(0)
+    mg.close()
+    ctx.close()
+    if n == 65:
+        assert files == ["v.npy"]
+        parts = {"v": want}
+    else:
+        assert files == ["v_centre_plane.npy", "v_sample.npy"]
+        parts = {"v_sample": want.reshape(-1)[bench.dump_sample_index(n)], "v_centre_plane": want[n // 2]}
+    for name, a in parts.items():
+        got = np.load(os.path.join(tmp_path, name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got.view(np.uint64), a.view(np.uint64)), name
