@@ -103,6 +103,11 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
                                    mgMultiGrid3D_##R** out);                                             \
     int mgMultiGrid3D_##R##_create_layout(mgx_ctx* ctx, const int finestGridSizeXYZ[3],                  \
                                           const real range[6], int layout, mgMultiGrid3D_##R** out);     \
+    /* nlevels > 0: the caller will use only the first nlevels levels (numGrids <= nlevels); the levels */ \
+    /* past them that would have an even extent are then not built (maxGrids stops before the first).  */ \
+    int mgMultiGrid3D_##R##_create_levels(mgx_ctx* ctx, const int finestGridSizeXYZ[3],                  \
+                                          const real range[6], int layout, int nlevels,                  \
+                                          mgMultiGrid3D_##R** out);                                      \
     void mgMultiGrid3D_##R##_destroy(mgMultiGrid3D_##R* mg);                                             \
     int mgMultiGrid3D_##R##_InitV(mgMultiGrid3D_##R* mg, int gridID);                                    \
     int mgMultiGrid3D_##R##_InitF(mgMultiGrid3D_##R* mg, int gridID);                                    \

@@ -34,7 +34,8 @@
  *   - every function returns an int status (MGX_OK = 0); nothing aborts
  *     (the reference asserts, N3/MultiGrid3D.cpp:60-62).  mgx_last_error() gives text.
  *   - arrays are dense, unpadded, x fastest: idx = x + y*sx + z*sx*sy
- *     (N3/MultiGrid3D.cpp:531); sizes are int[dim] = {sx, sy(, sz)}, each 2^k+1.
+ *     (N3/MultiGrid3D.cpp:531); sizes are int[dim] = {sx, sy(, sz)}, each odd and >= 3
+ *     (2^k+1 is not required; a hierarchy needs every one of its levels odd).
  *   - all `real*` arguments are DEVICE pointers obtained from mgx_malloc unless the
  *     name starts with host_.
  *   - kernels run on the context's compute stream; calls are asynchronous with respect

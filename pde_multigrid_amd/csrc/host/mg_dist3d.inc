@@ -176,7 +176,7 @@ int FN(InitF)(MGRID* mg, int gridID) {
     for (int i = 0; i < sx; i++) { REAL x = g->x_a + i * g->h_x; tx[i] = sin(MG_PI * x); } /* N3/Grid3D.cpp:88-92 */
     for (int i = 0; i < sy; i++) { REAL y = g->y_a + i * g->h_y; ty[i] = sin(MG_PI * y); }
     for (int i = 0; i < sz; i++) { REAL z = g->z_a + i * g->h_z; tz[i] = sin(MG_PI * z); }
-    /* init_f works plane by plane, so the slab is initialised in slices of 3 planes (a valid 2^k+1 size) */
+    /* init_f works plane by plane, so the slab is initialised in slices of 3 planes (a valid size: odd, >= 3) */
     const size_t pl = MG_CAT(plane3_, R)(g);
     int st = MGX_OK;
     for (int z = 0; z < g->plan.nzl && !st; z += 3) {
@@ -194,7 +194,7 @@ int FN(create)(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const REAL range[6]
     *out = NULL;
     for (int d = 0; d < 3; d++)
         MG_REQUIRE(finestGridSizeXYZ[d] >= 3 && (finestGridSizeXYZ[d] - 1) % 2 == 0, MGX_ERR_SIZE,
-                   "DistMultiGrid3D: size[%d] = %d is not 2^k+1", d, finestGridSizeXYZ[d]);
+                   "DistMultiGrid3D: size[%d] = %d is not odd and >= 3", d, finestGridSizeXYZ[d]);
     MG_REQUIRE(range[1] > range[0] && range[3] > range[2] && range[5] > range[4], MGX_ERR_INVALID, "DistMultiGrid3D: empty range");
     int minSize = finestGridSizeXYZ[0];
     if (finestGridSizeXYZ[1] < minSize) minSize = finestGridSizeXYZ[1];

@@ -12,7 +12,7 @@
 
 /* Grid1D::Grid1D + InitV + InitF.                                      N1/Grid1D.cpp:4-43 */
 static int MG_CAT(grid1_new_, R)(int sizeX, const REAL range[2], GRID** out) {
-    MG_REQUIRE(sizeX >= 3 && (sizeX - 1) % 2 == 0, MGX_ERR_SIZE, "Grid1D: size %d is not 2^k+1", sizeX); /* :6-7 */
+    MG_REQUIRE(sizeX >= 3 && (sizeX - 1) % 2 == 0, MGX_ERR_SIZE, "Grid1D: size %d is not odd and >= 3", sizeX); /* :6-7 */
     MG_REQUIRE(range[1] > range[0], MGX_ERR_INVALID, "Grid1D: empty range");                              /* :10 */
     GRID* g = (GRID*)calloc(1, sizeof(GRID));
     MG_REQUIRE(g, MGX_ERR_NOMEM, "Grid1D: out of host memory");

@@ -13,7 +13,7 @@ static size_t MG_CAT(vol2_, R)(const GRID* g) { return (size_t)g->sizeX * g->siz
 /* Grid2D::Grid2D.                                                     N2/Grid2D.cpp:4-42 */
 static int MG_CAT(grid2_new_, R)(mgx_ctx* ctx, const int sizeXY[2], const REAL range[4], GRID** out) {
     for (int d = 0; d < 2; d++)
-        MG_REQUIRE(sizeXY[d] >= 3 && (sizeXY[d] - 1) % 2 == 0, MGX_ERR_SIZE, "Grid2D: size[%d] = %d is not 2^k+1", d,
+        MG_REQUIRE(sizeXY[d] >= 3 && (sizeXY[d] - 1) % 2 == 0, MGX_ERR_SIZE, "Grid2D: size[%d] = %d is not odd and >= 3", d,
                    sizeXY[d]); /* :11-15 */
     MG_REQUIRE(range[1] > range[0] && range[3] > range[2], MGX_ERR_INVALID, "Grid2D: empty range"); /* :21-22 */
     GRID* g = (GRID*)calloc(1, sizeof(GRID));

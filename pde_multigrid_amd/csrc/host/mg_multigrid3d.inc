@@ -16,10 +16,10 @@ static size_t MG_CAT(dvol3_, R)(int layout, const GRID* g) {
 
 /* Grid3D::Grid3D geometry part.                                   N3/Grid3D.cpp:4-53 */
 static int MG_CAT(grid3_new_, R)(mgx_ctx* ctx, int layout, const int sizeXYZ[3], const REAL range[6], GRID** out) {
-    /* the reference asserts equal sizes (N3/Grid3D.cpp:10-11); the kernels do not need that,
-     * only 2^k+1 per axis, so it is not enforced here. */
+    /* the reference asserts equal sizes (N3/Grid3D.cpp:10-11); the kernels do not need that, nor 2^k+1: every axis
+     * has to be odd and >= 3 (every level of a hierarchy, so that it restricts onto the next one), nothing more. */
     for (int d = 0; d < 3; d++)
-        MG_REQUIRE(sizeXYZ[d] >= 3 && (sizeXYZ[d] - 1) % 2 == 0, MGX_ERR_SIZE, "Grid3D: size[%d] = %d is not 2^k+1", d,
+        MG_REQUIRE(sizeXYZ[d] >= 3 && (sizeXYZ[d] - 1) % 2 == 0, MGX_ERR_SIZE, "Grid3D: size[%d] = %d is not odd and >= 3", d,
                    sizeXYZ[d]); /* :13-20 */
     MG_REQUIRE(range[1] > range[0] && range[3] > range[2] && range[5] > range[4], MGX_ERR_INVALID,
                "Grid3D: empty range"); /* :27-29 */
@@ -41,7 +41,7 @@ static int MG_CAT(grid3_new_, R)(mgx_ctx* ctx, int layout, const int sizeXYZ[3],
     int st;
     if ((st = mgx_malloc(ctx, bytes, (void**)&g->d_v)) || (st = mgx_malloc(ctx, bytes, (void**)&g->d_f)) ||
         (st = mgx_malloc(ctx, bytes, (void**)&g->d_r)) || (st = mgx_malloc(ctx, bytes, (void**)&g->d_e)) ||
-        /* pad entries of the x-split layout are never written: zero them once */
+        /* pad entries of the x-split layout are never written but by whole-array zero fills: zero them once */
         (st = mgx_memset_zero(ctx, g->d_v, bytes)) || (st = mgx_memset_zero(ctx, g->d_f, bytes)) ||
         (st = mgx_memset_zero(ctx, g->d_r, bytes)) || (st = mgx_memset_zero(ctx, g->d_e, bytes))) {
         mgx_free(ctx, g->d_v); mgx_free(ctx, g->d_f); mgx_free(ctx, g->d_r); mgx_free(ctx, g->d_e);
@@ -90,11 +90,18 @@ int FN(InitF)(MGRID* mg, int gridID) {
 
 /* MultiGrid3D::MultiGrid3D + InitGrids.                               N3/MultiGrid3D.cpp:5-47 */
 int FN(create)(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const REAL range[6], MGRID** out) {
-    return FN(create_layout)(ctx, finestGridSizeXYZ, range, 1, out);
+    return FN(create_levels)(ctx, finestGridSizeXYZ, range, 1, 0, out);
 }
 
 /* layout: 0 = device arrays in the reference layout, 1 = x-split (default of create(); faster smoother) */
 int FN(create_layout)(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const REAL range[6], int layout, MGRID** out) {
+    return FN(create_levels)(ctx, finestGridSizeXYZ, range, layout, 0, out);
+}
+
+/* nlevels > 0: only the first nlevels levels will be used.  An odd extent that is not 2^k+1 reaches an even one further down
+ * (97 -> 49 -> 25 -> 13 -> 7 -> 4): with the level count of the reference's rule that is MGX_ERR_SIZE, as the reference's Grid3D
+ * asserts; levels past nlevels are not built, so such a grid runs with a shorter hierarchy. */
+int FN(create_levels)(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const REAL range[6], int layout, int nlevels, MGRID** out) {
     MG_REQUIRE(ctx && finestGridSizeXYZ && range && out, MGX_ERR_INVALID, "MultiGrid3D: NULL argument");
     *out = NULL;
     int minSize = finestGridSizeXYZ[0]; /* :25-30 */
@@ -115,6 +122,10 @@ int FN(create_layout)(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const REAL r
     if (!mg->grids3D) { free(mg); return mg_fail(MGX_ERR_NOMEM, "MultiGrid3D: out of host memory"); }
     int cur[3] = {finestGridSizeXYZ[0], finestGridSizeXYZ[1], finestGridSizeXYZ[2]};
     for (int i = 0; i < mg->maxGrids; i++) {
+        if (nlevels > 0 && i >= nlevels && (cur[0] % 2 == 0 || cur[1] % 2 == 0 || cur[2] % 2 == 0)) {
+            mg->numGrids = mg->maxGrids = i; /* the levels from here on would never be visited */
+            break;
+        }
         int st = MG_CAT(grid3_new_, R)(ctx, mg->layout, cur, range, &mg->grids3D[i]);
         if (!st) st = FN(InitV)(mg, i);
         if (!st) st = FN(InitF)(mg, i);
@@ -458,7 +469,7 @@ static int MG_CAT(solve3_, R)(mgx_ctx* ctx, REAL* grid, const REAL* rhs, const i
                               int fmg, int v0, int v1, int v2, int ncycles, int residual_mode, int grid_is_zero) {
     MG_REQUIRE(ctx && grid && sizeXYZ && range, MGX_ERR_INVALID, "mg3d_solve: NULL argument");
     MGRID* mg = NULL;
-    MG_TRY(FN(create)(ctx, sizeXYZ, range, &mg)); /* InitV: v = 0; InitF: the reference's analytic right-hand side */
+    MG_TRY(FN(create_levels)(ctx, sizeXYZ, range, 1, nlevels, &mg)); /* InitV: v = 0; InitF: the reference's analytic right-hand side */
     int st = MGX_OK;
     if (nlevels > 0) {
         if (nlevels > mg->maxGrids) st = mg_fail(MGX_ERR_SIZE, "mg3d_solve: nlevels %d > %d", nlevels, mg->maxGrids);

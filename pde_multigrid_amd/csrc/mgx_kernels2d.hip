@@ -649,7 +649,7 @@ static inline dim3 grd2(int nx, int ny) { return dim3(ceil_div(nx, 64), ceil_div
 static int check_n2(const int n[2], const char* what) {
     MGX_REQUIRE(n, MGX_ERR_INVALID, "%s: size array is NULL", what);
     for (int d = 0; d < 2; d++)
-        MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "%s: size[%d] = %d is not 2^k+1 >= 3", what, d, n[d]);
+        MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "%s: size[%d] = %d is not odd and >= 3", what, d, n[d]);
     return MGX_OK;
 }
 

@@ -957,7 +957,7 @@ __global__ void __launch_bounds__(64 * WX * WY)
     __shared__ real sK[CORR ? 3 : 1][CORR ? KR : 1][CORR ? KC : 1];
     const Geo<XSplit, real> g(sx, sy);
     const int H = g.H;
-    const int M = (sx + 1) >> 1;  // M - 1 pairs hold an interior point; M - 1 is even (sx = 2^k + 1 >= 5)
+    const int M = (sx + 1) >> 1;  // M - 1 pairs hold an interior point; M - 1 is even (the host: pipe_v2_takes)
     const double rd = relax3d_rd<real>(hx2, hy2, hz2);
     unsigned b = blockIdx.x;
     if (xcd_mode == 1) {
@@ -2328,7 +2328,7 @@ static inline dim3 grd(int nx, int ny, int nz) { return dim3(ceil_div(nx, 64), c
 static int check_n3(const int n[3], const char* what) {
     MGX_REQUIRE(n, MGX_ERR_INVALID, "%s: size array is NULL", what);
     for (int d = 0; d < 3; d++)
-        MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "%s: size[%d] = %d is not 2^k+1 >= 3", what, d, n[d]);
+        MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "%s: size[%d] = %d is not odd and >= 3", what, d, n[d]);
     MGX_REQUIRE((double)n[0] * n[1] * n[2] < 2147483647.0 * 4, MGX_ERR_SIZE, "%s: grid too large", what);
     return MGX_OK;
 }
@@ -2482,13 +2482,23 @@ static int pipe_min_planes(int sx) {
     return M - 1 >= 512 ? 8 : (M - 1 >= 256 ? 24 : 64);
 }
 
+// fp32 on wide levels: two x-pairs per lane (relax3d_xs_pipe_v2_kernel).  A lane of that kernel owns both pairs of its slot or
+// none, so the level needs an even number of interior pairs: rows of 4k + 1 points (every 2^k + 1 >= 5).  Rows of 4k + 3 points
+// (515, 771, 1023, ...) would have the last lane relax the boundary column x = sx - 1 and store into the odd half's pad: they
+// take the one-pair kernel.
+template <class real>
+static bool pipe_v2_takes(const mgx_ctx* ctx, int sx) {
+    const int pairs = (sx + 1) / 2 - 1;
+    return sizeof(real) == 4 && ctx->relax_v2 && pairs >= 256 && pairs % 2 == 0;
+}
+
 template <class real>
 static bool relax3d_xs_pass_lds(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zbeg, int zend, real hx2, real hy2,
                                 real hz2, int colour) {
     const int M = (sx + 1) / 2;
     int zchunk = ctx->relax_zchunk;
     int code = ctx->relax_lds;
-    if (code < 0 && sizeof(real) == 4 && ctx->relax_v2 && M - 1 >= 256 && sy - 2 >= 64 && zend - zbeg >= 8) {
+    if (code < 0 && pipe_v2_takes<real>(ctx, sx) && sy - 2 >= 64 && zend - zbeg >= 8) {
         // fp32 on wide levels: two pairs per lane (8-byte loads), 2 x 8 waves of 2 rows over 256 pairs x 16 rows
         if (zchunk <= 0) {
             const int tiles = ceil_div(M - 1, 256) * ceil_div(sy - 2, 16);
@@ -2568,7 +2578,7 @@ template <class real>
 static bool relax3d_xs_first_sweep_zero(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int sz, real hx2, real hy2, real hz2) {
     const int M = (sx + 1) / 2, zbeg = 1, zend = sz - 1;
     if (!ctx->relax_zero_sweep || ctx->relax_lds != -1 || M - 1 < 128 || sy - 2 < 64 || zend - zbeg < 8) return false;
-    if (sizeof(real) == 4 && ctx->relax_v2 && M - 1 >= 256) return false;
+    if (pipe_v2_takes<real>(ctx, sx)) return false;
     const bool fnt = (size_t)sx * sy * (size_t)(zend - zbeg) * sizeof(real) > ((size_t)256 << 20);
     const bool low = sizeof(real) == 8 && sy - 2 <= 256 && !fnt;
     int zchunk = ctx->relax_zchunk;
@@ -3115,7 +3125,7 @@ int relax3d_colour_slab(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, co
                         int zend, int zoff) {
     MGX_REQUIRE(ctx && v && f && h, MGX_ERR_INVALID, "relax_colour_slab: NULL argument");
     MGX_USE(ctx);
-    MGX_REQUIRE(valid_size(sx) && valid_size(sy), MGX_ERR_SIZE, "relax_colour_slab: sizes %d x %d are not 2^k+1", sx, sy);
+    MGX_REQUIRE(valid_size(sx) && valid_size(sy), MGX_ERR_SIZE, "relax_colour_slab: sizes %d x %d are not odd and >= 3", sx, sy);
     MGX_REQUIRE((colour == 0 || colour == 1) && zbeg >= 1 && zend >= zbeg && zoff >= 0, MGX_ERR_INVALID,
                 "relax_colour_slab: bad colour / plane range");
     const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
@@ -3130,7 +3140,7 @@ int relax3d_colour_slab2(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, c
                          int ze2, int zoff) {
     MGX_REQUIRE(ctx && v && f && h, MGX_ERR_INVALID, "relax_colour_slab2: NULL argument");
     MGX_USE(ctx);
-    MGX_REQUIRE(valid_size(sx) && valid_size(sy), MGX_ERR_SIZE, "relax_colour_slab2: sizes %d x %d are not 2^k+1", sx, sy);
+    MGX_REQUIRE(valid_size(sx) && valid_size(sy), MGX_ERR_SIZE, "relax_colour_slab2: sizes %d x %d are not odd and >= 3", sx, sy);
     MGX_REQUIRE((colour == 0 || colour == 1) && zb1 >= 1 && ze1 >= zb1 && zb2 >= ze1 && ze2 >= zb2 && zoff >= 0, MGX_ERR_INVALID,
                 "relax_colour_slab2: bad colour / plane ranges");
     const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
@@ -3149,7 +3159,7 @@ int relax3d_zero_colour_slab(mgx_ctx* ctx, real* v, const real* f, int sx, int s
                              int zoff) {
     MGX_REQUIRE(ctx && v && f && h, MGX_ERR_INVALID, "relax_zero_colour_slab: NULL argument");
     MGX_USE(ctx);
-    MGX_REQUIRE(valid_size(sx) && valid_size(sy), MGX_ERR_SIZE, "relax_zero_colour_slab: sizes %d x %d are not 2^k+1", sx, sy);
+    MGX_REQUIRE(valid_size(sx) && valid_size(sy), MGX_ERR_SIZE, "relax_zero_colour_slab: sizes %d x %d are not odd and >= 3", sx, sy);
     MGX_REQUIRE((colour == 0 || colour == 1) && zbeg >= 1 && zend >= zbeg && zoff >= 0, MGX_ERR_INVALID,
                 "relax_zero_colour_slab: bad colour / plane range");
     if (zend == zbeg) return MGX_OK;
@@ -3202,7 +3212,7 @@ int residual_sumsq3d_slab(mgx_ctx* ctx, const real* v, const real* f, int sx, in
                           int zend, double* dev_out) {
     MGX_REQUIRE(ctx && v && f && h && dev_out, MGX_ERR_INVALID, "residual_sumsq_slab: NULL argument");
     MGX_USE(ctx);
-    MGX_REQUIRE(valid_size(sx) && valid_size(sy), MGX_ERR_SIZE, "residual_sumsq_slab: sizes %d x %d are not 2^k+1", sx, sy);
+    MGX_REQUIRE(valid_size(sx) && valid_size(sy), MGX_ERR_SIZE, "residual_sumsq_slab: sizes %d x %d are not odd and >= 3", sx, sy);
     MGX_REQUIRE(zbeg >= 1 && zend >= zbeg, MGX_ERR_INVALID, "residual_sumsq_slab: bad plane range");
     MGX_REQUIRE(mode == MGX_RESIDUAL_REF_COMPAT || mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "bad residual mode %d", mode);
     if (zend == zbeg) {
@@ -3280,7 +3290,7 @@ static bool corr_fused_takes(const mgx_ctx* ctx, int sx, int sy, int sz_global, 
 // pairs per tile of the correcting red pass on a level of sx-point rows
 template <class real>
 static int corr_tile_pairs(const mgx_ctx* ctx, int sx) {
-    return sizeof(real) == 4 && ctx->relax_v2 && ctx->corr_v2 && (sx + 1) / 2 - 1 >= 256 ? 256 : 128;
+    return ctx->corr_v2 && pipe_v2_takes<real>(ctx, sx) ? 256 : 128;
 }
 template <class real>
 static void corr_pset_launch(mgx_ctx* ctx, real* v, int sx, int sy, int fzoff, const real* coarse_v, const int cn[3], int czoff, int zmin,

@@ -766,8 +766,11 @@ static int sweep3d_mid_launch(mgx_ctx* ctx, const real* vin, real* vout, const r
     MGX_REQUIRE(sweep3d_mid_tile<real>(sx, sy, sz, &TY, &TZ, 129), MGX_ERR_SIZE, "sweep3d_mid: level %d x %d x %d does not take the kernel", sx, sy, sz);
     const size_t lds = (size_t)((sx + 1) / 2) * ((TY + 4) * (TZ + 4) + (TY + 2) * (TZ + 2)) * sizeof(real);
     const int gy = ceil_div(sy - 2, TY), gz = ceil_div(sz - 2, TZ);
-    const int threads = (size_t)TY * TZ * ((sx + 1) / 2) >= 2048 ? 1024 : 512;
-    MGX_REQUIRE((TY + 2) * (TZ + 2) * ((sx + 1) / 2) <= 4 * threads, MGX_ERR_SIZE, "sweep3d_mid: tile %d x %d of %d-point rows has more than 4 items per thread",
+    // 512 threads for small tiles, unless the red items of the tile (sweep3d_mid_tile bounds them by 4 per thread of 1024) need
+    // more: rows whose pair count is no power of two (75 points: 10 x 6 lines of 38 entries on a 8 x 4 tile) do
+    const int items = (TY + 2) * (TZ + 2) * ((sx + 1) / 2);
+    const int threads = (size_t)TY * TZ * ((sx + 1) / 2) >= 2048 || items > 4 * 512 ? 1024 : 512;
+    MGX_REQUIRE(items <= 4 * threads, MGX_ERR_SIZE, "sweep3d_mid: tile %d x %d of %d-point rows has more than 4 items per thread",
                 TY, TZ, sx);
     if (lds > 64 * 1024) {
         MGX_HIP(hipFuncSetAttribute((const void*)sweep3d_xs_mid_kernel<real, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -812,7 +815,7 @@ int relax3d_xs_pp(mgx_ctx* ctx, real* v, real* w, const real* f, const int n[3],
     MGX_REQUIRE(v != w, MGX_ERR_INVALID, "relax_pp3d: v and w must differ");
     MGX_USE(ctx);
     MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "relax_pp3d: ncycles = %d < 0", ncycles);
-    for (int d = 0; d < 3; d++) MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "relax_pp3d: size[%d] = %d is not 2^k+1 >= 3", d, n[d]);
+    for (int d = 0; d < 3; d++) MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "relax_pp3d: size[%d] = %d is not odd and >= 3", d, n[d]);
     // a call the resident kernel takes (all passes in one launch, in place: mgx_resident3d.hip) needs no partner array
     const int shape = ncycles >= 2 && !relax3d_resident_takes(ctx, n, ncycles) ? sweep3d_shape<real>(ctx, n[0], n[1], n[2]) : 0;
     if (!shape) return relax3d_xs_colour_passes<real>(ctx, v, f, n, h, ncycles);
@@ -855,7 +858,7 @@ int relax3d_xs_from_zero_pp(mgx_ctx* ctx, real* v, real* w, const real* f, const
     MGX_REQUIRE(ctx && v && w && f && h && n, MGX_ERR_INVALID, "relax_from_zero_pp3d: NULL argument");
     MGX_REQUIRE(v != w, MGX_ERR_INVALID, "relax_from_zero_pp3d: v and w must differ");
     MGX_USE(ctx);
-    for (int d = 0; d < 3; d++) MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "relax_from_zero_pp3d: size[%d] = %d is not 2^k+1 >= 3", d, n[d]);
+    for (int d = 0; d < 3; d++) MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "relax_from_zero_pp3d: size[%d] = %d is not odd and >= 3", d, n[d]);
     const int shape = from_zero_pp_takes<real>(ctx, n, ncycles, rim_is_zero) ? SWEEP_MID : 0;
     if (shape != SWEEP_MID) return relax3d_xs_from_zero<real>(ctx, v, f, n, h, ncycles, rim_is_zero);
     const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];

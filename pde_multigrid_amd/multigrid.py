@@ -595,9 +595,9 @@ class MultiGrid3D(_MGBase):
         self._sfx, self._ct = _ct(dtype)
         self._G, self._M = _grid3_struct(self._ct)
         self._mg = C.POINTER(self._M)()
-        fn = getattr(lib, "mgMultiGrid3D_%s_create_layout" % self._sfx)
+        fn = getattr(lib, "mgMultiGrid3D_%s_create_levels" % self._sfx)
         lay = {"natural": 0, "xsplit": 1}[layout]
-        check(fn(ctx._h, _ip(finestGridSizeXYZ), _rp(rng, self._ct), C.c_int(lay), C.byref(self._mg)))
+        check(fn(ctx._h, _ip(finestGridSizeXYZ), _rp(rng, self._ct), C.c_int(lay), C.c_int(int(nlevels)), C.byref(self._mg)))
         if nlevels:
             self.numGrids = nlevels
         self._mg.contents.residual_mode = int(residual_mode)

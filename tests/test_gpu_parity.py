@@ -331,10 +331,12 @@ def test_3d_relax_from_zero(ctx, layout, dtype, n3):
         ctx.set_param("relax3d.zero_first", 1)
 
 
-@pytest.mark.parametrize("n3", [(513, 129, 17), (1025, 129, 17), (513, 257, 9), (2049, 129, 9), (513, 513, 33)])
+@pytest.mark.parametrize("n3", [(513, 129, 17), (1025, 129, 17), (513, 257, 9), (2049, 129, 9), (513, 513, 33), (769, 129, 17),
+                                (771, 129, 17)])
 def test_3d_xsplit_relax_fp32_two_pairs_per_lane(ctx, n3):
     """relax3d_xs_pipe_v2_kernel (fp32 on wide levels: a lane owns two x-pairs, 8-byte loads) == oracle == the one-pair
-    kernel, on rows that do and do not fill the 256-pair tiles, with every run length of the plane march"""
+    kernel, on rows that do (256, 512, 1024 pairs) and do not (384, 385) fill the 256-pair tiles, with every run length of
+    the plane march.  A lane owns both pairs of its slot or none, so rows with an odd pair count (771) take the one-pair kernel"""
     rg = [-1, 1, 0, 2, 0.5, 3]
     rng = np.random.default_rng(sum(n3))
     v = rng.uniform(-1, 1, O.shape(n3)).astype(np.float32)
@@ -347,7 +349,7 @@ def test_3d_xsplit_relax_fp32_two_pairs_per_lane(ctx, n3):
                 ctx.set_param("relax3d.zchunk", zchunk)
                 assert bits_equal(P.ops3dxs.relax(ctx, v, f, n3, rg, 2), want), (v2, zchunk)
                 if v2 and zchunk == 0 and n3[2] - 2 >= 8:
-                    assert "v2" in ctx.last_relax_kernel()
+                    assert ("v2" in ctx.last_relax_kernel()) == ((n3[0] - 1) // 2 % 2 == 0), ctx.last_relax_kernel()
     finally:
         ctx.set_param("relax3d.v2", 1)
         ctx.set_param("relax3d.zchunk", 0)
