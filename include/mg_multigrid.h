@@ -98,6 +98,18 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
         /* boundary points.  Cleared by everything that may write either array's boundary.  External      */ \
         /* writers of d_v / d_e through the raw device pointers must clear it (and v_rim_zero) themselves. */ \
         unsigned char e_rim_valid[MG_MAX_LEVELS];                                                        \
+        /* internal: scratch of PCG (level-0 arrays in the hierarchy's layout, allocated by the first    */ \
+        /* call, freed by _destroy): the iterate x, a copy of the right-hand side b, the direction p,    */ \
+        /* q = A p; the CG state (MGX_CG_STATE doubles) and the reduction scratch; the graph of its      */ \
+        /* preconditioning V-cycle (kept apart from graph_exec[0], which holds VCycle's)                  */ \
+        real* pcg_x;                                                                                     \
+        real* pcg_b;                                                                                     \
+        real* pcg_p;                                                                                     \
+        real* pcg_q;                                                                                     \
+        double* pcg_state;                                                                               \
+        double* pcg_work;                                                                                \
+        void* pcg_graph_exec;                                                                            \
+        long long pcg_graph_key;                                                                         \
     } mgMultiGrid3D_##R;                                                                                 \
     int mgMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6],     \
                                    mgMultiGrid3D_##R** out);                                             \
@@ -135,6 +147,20 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
     /* relative L2 of diff = sin(pi x) sin(pi y) sin(pi z) - v over all points of level gridID              */ \
     int mgMultiGrid3D_##R##_DiffStats(mgMultiGrid3D_##R* mg, int gridID, double* mean_abs,               \
                                       double* max_abs, double* rel_l2);                                  \
+    /* PCG (an addition: the reference only cycles): solves A v = f on level 0 to a relative residual   */ \
+    /* ||f - A v|| / ||f - A v0|| < tol by flexible CG (Polak-Ribiere beta) preconditioned by one       */ \
+    /* VCycle(0, v1, v2) from zero per iteration (krylov != 0), or by plain VCycle(0, v1, v2) cycling   */ \
+    /* (krylov = 0).  Needs layout = 1 and residual_mode = MGX_RESIDUAL_CORRECT.  The initial guess is   */ \
+    /* d_v[0], whose boundary holds the Dirichlet data and is never changed; on return d_v[0] holds the */ \
+    /* solution and d_f[0] its old contents, bit for bit.  *iters = iterations (cycles) run; *rel_res = */ \
+    /* the TRUE relative residual of the result (a recursive residual below tol is re-checked against  */ \
+    /* f - A v, and the iteration goes on from the true residual when that is not below tol);          */ \
+    /* host_hist[k] (k < hist_cap) = relative residual after iteration k + 1 (recursive for CG).  A     */ \
+    /* breakdown (<p, q> zero or not finite) returns MGX_OK with *converged = 0.  use_graph captures   */ \
+    /* the preconditioning V-cycle.  Blocking: the host reads one double per iteration.                */ \
+    int mgMultiGrid3D_##R##_PCG(mgMultiGrid3D_##R* mg, int v1, int v2, double tol, int maxit, int krylov, \
+                                int* iters, double* rel_res, int* converged, double* host_hist,          \
+                                int hist_cap);                                                           \
     /* solve(grid, rhs, nlevels): host arrays in the reference layout; grid = initial guess incl.     */ \
     /* boundary values on input, solution on output; nlevels = 0 -> reference rule; ncycles V(v1,v2)  */ \
     /* cycles from the given guess, or one FullMultiGridVCycle(v0,v1,v2) when fmg != 0.               */ \
@@ -148,6 +174,12 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
     int mg3d_solve_from_zero_##R(mgx_ctx* ctx, real* grid_out, const real* rhs, const int sizeXYZ[3],    \
                                  const real range[6], int nlevels, int fmg, int v0, int v1, int v2,      \
                                  int ncycles, int residual_mode);                                        \
+    /* solve_pcg: mgMultiGrid3D_<r>_PCG on a hierarchy built for the call (x-split, CORRECT residual);   */ \
+    /* grid = initial guess with its Dirichlet boundary on input, solution on output; host arrays in    */ \
+    /* the reference layout; rhs == NULL: the reference's own right-hand side                           */ \
+    int mg3d_solve_pcg_##R(mgx_ctx* ctx, real* grid, const real* rhs, const int sizeXYZ[3],              \
+                           const real range[6], int nlevels, int v1, int v2, double tol, int maxit,      \
+                           int krylov, int* iters, double* rel_res, int* converged);                     \
     /* ---- z-slab decomposed 3D V-cycle (one process per GPU; csrc/host/mg_dist3d.inc) ---- */         \
     typedef struct mgSlab3D_##R {                                                                        \
         real* d_v; /* local planes [zoff, zoff+nzl) of the level, x-split layout, ghosts included */     \

@@ -447,10 +447,42 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     int mgx2d_init_v_##SFX(mgx_ctx* ctx, real* v, const int n[2], const real h[2], const real a[2]);    \
     int mgx2d_mean_abs_error_##SFX(mgx_ctx* ctx, const real* v, const int n[2], const real h[2],        \
                                    const real a[2], double* host_mean);                                 \
-    int mgx_norm2_##SFX(mgx_ctx* ctx, const real* x, size_t count, double* host_sumsq);
+    int mgx_norm2_##SFX(mgx_ctx* ctx, const real* x, size_t count, double* host_sumsq);                \
+    /* ---- vector kernels of the preconditioned CG solve (mgMultiGrid3D_<r>_PCG), x-split layout ----  */ \
+    /* Interior points only: boundary and pad entries are neither read as data nor written.  Sums are  */ \
+    /* accumulated in double in a fixed order (per-block partials in dev_work, then one final kernel), */ \
+    /* so a call gives the same bits on every run.  dev_work: mgx3dxs_krylov_work_elems doubles of    */ \
+    /* device scratch; dev_sum / dev_alpha / dev_beta: device doubles.  Asynchronous on the compute    */ \
+    /* stream.  An addition: the reference has no Krylov solver.                                       */ \
+    size_t mgx3dxs_krylov_work_elems_##SFX(const int n[3]);                                             \
+    /* laplace_dot: q = A p with A the Laplacian of MGX_RESIDUAL_CORRECT (q is bit-identical to        */ \
+    /* -mgx3dxs_residual(p, f = 0, CORRECT)); *dev_sum = <p, q>.  p's boundary is read, q's is not     */ \
+    /* written.                                                                                         */ \
+    int mgx3dxs_laplace_dot_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3], const real h[3], \
+                                  double* dev_work, double* dev_sum);                                   \
+    /* cg_update: x += a p (skipped when x is NULL), r -= a q with a = (real)*dev_alpha;               */ \
+    /* *dev_sum = <r, r> of the new r                                                                   */ \
+    int mgx3dxs_cg_update_##SFX(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q,           \
+                                const int n[3], const double* dev_alpha, double* dev_work,              \
+                                double* dev_sum);                                                       \
+    /* dot2: dev_sum[0] = <a, b> and, unless c is NULL, dev_sum[1] = <a, c> (one pass over a)          */ \
+    int mgx3dxs_dot2_##SFX(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3],   \
+                           double* dev_work, double* dev_sum);                                          \
+    /* cg_direction: x += (real)*dev_alpha * p with the old p (skipped when x is NULL), then, unless z  */ \
+    /* is NULL, p = z + (real)*dev_beta * p, or p = z when dev_beta is NULL                             */ \
+    int mgx3dxs_cg_direction_##SFX(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3],       \
+                                   const double* dev_alpha, const double* dev_beta);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)
+
+/* State vector of the flexible CG solve, MGX_CG_STATE device doubles, and its scalar steps (one thread, on the compute stream):
+ *   step 0: alpha = RZ / PQ; NaN when PQ is 0 or alpha or PQ is not finite (a breakdown: the following cg_update then
+ *           reports a NaN norm);
+ *   step 1: beta = -alpha ZQ / RZ (Polak-Ribiere: = <z, r_new - r_old> / <r_old, z_old>), then RZ = ZR;
+ *   step 2: RZ = ZR (restart). */
+enum { MGX_CG_RZ = 0, MGX_CG_PQ = 1, MGX_CG_ALPHA = 2, MGX_CG_RR = 3, MGX_CG_ZR = 4, MGX_CG_ZQ = 5, MGX_CG_BETA = 6, MGX_CG_STATE = 8 };
+int mgx_cg_scalars(mgx_ctx* ctx, double* dev_state, int step);
 
 /* ---- multi-GPU: z-slab halo exchange over RCCL (xGMI) ------------------------------
  * One process per GPU.  The unique id is created on rank 0 (mgx_comm_unique_id) and

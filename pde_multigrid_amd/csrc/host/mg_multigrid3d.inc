@@ -140,6 +140,9 @@ void FN(destroy)(MGRID* mg) {
     if (!mg) return;
     for (int i = 0; i < MG_MAX_LEVELS; i++)
         if (mg->graph_exec[i]) mgx_graph_destroy(mg->ctx, mg->graph_exec[i]);
+    if (mg->pcg_graph_exec) mgx_graph_destroy(mg->ctx, mg->pcg_graph_exec);
+    mgx_free(mg->ctx, mg->pcg_x); mgx_free(mg->ctx, mg->pcg_b); mgx_free(mg->ctx, mg->pcg_p); mgx_free(mg->ctx, mg->pcg_q);
+    mgx_free(mg->ctx, mg->pcg_state); mgx_free(mg->ctx, mg->pcg_work);
     if (mg->grids3D)
         for (int i = 0; i < mg->maxGrids; i++) MG_CAT(grid3_free_, R)(mg->ctx, mg->grids3D[i]);
     free(mg->grids3D);
@@ -222,7 +225,8 @@ int FN(ApplyCorrection)(MGRID* mg, REAL* fine, const int fsizeXYZ[3], const REAL
 
 /* use_graph: the cycle that starts at gridID is captured once into a HIP graph and replayed; the key holds every
  * host-side input of the launch sequence (the device arrays and their sizes are fixed for the hierarchy's life) */
-static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int (*body)(MGRID*, int, int, int)) {
+static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int (*body)(MGRID*, int, int, int), void** slot_exec,
+                                     long long* slot_key, long long extra) {
     long long obits = 0;
     memcpy(&obits, &mg->omega, sizeof(REAL));
     long long key = 1 + (((long long)v1 & 0xfff) | (((long long)v2 & 0xfff) << 12) | ((long long)mg->numGrids << 24) |
@@ -230,9 +234,10 @@ static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int 
                                ((long long)mg->smoother << 33)) + obits * 1000003LL;
     for (int i = gridID + 1; i < mg->numGrids; i++) key = key * 5 + mg->f_rim_zero[i] + 2 * mg->v_rim_zero[i]; /* pick kernel forms */
     for (int i = gridID; i < mg->numGrids; i++) key = key * 3 + mg->e_rim_valid[i]; /* a boundary copy is part of the sequence or not */
-    if (!mg->graph_exec[gridID] || mg->graph_key[gridID] != key) {
-        if (mg->graph_exec[gridID]) MG_TRY(mgx_graph_destroy(mg->ctx, mg->graph_exec[gridID]));
-        mg->graph_exec[gridID] = NULL;
+    key = key * 7 + extra; /* what else the caller's body depends on */
+    if (!*slot_exec || *slot_key != key) {
+        if (*slot_exec) MG_TRY(mgx_graph_destroy(mg->ctx, *slot_exec));
+        *slot_exec = NULL;
         MG_TRY(mgx_graph_begin(mg->ctx));
         mg->capturing = 1;
         const int st = body(mg, gridID, v1, v2);
@@ -244,10 +249,10 @@ static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int 
             return st;
         }
         MG_TRY(st2);
-        mg->graph_exec[gridID] = exec;
-        mg->graph_key[gridID] = key;
+        *slot_exec = exec;
+        *slot_key = key;
     }
-    return mgx_graph_launch(mg->ctx, mg->graph_exec[gridID]);
+    return mgx_graph_launch(mg->ctx, *slot_exec);
 }
 
 /* VCycle from level gridID down.  v_zero: the level's v counts as all zeros (the coarse error of :634) but has not been
@@ -342,7 +347,8 @@ int FN(VCycle)(MGRID* mg, int gridID, int v1, int v2) {
                mg ? mg->numGrids : -1, mg ? mg->maxGrids : -1);
     MG_REQUIRE(gridID >= 0 && gridID < mg->numGrids, MGX_ERR_INVALID, "VCycle: bad gridID %d", gridID);
     MG_REQUIRE(v1 >= 0 && v2 >= 0, MGX_ERR_INVALID, "VCycle: negative sweep count");
-    if (mg->use_graph && !mg->capturing) return MG_CAT(vcycle_graph3_, R)(mg, gridID, v1, v2, FN(VCycle));
+    if (mg->use_graph && !mg->capturing)
+        return MG_CAT(vcycle_graph3_, R)(mg, gridID, v1, v2, FN(VCycle), &mg->graph_exec[gridID], &mg->graph_key[gridID], 0);
     return MG_CAT(vcycle_body3_, R)(mg, gridID, v1, v2, 0);
 }
 
@@ -463,6 +469,191 @@ int FN(DiffStats)(MGRID* mg, int gridID, double* mean_abs, double* max_abs, doub
     if (max_abs) *max_abs = out[1];
     if (rel_l2) *rel_l2 = out[3] > 0 ? sqrt(out[2] / out[3]) : sqrt(out[2]);
     return MGX_OK;
+}
+
+/* ---------------------------------------------------------------- PCG (an addition: the reference only cycles) */
+/* preconditioner body: VCycle(gridID, v1, v2) with v[gridID] counting as zero (the graph helper's body signature) */
+static int MG_CAT(pcg_vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2) {
+    return MG_CAT(vcycle_body3_, R)(mg, gridID, v1, v2, 1);
+}
+
+/* z = M r: d_v[0] := VCycle from zero with d_f[0] = r */
+static int MG_CAT(pcg_precond3_, R)(MGRID* mg, int v1, int v2) {
+    if (mg->use_graph)  /* the sequence also depends on whether d_v[0]'s boundary still has to be zeroed */
+        return MG_CAT(vcycle_graph3_, R)(mg, 0, v1, v2, MG_CAT(pcg_vcycle_body3_, R), &mg->pcg_graph_exec, &mg->pcg_graph_key,
+                                         1 + mg->v_rim_zero[0]);
+    return MG_CAT(vcycle_body3_, R)(mg, 0, v1, v2, 1);
+}
+
+/* ||b - A x||^2 of level 0 into *ss (blocking, no residual array) */
+static int MG_CAT(pcg_true_sumsq3_, R)(MGRID* mg, const REAL* x, const REAL* b, double* ss) {
+    GRID* g = mg->grids3D[0];
+    const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    MG_TRY(MG_CAT(mgx3dxs_residual_sumsq_slab_, R)(mg->ctx, x, b, g->sizeX, g->sizeY, h, MGX_RESIDUAL_CORRECT, 1, g->sizeZ - 1,
+                                                   mg->pcg_state + MGX_CG_RR));
+    return mgx_memcpy_d2h(mg->ctx, ss, mg->pcg_state + MGX_CG_RR, sizeof(double));
+}
+
+/* krylov = 0: plain cycling of d_v[0] with the same stopping rule (the true residual after every cycle) */
+static int MG_CAT(pcg_plain3_, R)(MGRID* mg, int v1, int v2, double tol, int maxit, int* iters, double* rel_res, int* converged,
+                                  double* host_hist, int hist_cap) {
+    GRID* g = mg->grids3D[0];
+    double rr0 = 0.0, rr = 0.0;
+    MG_TRY(MG_CAT(pcg_true_sumsq3_, R)(mg, g->d_v, g->d_f, &rr0));
+    if (rr0 == 0.0) { *converged = 1; return MGX_OK; }
+    for (int k = 1; k <= maxit; k++) {
+        MG_TRY(FN(VCycle)(mg, 0, v1, v2));
+        MG_TRY(MG_CAT(pcg_true_sumsq3_, R)(mg, g->d_v, g->d_f, &rr));
+        const double rel = sqrt(rr / rr0);
+        if (k - 1 < hist_cap) host_hist[k - 1] = rel;
+        *iters = k;
+        *rel_res = rel;
+        if (rel < tol) { *converged = 1; break; }
+        if (!isfinite(rel)) break;
+    }
+    return MGX_OK;
+}
+
+static int MG_CAT(pcg_alloc3_, R)(MGRID* mg) {
+    if (mg->pcg_x) return MGX_OK;
+    GRID* g = mg->grids3D[0];
+    const size_t bytes = MG_CAT(dvol3_, R)(mg->layout, g) * sizeof(REAL);
+    const size_t wbytes = MG_CAT(mgx3dxs_krylov_work_elems_, R)(g->sizeXYZ) * sizeof(double);
+    int st;
+    if ((st = mgx_malloc(mg->ctx, bytes, (void**)&mg->pcg_x)) || (st = mgx_malloc(mg->ctx, bytes, (void**)&mg->pcg_b)) ||
+        (st = mgx_malloc(mg->ctx, bytes, (void**)&mg->pcg_p)) || (st = mgx_malloc(mg->ctx, bytes, (void**)&mg->pcg_q)) ||
+        (st = mgx_malloc(mg->ctx, MGX_CG_STATE * sizeof(double), (void**)&mg->pcg_state)) ||
+        (st = mgx_malloc(mg->ctx, wbytes, (void**)&mg->pcg_work)) ||
+        /* p and q: their boundary and pad entries are never written by the kernels; zero them once (q's boundary is read */
+        /* by nobody, p's by the Laplacian as zero Dirichlet data) */
+        (st = mgx_memset_zero(mg->ctx, mg->pcg_p, bytes)) || (st = mgx_memset_zero(mg->ctx, mg->pcg_q, bytes)) ||
+        (st = mgx_memset_zero(mg->ctx, mg->pcg_state, MGX_CG_STATE * sizeof(double)))) {
+        mgx_free(mg->ctx, mg->pcg_x); mgx_free(mg->ctx, mg->pcg_b); mgx_free(mg->ctx, mg->pcg_p); mgx_free(mg->ctx, mg->pcg_q);
+        mgx_free(mg->ctx, mg->pcg_state); mgx_free(mg->ctx, mg->pcg_work);
+        mg->pcg_x = mg->pcg_b = mg->pcg_p = mg->pcg_q = NULL;
+        mg->pcg_state = mg->pcg_work = NULL;
+        return st;
+    }
+    return MGX_OK;
+}
+
+/* flexible CG (the algorithm of mg_multigrid.h).  r lives in d_f[0] (the preconditioner's right-hand side), z in d_v[0] (its
+ * result); x, a copy of b, p and q in the scratch.  The update of x by alpha p is deferred into the next direction pass
+ * (x += alpha p; p = z + beta p in one pass over p), so an iteration streams 13 reals per point outside the V-cycle:
+ * laplace_dot 2, cg_update 3 (r, q -> r), dot2 3 (z, r, q), cg_direction 5 (x, p, z -> x, p). */
+static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int maxit, int* iters, double* rel_res, int* converged,
+                                   double* host_hist, int hist_cap) {
+    mgx_ctx* ctx = mg->ctx;
+    GRID* g = mg->grids3D[0];
+    const int* n = g->sizeXYZ;
+    const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    const size_t bytes = MG_CAT(dvol3_, R)(mg->layout, g) * sizeof(REAL);
+    REAL *x = mg->pcg_x, *b = mg->pcg_b, *p = mg->pcg_p, *q = mg->pcg_q, *r = g->d_f, *z = g->d_v;
+    double *s = mg->pcg_state, *w = mg->pcg_work;
+    const unsigned char v_rim0 = mg->v_rim_zero[0], f_rim0 = mg->f_rim_zero[0];
+    MG_TRY(mgx_memcpy_d2d(ctx, x, g->d_v, bytes)); /* x: the guess with its Dirichlet boundary; pads are zero in both */
+    MG_TRY(mgx_memcpy_d2d(ctx, b, g->d_f, bytes));
+    int st = MGX_OK;
+    double rr0 = 0.0, rr = 0.0;
+    int pending = 0; /* x still lacks alpha p of the last iteration */
+    /* r = b - A x (0 on the boundary), ||r0|| */
+    st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
+    mg->f_rim_zero[0] = 0;
+    if (!st) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
+    if (!st) st = mgx_memcpy_d2h(ctx, &rr0, s + MGX_CG_RR, sizeof(double));
+    if (!st && rr0 == 0.0) *converged = 1;
+    int restart = 1; /* z = M r, p = z, rz = <r, z> */
+    for (int k = 1; !st && !*converged && k <= maxit; k++) {
+        if (restart) {
+            st = MG_CAT(pcg_precond3_, R)(mg, v1, v2);
+            if (!st) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, z, r, NULL, n, w, s + MGX_CG_ZR);
+            if (!st) st = mgx_cg_scalars(ctx, s, 2);
+            if (!st) st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, NULL, p, z, n, NULL, NULL);
+            restart = 0;
+        }
+        /* q = A p, alpha = <r, z> / <p, q>; r -= alpha q */
+        if (!st) st = MG_CAT(mgx3dxs_laplace_dot_, R)(ctx, p, q, n, h, w, s + MGX_CG_PQ);
+        if (!st) st = mgx_cg_scalars(ctx, s, 0);
+        if (!st) st = MG_CAT(mgx3dxs_cg_update_, R)(ctx, NULL, p, r, q, n, s + MGX_CG_ALPHA, w, s + MGX_CG_RR);
+        if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double)); /* the one host read of the iteration */
+        if (st) break;
+        *iters = k;
+        if (!isfinite(rr)) break; /* breakdown: alpha was NaN; x is the previous iterate */
+        pending = 1;
+        const double rel = sqrt(rr / rr0);
+        if (k - 1 < hist_cap) host_hist[k - 1] = rel;
+        if (rel < tol) { /* the recursive residual may have drifted from b - A x: check the true one */
+            st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL);
+            pending = 0;
+            if (!st) st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
+            if (!st) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
+            if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double));
+            if (!st && sqrt(rr / rr0) < tol) *converged = 1;
+            restart = 1; /* otherwise go on from the true residual */
+            continue;
+        }
+        /* z = M r; beta = -alpha <z, q> / <r, z>_old; x += alpha p; p = z + beta p */
+        st = MG_CAT(pcg_precond3_, R)(mg, v1, v2);
+        if (!st) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, z, r, q, n, w, s + MGX_CG_ZR);
+        if (!st) st = mgx_cg_scalars(ctx, s, 1);
+        if (!st) st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, z, n, s + MGX_CG_ALPHA, s + MGX_CG_BETA);
+        pending = 0;
+    }
+    if (!st && pending) st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL);
+    /* the true relative residual of the result */
+    if (!st && rr0 > 0.0) {
+        double ss = 0.0;
+        st = MG_CAT(pcg_true_sumsq3_, R)(mg, x, b, &ss);
+        if (!st) *rel_res = sqrt(ss / rr0);
+    } else if (!st && rr0 != 0.0) {
+        *rel_res = rr0; /* NaN: the initial residual is not finite */
+    }
+    /* d_v[0] := x (its boundary is the guess's), d_f[0] := b; their flags as they were (same boundary contents); d_e's */
+    /* boundary copy no longer matches d_v's */
+    const int st2 = mgx_memcpy_d2d(ctx, g->d_v, x, bytes);
+    const int st3 = mgx_memcpy_d2d(ctx, g->d_f, b, bytes);
+    mg->v_rim_zero[0] = v_rim0;
+    mg->f_rim_zero[0] = f_rim0;
+    mg->e_rim_valid[0] = 0;
+    if (!st) st = st2 ? st2 : st3;
+    if (!st) st = mgx_ctx_sync(ctx);
+    return st;
+}
+
+int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* iters, double* rel_res, int* converged, double* host_hist,
+            int hist_cap) {
+    MG_REQUIRE(mg && iters && rel_res && converged && (host_hist || hist_cap <= 0), MGX_ERR_INVALID, "PCG: NULL argument");
+    MG_REQUIRE(mg->numGrids >= 1 && mg->numGrids <= mg->maxGrids, MGX_ERR_INVALID, "PCG: numGrids = %d outside [1,%d]", mg->numGrids,
+               mg->maxGrids);
+    MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "PCG: needs the x-split layout (layout = 1)");
+    MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "PCG: needs residual_mode = MGX_RESIDUAL_CORRECT");
+    MG_REQUIRE(tol > 0 && maxit >= 1 && v1 >= 0 && v2 >= 0 && v1 + v2 >= 1, MGX_ERR_INVALID,
+               "PCG: bad arguments (tol %g, maxit %d, v1 %d, v2 %d)", tol, maxit, v1, v2);
+    *iters = 0;
+    *rel_res = 0.0;
+    *converged = 0;
+    MG_TRY(MG_CAT(pcg_alloc3_, R)(mg));
+    if (!krylov) return MG_CAT(pcg_plain3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);
+    return MG_CAT(pcg_krylov3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);
+}
+
+int MG_CAT(mg3d_solve_pcg_, R)(mgx_ctx* ctx, REAL* grid, const REAL* rhs, const int sizeXYZ[3], const REAL range[6], int nlevels, int v1,
+                               int v2, double tol, int maxit, int krylov, int* iters, double* rel_res, int* converged) {
+    MG_REQUIRE(ctx && grid && sizeXYZ && range, MGX_ERR_INVALID, "mg3d_solve_pcg: NULL argument");
+    MGRID* mg = NULL;
+    MG_TRY(FN(create_levels)(ctx, sizeXYZ, range, 1, nlevels, &mg));
+    int st = MGX_OK;
+    if (nlevels > 0) {
+        if (nlevels > mg->maxGrids) st = mg_fail(MGX_ERR_SIZE, "mg3d_solve_pcg: nlevels %d > %d", nlevels, mg->maxGrids);
+        else mg->numGrids = nlevels;
+    }
+    mg->residual_mode = MGX_RESIDUAL_CORRECT;
+    if (!st) st = FN(upload_v)(mg, 0, grid);
+    if (!st && rhs) st = FN(upload_f)(mg, 0, rhs);
+    if (!st) st = FN(PCG)(mg, v1, v2, tol, maxit, krylov, iters, rel_res, converged, NULL, 0);
+    if (!st) st = FN(download_v)(mg, 0, grid);
+    FN(destroy)(mg);
+    return st;
 }
 
 static int MG_CAT(solve3_, R)(mgx_ctx* ctx, REAL* grid, const REAL* rhs, const int sizeXYZ[3], const REAL range[6], int nlevels,

@@ -399,6 +399,68 @@ class _Ops3D(_Ops):
         return float(out.value)
 
 
+    # ---- vector kernels of the preconditioned CG solve (x-split only; every array in the reference layout on the host)
+    def _krylov_work(self, ctx, n, dtype):
+        s, _ = _ct(dtype)
+        fn = getattr(lib, "mgx3dxs_krylov_work_elems_" + s)
+        fn.restype = C.c_size_t
+        return ctx.to_device(np.zeros(max(int(fn(_ip(n))), 1), np.float64))
+
+    def _krylov(self, ctx, n, arrays, scalars, call, dtype, nsum):
+        """upload arrays (x-split) and the device doubles `scalars`, run call(work, sums, *scalar ptrs, *array ptrs), return
+        (arrays as stored, padded rows, sums)"""
+        assert self.xsplit, "the Krylov kernels exist for the x-split layout only"
+        work = self._krylov_work(ctx, n, dtype)
+        dev = [ctx.to_device(np.array(scalars + [0.0] * nsum, np.float64))]
+        ptrs = [ctx.to_device(a) if a is not None else None for a in arrays]
+        try:
+            sp = [C.c_void_p(dev[0].value + 8 * i) for i in range(len(scalars) + nsum)]
+            check(call(work, *sp, *ptrs))
+            sums = ctx.to_host(dev[0], (len(scalars) + nsum,), np.float64)[len(scalars):]
+            return [ctx.to_host(p, a.shape, dtype) if p is not None else None for p, a in zip(ptrs, arrays)], sums
+        finally:
+            for p in ptrs + dev + [work]:
+                if p is not None:
+                    ctx.free(p)
+
+    def laplace_dot(self, ctx, p, n, rng, q=None, packed=False, dtype=None):
+        """q = A p (CORRECT Laplacian) and <p, q>: returns (q, pq).  q: the array written into (default zeros; its boundary
+        and pad entries are left as they are).  packed=True: p and q are given, and q returned, as stored (x-split)."""
+        dtype = dtype or p.dtype
+        fn, ct = self._fn("laplace_dot", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        pp = p if packed else xs_pack(np.ascontiguousarray(p, dtype))
+        qq = np.zeros_like(pp) if q is None else (q if packed else xs_pack(np.ascontiguousarray(q, dtype)))
+        (_, qo), sums = self._krylov(ctx, n, [pp, qq], [], lambda w, s0, a, b: fn(ctx._h, a, b, _ip(n), h, w, s0), dtype, 1)
+        return (qo if packed else xs_unpack(qo, n[0])), float(sums[0])
+
+    def cg_update(self, ctx, x, p, r, q, n, alpha, dtype=None):
+        """x += (real)alpha p (x None: skipped); r -= (real)alpha q; arrays packed (x-split).  Returns (x, r, <r, r>)."""
+        dtype = dtype or r.dtype
+        fn, _ = self._fn("cg_update", dtype)
+        (xo, _, ro, _), sums = self._krylov(ctx, n, [x, p, r, q], [float(alpha)],
+                                            lambda w, a, s0, xp, pp, rp, qp: fn(ctx._h, xp, pp, rp, qp, _ip(n), a, w, s0), dtype, 1)
+        return xo, ro, float(sums[0])
+
+    def dot2(self, ctx, a, b, c, n, dtype=None):
+        """(<a, b>, <a, c>) over the interior (c None: <a, c> is None); arrays packed (x-split)"""
+        dtype = dtype or a.dtype
+        fn, _ = self._fn("dot2", dtype)
+        _, sums = self._krylov(ctx, n, [a, b, c], [], lambda w, s0, s1, ap, bp, cp: fn(ctx._h, ap, bp, cp, _ip(n), w, s0), dtype, 2)
+        return float(sums[0]), (float(sums[1]) if c is not None else None)
+
+    def cg_direction(self, ctx, x, p, z, n, alpha=None, beta=None, dtype=None):
+        """x += (real)alpha p (x None: skipped); then p = z + (real)beta p, or p = z when beta is None (z None: p kept);
+        arrays packed (x-split).  Returns (x, p)."""
+        dtype = dtype or p.dtype
+        fn, _ = self._fn("cg_direction", dtype)
+
+        def call(w, a, b, xp, pp, zp):
+            return fn(ctx._h, xp, pp, zp, _ip(n), a if alpha is not None else None, b if beta is not None else None)
+        (xo, po, _), _ = self._krylov(ctx, n, [x, p, z], [float(alpha or 0.0), float(beta or 0.0)], call, dtype, 0)
+        return xo, po
+
+
 class _Ops2D(_Ops):
     def __init__(self):
         super().__init__(2)
@@ -661,6 +723,18 @@ class MultiGrid3D(_MGBase):
         out = np.empty(_shape(self.size(gridID)), self.dtype)
         self._call("download_f", C.c_int(gridID), out.ctypes.data_as(C.c_void_p))
         return out
+
+    def PCG(self, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True):
+        """Solve on level 0 to a relative residual < tol from the guess in v[0] (its boundary = the Dirichlet data): flexible CG
+        preconditioned by one V(v1, v2) cycle from zero per iteration, or plain V-cycles with krylov=False.  Needs the x-split
+        layout and residual_mode=CORRECT.  Returns (iters, rel_res, converged, history): rel_res is the TRUE relative
+        residual of the result, history one relative residual per iteration."""
+        it, conv = C.c_int(), C.c_int()
+        rel = C.c_double()
+        hist = np.zeros(int(maxit), np.float64)
+        self._call("PCG", C.c_int(v1), C.c_int(v2), C.c_double(tol), C.c_int(maxit), C.c_int(int(bool(krylov))), C.byref(it),
+                   C.byref(rel), C.byref(conv), hist.ctypes.data_as(C.c_void_p), C.c_int(len(hist)))
+        return int(it.value), float(rel.value), bool(conv.value), hist[:it.value].copy()
 
 
 class MultiGrid2D(_MGBase):
@@ -971,6 +1045,20 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
                                                     C.c_int(int(fmg)), C.c_int(v0), C.c_int(v1), C.c_int(v2), C.c_int(ncycles),
                                                     C.c_int(residual_mode)))
     return out
+
+
+def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True):
+    """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged)"""
+    grid = np.ascontiguousarray(grid).copy()
+    s, ct = _ct(grid.dtype)
+    r = np.ascontiguousarray(rhs, grid.dtype).ctypes.data_as(C.c_void_p) if rhs is not None else None
+    n = tuple(reversed(grid.shape))
+    it, conv = C.c_int(), C.c_int()
+    rel = C.c_double()
+    check(getattr(lib, "mg3d_solve_pcg_" + s)(ctx._h, grid.ctypes.data_as(C.c_void_p), r, _ip(n), _rp(rng, ct), C.c_int(nlevels),
+                                              C.c_int(v1), C.c_int(v2), C.c_double(tol), C.c_int(maxit),
+                                              C.c_int(int(bool(krylov))), C.byref(it), C.byref(rel), C.byref(conv)))
+    return grid, int(it.value), float(rel.value), bool(conv.value)
 
 
 def solve2d(ctx, grid, rhs, rng, A, alfa, nlevels=0, fmg=False, v0=1, v1=2, v2=2, ncycles=1):

@@ -1,0 +1,351 @@
+"""GPU suite: the multigrid-preconditioned CG solve of the 3D hierarchy (mgMultiGrid3D_<r>_PCG) and its vector kernels.
+
+The kernels are checked against numpy restatements (bit for bit where the issue fixes the expression, to 1e-13 for the sums);
+the solver against flexible CG written out in numpy below, preconditioned by the oracle's own V-cycle (the GPU V-cycle is
+bit-identical to it, so a divergence can only come from the new code)."""
+import math
+
+import numpy as np
+import pytest
+
+import oracle as O
+import pde_multigrid_amd as P
+from conftest import bits_equal
+from odd_shapes import pack_poisoned, pads_unchanged
+from pde_multigrid_amd.multigrid import xs_unpack
+
+pytestmark = pytest.mark.gpu
+RG = [-1, 1, 0, 2, 0.5, 3]
+UNIT = [0, 1, 0, 1, 0, 1]
+DTYPES = [np.float64, np.float32]
+# cubic, 2^k + 1 non-cubic, odd but not 2^k + 1 (x-rows end inside a tile; the odd-x half has pads)
+SHAPES = [(17, 17, 17), (33, 17, 9), (23, 19, 13), (259, 9, 7), (515, 5, 5)]
+# the five grids of the issue: (sizeXYZ, range, levels; 0 = all).  49 x 41 x 57 reaches an even extent at its fourth level
+# (7 x 6 x 8), so its hierarchy has three.
+GRIDS = [((33, 33, 33), UNIT, 0), ((65, 65, 65), UNIT, 0), ((65, 65, 65), [0, 1, 0, 1, 0, 4], 0), ((65, 33, 129), UNIT, 0),
+         ((49, 41, 57), [0, 1, 0, 2, 0, 1], 3)]
+ANISO = GRIDS[2:]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = P.Context(0)
+    yield c
+    c.close()
+
+
+def _rand(n3, dtype, seed):
+    return np.random.default_rng(seed).uniform(-1, 1, O.shape(n3)).astype(dtype)
+
+
+def _interior(a):
+    return a[1:-1, 1:-1, 1:-1]
+
+
+def _boundary_mask(n3):
+    m = np.ones(O.shape(n3), bool)
+    m[1:-1, 1:-1, 1:-1] = False
+    return m
+
+
+def _fsum_dot(a, b):
+    return math.fsum((_interior(a).astype(np.float64) * _interior(b).astype(np.float64)).ravel())
+
+
+def _close(got, want, rtol):
+    return abs(got - want) <= rtol * max(abs(want), 1e-300)
+
+
+# ---------------------------------------------------------------------------------------------------------- kernels
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n3", SHAPES)
+@pytest.mark.parametrize("rg", ["aniso", "unit"])
+def test_laplace_dot(ctx, dtype, n3, rg):
+    rng = RG if rg == "aniso" else UNIT  # the unit cube on 2^k + 1 points: the exact-reciprocal form
+    p, q0 = _rand(n3, dtype, 1), _rand(n3, dtype, 2)
+    pp, qp = pack_poisoned(p), pack_poisoned(q0)
+    outs = [P.ops3dxs.laplace_dot(ctx, pp, n3, rng, q=qp, packed=True, dtype=dtype) for _ in range(2)]
+    q_st, pq = outs[0]
+    want = -O.residual3d(n3, rng, p, np.zeros_like(p), P.CORRECT, dtype=dtype)
+    got = xs_unpack(q_st, n3[0])
+    assert bits_equal(_interior(got), _interior(want))
+    assert bits_equal(got[_boundary_mask(n3)], q0[_boundary_mask(n3)]), "q's boundary was written"
+    assert pads_unchanged(qp, q_st, n3[0])
+    ref = _fsum_dot(p, want)
+    assert _close(pq, ref, 1e-13 if dtype == np.float64 else 1e-12), (pq, ref)
+    assert outs[0][1] == outs[1][1] and bits_equal(outs[0][0], outs[1][0]), "the sum is not the same bits on every call"
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n3", SHAPES)
+@pytest.mark.parametrize("with_x", [True, False])
+def test_cg_update(ctx, dtype, n3, with_x):
+    x, p, r, q = (_rand(n3, dtype, s) for s in (3, 4, 5, 6))
+    alpha = 0.3141592653589793
+    ups = [pack_poisoned(a) for a in (x, p, r, q)]
+    res = [P.ops3dxs.cg_update(ctx, ups[0] if with_x else None, ups[1], ups[2], ups[3], n3, alpha, dtype=dtype) for _ in range(2)]
+    xo, ro, rr = res[0]
+    a = dtype(alpha)
+    want_x, want_r = x + a * p, r - a * q
+    gr = xs_unpack(ro, n3[0])
+    assert bits_equal(_interior(gr), _interior(want_r))
+    assert bits_equal(gr[_boundary_mask(n3)], r[_boundary_mask(n3)])
+    assert pads_unchanged(ups[2], ro, n3[0])
+    if with_x:
+        gx = xs_unpack(xo, n3[0])
+        assert bits_equal(_interior(gx), _interior(want_x))
+        assert bits_equal(gx[_boundary_mask(n3)], x[_boundary_mask(n3)])
+        assert pads_unchanged(ups[0], xo, n3[0])
+    ref = _fsum_dot(want_r, want_r)
+    assert _close(rr, ref, 1e-13 if dtype == np.float64 else 1e-12), (rr, ref)
+    assert res[1][2] == rr
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n3", SHAPES)
+def test_dot2(ctx, dtype, n3):
+    a, b, c = (_rand(n3, dtype, s) for s in (7, 8, 9))
+    pa, pb, pc = (pack_poisoned(t) for t in (a, b, c))
+    ab, ac = P.ops3dxs.dot2(ctx, pa, pb, pc, n3, dtype=dtype)
+    ab2, none = P.ops3dxs.dot2(ctx, pa, pb, None, n3, dtype=dtype)
+    assert none is None and ab2 == ab
+    assert (ab, ac) == P.ops3dxs.dot2(ctx, pa, pb, pc, n3, dtype=dtype)
+    tol = 1e-13 if dtype == np.float64 else 1e-12
+    assert _close(ab, _fsum_dot(a, b), tol) and _close(ac, _fsum_dot(a, c), tol)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n3", SHAPES)
+@pytest.mark.parametrize("form", ["x+p", "p", "x", "copy"])
+def test_cg_direction(ctx, dtype, n3, form):
+    x, p, z = (_rand(n3, dtype, s) for s in (10, 11, 12))
+    alpha, beta = -0.7071067811865476, 1.4142135623730951
+    ux, up, uz = (pack_poisoned(t) for t in (x, p, z))
+    use_x = form in ("x+p", "x")
+    use_z = form != "x"
+    xo, po = P.ops3dxs.cg_direction(ctx, ux if use_x else None, up, uz if use_z else None, n3,
+                                    alpha=alpha if use_x else None, beta=beta if form in ("x+p", "p") else None, dtype=dtype)
+    want_x = x + dtype(alpha) * p
+    want_p = {"x+p": z + dtype(beta) * p, "p": z + dtype(beta) * p, "x": p, "copy": z}[form]
+    gp = xs_unpack(po, n3[0])
+    assert bits_equal(_interior(gp), _interior(want_p))
+    assert bits_equal(gp[_boundary_mask(n3)], p[_boundary_mask(n3)])
+    assert pads_unchanged(up, po, n3[0])
+    if use_x:
+        gx = xs_unpack(xo, n3[0])
+        assert bits_equal(_interior(gx), _interior(want_x))
+        assert bits_equal(gx[_boundary_mask(n3)], x[_boundary_mask(n3)])
+        assert pads_unchanged(ux, xo, n3[0])
+
+
+# ---------------------------------------------------------------------------------------------------------- solver
+def fcg_restated(n3, rng, v0, f, v1, v2, tol, maxit, nlevels=0, dtype=np.float64):
+    """flexible CG of mg_multigrid.h in numpy: A p = -residual(p, 0, CORRECT), M r = the oracle's V-cycle from zero"""
+    def A(p):
+        return -O.residual3d(n3, rng, p, np.zeros_like(p), P.CORRECT, dtype=dtype)
+
+    def M(r):
+        return O.cycle3d(n3, rng, nlevels=nlevels, mode=0, v0=1, v1=v1, v2=v2, v=np.zeros_like(r), f=r, residual_mode=O.CORRECT,
+                         dtype=dtype)
+
+    def dot(a, b):
+        return math.fsum((a.astype(np.float64) * b.astype(np.float64)).ravel())
+
+    x = v0.copy()
+    r = O.residual3d(n3, rng, x, f, P.CORRECT, dtype=dtype)
+    rr0 = dot(r, r)
+    hist, k, restart, conv = [], 0, True, False
+    while k < maxit:
+        if restart:
+            z = M(r)
+            p, rz, restart = z.copy(), dot(r, z), False
+        k += 1
+        q = A(p)
+        alpha = rz / dot(p, q)
+        x = x + dtype(alpha) * p
+        r = r - dtype(alpha) * q
+        rel = math.sqrt(dot(r, r) / rr0)
+        hist.append(rel)
+        if rel < tol:
+            r = O.residual3d(n3, rng, x, f, P.CORRECT, dtype=dtype)
+            if math.sqrt(dot(r, r) / rr0) < tol:
+                conv = True
+                break
+            restart = True
+            continue
+        z = M(r)
+        beta = -alpha * dot(z, q) / rz
+        rz = dot(r, z)
+        p = z + dtype(beta) * p
+    return x, k, np.array(hist), conv
+
+
+def _problem(n3, dtype=np.float64, seed=0):
+    f = np.zeros(O.shape(n3), dtype)
+    _interior(f)[...] = np.random.default_rng(seed).uniform(-1, 1, _interior(f).shape)
+    return f
+
+
+def _mg(ctx, n3, rng, dtype=np.float64, f=None, v=None, **kw):
+    mg = P.MultiGrid3D(ctx, n3, rng, dtype, residual_mode=P.CORRECT, **kw)
+    mg.upload_v(0, np.zeros(O.shape(n3), dtype) if v is None else v)
+    mg.upload_f(0, _problem(n3, dtype) if f is None else f)
+    return mg
+
+
+@pytest.mark.parametrize("v", [1, 2])
+@pytest.mark.parametrize("case", range(len(GRIDS)))
+def test_pcg_matches_restatement(ctx, case, v):
+    n3, rng, nlev = GRIDS[case]
+    f = _problem(n3)
+    want_x, want_k, want_h, want_c = fcg_restated(n3, rng, np.zeros_like(f), f, v, v, 1e-10, 200, nlevels=nlev)
+    mg = _mg(ctx, n3, rng, f=f, nlevels=nlev)
+    k, rel, conv, hist = mg.PCG(v, v, 1e-10, 200)
+    x = mg.download_v(0)
+    mg.close()
+    assert conv and want_c and rel < 1e-10
+    assert abs(k - want_k) <= 1, (k, want_k)
+    m = min(len(hist), len(want_h))
+    upto = want_h[:m] >= 1e-10
+    assert np.allclose(hist[:m][upto], want_h[:m][upto], rtol=1e-6, atol=0), (hist[:m], want_h[:m])
+    assert np.abs(x - want_x).max() <= 1e-9 * np.abs(want_x).max()
+
+
+@pytest.mark.parametrize("case", range(len(ANISO)))
+def test_pcg_beats_plain_cycles_on_anisotropic_grids(ctx, case):
+    n3, rng, nlev = ANISO[case]
+    its = {}
+    for krylov in (True, False):
+        mg = _mg(ctx, n3, rng, nlevels=nlev)
+        k, rel, conv, hist = mg.PCG(2, 2, 1e-10, 300, krylov=krylov)
+        mg.close()
+        assert conv and rel < 1e-10 and len(hist) == k
+        its[krylov] = k
+    assert 2 * its[True] <= its[False], its
+
+
+def test_pcg_dirichlet_quadratic(ctx):
+    n3, rng = (33, 25, 41), [-1, 1, 0, 2, 0.5, 3]
+    xs = [np.float64(rng[2 * d]) + np.arange(n3[d]) * P.grid_spacing(n3, rng, np.float64)[d] for d in range(3)]
+    Z, Y, X = np.meshgrid(xs[2], xs[1], xs[0], indexing="ij")
+    u = X * X + 2 * Y * Y + 3 * Z * Z
+    v0 = u.copy()
+    _interior(v0)[...] = 0
+    f = np.full(O.shape(n3), 12.0)
+    mg = _mg(ctx, n3, rng, f=f, v=v0, nlevels=3)  # the fourth level would be 5 x 4 x 6
+    k, rel, conv, _ = mg.PCG(2, 2, 1e-12, 100)
+    x = mg.download_v(0)
+    mg.close()
+    assert conv and rel < 1e-12
+    assert np.abs(x - u).max() <= 1e-8
+    assert bits_equal(x[_boundary_mask(n3)], v0[_boundary_mask(n3)])
+    # the one-call host form gives the same
+    got, k2, rel2, conv2 = P.solve3d_pcg(ctx, v0, f, rng, nlevels=3, v1=2, v2=2, tol=1e-12, maxit=100)
+    assert (k2, conv2) == (k, conv) and rel2 == rel and bits_equal(got, x)
+
+
+def test_pcg_fp32_is_honest(ctx):
+    n3, rng = (65, 65, 65), [0, 1, 0, 1, 0, 4]
+    mg = _mg(ctx, n3, rng, np.float32)
+    k, rel, conv, _ = mg.PCG(2, 2, 1e-5, 15)
+    mg.close()
+    assert conv and rel < 1e-5 and k <= 15
+    mg = _mg(ctx, n3, rng, np.float32)
+    k, rel, conv, hist = mg.PCG(2, 2, 1e-9, 40)
+    # the true residual of fp32 stalls far above 1e-9 while the recursive one keeps falling: never report that as success
+    r = mg.CalculateResidual(0).astype(np.float64)
+    f = _problem(n3, np.float32).astype(np.float64)
+    mg.close()
+    assert not conv and rel >= 1e-9
+    true_rel = np.linalg.norm(r) / np.linalg.norm(f)  # the guess is zero: r0 = f
+    assert abs(true_rel - rel) <= 1e-3 * rel
+
+
+def test_pcg_hierarchy_contract(ctx):
+    n3, rng = (65, 33, 129), [0, 1, 0, 2, 0, 1]
+    f, v0 = _problem(n3, seed=3), _rand(n3, np.float64, 4)
+    results = []
+    for use_graph in (False, True, True):
+        mg = _mg(ctx, n3, rng, f=f, v=v0)
+        mg.use_graph = use_graph
+        k, rel, conv, hist = mg.PCG(1, 1, 1e-9, 100)
+        assert conv
+        assert bits_equal(mg.download_f(0), f), "d_f[0] not restored"
+        v = mg.download_v(0)
+        assert bits_equal(v[_boundary_mask(n3)], v0[_boundary_mask(n3)])
+        results.append((k, rel, hist, v))
+        # the hierarchy goes on working as a hierarchy
+        mg.VCycle(0, 2, 2)
+        want = O.cycle3d(n3, rng, mode=0, v0=1, v1=2, v2=2, v=v, f=f, residual_mode=O.CORRECT, dtype=np.float64)
+        assert bits_equal(mg.download_v(0), want)
+        mg.close()
+    for k, rel, hist, v in results[1:]:
+        assert k == results[0][0] and rel == results[0][1] and bits_equal(hist, results[0][2]) and bits_equal(v, results[0][3])
+
+
+def test_pcg_second_call_and_fewer_levels(ctx):
+    n3, rng = (65, 33, 129), UNIT
+    f = _problem(n3, seed=5)
+    mg = _mg(ctx, n3, rng, f=f)
+    mg.numGrids = 3
+    k, rel, conv, _ = mg.PCG(2, 2, 1e-10, 200)
+    want_x, want_k, _, _ = fcg_restated(n3, rng, np.zeros_like(f), f, 2, 2, 1e-10, 200, nlevels=3)
+    assert conv and abs(k - want_k) <= 1
+    x = mg.download_v(0)
+    assert np.abs(x - want_x).max() <= 1e-9 * np.abs(want_x).max()
+    # a second call starts from the solution (the tolerance is relative to ITS initial residual, already ~1e-10 of f's)
+    k2, rel2, conv2, _ = mg.PCG(2, 2, 1e-3, 20)
+    assert conv2 and rel2 < 1e-3
+    assert bits_equal(mg.download_f(0), f)
+    mg.close()
+
+
+def test_pcg_rejects_invalid_arguments(ctx):
+    n3 = (17, 17, 17)
+    mg = _mg(ctx, n3, UNIT)
+    for args in [dict(tol=0), dict(tol=-1), dict(maxit=0), dict(v1=0, v2=0)]:
+        kw = dict(v1=1, v2=1, tol=1e-8, maxit=10)
+        kw.update(args)
+        with pytest.raises(P.MgxError) as e:
+            mg.PCG(**kw)
+        assert e.value.status == P.MGX_ERR_INVALID
+    mg._mg.contents.residual_mode = P.REF_COMPAT
+    with pytest.raises(P.MgxError) as e:
+        mg.PCG(1, 1, 1e-8, 10)
+    assert e.value.status == P.MGX_ERR_INVALID
+    mg.close()
+    mg = P.MultiGrid3D(ctx, n3, UNIT, np.float64, residual_mode=P.CORRECT, layout="natural")
+    with pytest.raises(P.MgxError) as e:
+        mg.PCG(1, 1, 1e-8, 10)
+    assert e.value.status == P.MGX_ERR_INVALID
+    mg.close()
+
+
+def test_pcg_breakdown_is_not_success(ctx):
+    # p = 0 from the start is impossible with a nonzero residual, but a NaN right-hand side makes <p, q> NaN
+    n3 = (17, 17, 17)
+    f = _problem(n3)
+    f[8, 8, 8] = np.nan
+    mg = _mg(ctx, n3, UNIT, f=f)
+    k, rel, conv, _ = mg.PCG(1, 1, 1e-8, 10)
+    assert not conv and k <= 1
+    assert bits_equal(mg.download_f(0), f)
+    mg.close()
+
+
+def test_pcg_scale_513(ctx):
+    n3 = (513, 513, 513)
+    mg = P.MultiGrid3D(ctx, n3, UNIT, np.float64, residual_mode=P.CORRECT)  # InitV / InitF: the reference's problem
+    k, rel, conv, _ = mg.PCG(2, 2, 1e-10, 20)
+    ds_pcg = mg.DiffStats(0)
+    mg.close()
+    assert conv and k <= 8, (k, rel)
+    mg = P.MultiGrid3D(ctx, n3, UNIT, np.float64, residual_mode=P.CORRECT)
+    kp, relp, convp, _ = mg.PCG(2, 2, 1e-10, 40, krylov=False)
+    ds_plain = mg.DiffStats(0)
+    mg.close()
+    assert convp and kp > k
+    # both are the discrete solution up to the algebraic error a relative residual of 1e-10 leaves (~1e-11 here, the solution
+    # being O(1)); the discretisation error DiffStats measures is ~1e-6, so the two agree to that error and not further
+    for a, b in zip(ds_pcg, ds_plain):
+        assert abs(a - b) <= 1e-4 * abs(b), (ds_pcg, ds_plain, k, kp)
