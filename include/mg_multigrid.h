@@ -54,6 +54,19 @@ int mg_dist_num_levels_single(int sizeZ_finest, int numGrids, int min_planes);
 int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
 
 #define MG_MAX_LEVELS 32 /* (int)log2(size-1) of any int size */
+/* use_graph: a captured cycle is replayed only while every host-side input of its launch sequence is what it was at
+ * capture time.  Those inputs are serialised (mg_graph_record, csrc/host/mg_common.h) into a fixed-size record of
+ * unsigned words, and a replay needs the caller's record to equal the capture's word for word. */
+#define MG_GRAPH_REC_WORDS 74
+typedef struct mgGraphRec {
+    unsigned int w[MG_GRAPH_REC_WORDS];
+} mgGraphRec;
+/* the rim flags a captured cycle reads and writes (3D: f_rim_zero, v_rim_zero, e_rim_valid; slab: v_rim_zero, gv, gf and
+ * the replicated tail's three): a replay leaves them as the capture did */
+#define MG_GRAPH_FLAG_ARRAYS 6
+typedef struct mgGraphFlags {
+    unsigned char a[MG_GRAPH_FLAG_ARRAYS][MG_MAX_LEVELS];
+} mgGraphFlags;
 #define MG_NORM_HISTORY 255 /* residual-norm history entries a distributed hierarchy keeps on the device */
 #define MG_DECLARE(R, real)                                                                              \
     /* ------------------------------------------------------------------ 3D ------ */                  \
@@ -81,7 +94,7 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
         real omega;   /* Jacobi weight, default 2/3 */                                                   \
         int use_graph; /* 1: VCycle(gridID, v1, v2) is captured into a HIP graph on first use and     */ \
                        /* replayed afterwards (re-captured when its arguments or the fields above     */ \
-                       /* change; context parameters are frozen at capture time).  Default 0.         */ \
+                       /* change, or the context's parameters, mgx_ctx_generation).  Default 0.       */ \
         int capturing;                                                                                   \
         void* graph_exec[MG_MAX_LEVELS];                                                                 \
         long long graph_key[MG_MAX_LEVELS];                                                              \
@@ -109,7 +122,13 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
         double* pcg_state;                                                                               \
         double* pcg_work;                                                                                \
         void* pcg_graph_exec;                                                                            \
-        long long pcg_graph_key;                                                                         \
+        long long pcg_graph_key; /* unused: kept so that the members after it keep their offsets */     \
+        /* internal: the record each graph was captured under and the rim flags its capture left behind  */ \
+        /* (graph_key[] above is unused likewise)                                                        */ \
+        mgGraphRec graph_rec[MG_MAX_LEVELS];                                                             \
+        mgGraphFlags graph_post[MG_MAX_LEVELS];                                                          \
+        mgGraphRec pcg_graph_rec;                                                                        \
+        mgGraphFlags pcg_graph_post;                                                                     \
     } mgMultiGrid3D_##R;                                                                                 \
     int mgMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6],     \
                                    mgMultiGrid3D_##R** out);                                             \
@@ -238,6 +257,10 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
                                    /* planes before mgx_comm_wait                                       */ \
         /* halo exchanges + collectives enqueued since creation (bench.py: exchanges per cycle)          */ \
         long long n_exchanges;                                                                           \
+        /* internal: the record graph_exec was captured under (graph_key above is unused) and the flags */ \
+        /* its capture left behind                                                                      */ \
+        mgGraphRec graph_rec;                                                                            \
+        mgGraphFlags graph_post;                                                                         \
     } mgDistMultiGrid3D_##R;                                                                             \
     int mgDistMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6], \
                                        int min_planes, mgDistMultiGrid3D_##R** out);                     \
@@ -292,7 +315,8 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
         int use_graph; /* as in mgMultiGrid3D: the 1025^2 cycle is launch-bound */                       \
         int capturing;                                                                                   \
         void* graph_exec[MG_MAX_LEVELS];                                                                 \
-        long long graph_key[MG_MAX_LEVELS];                                                              \
+        long long graph_key[MG_MAX_LEVELS]; /* unused: kept so that the members keep their offsets */   \
+        mgGraphRec graph_rec[MG_MAX_LEVELS]; /* internal: the record each graph was captured under */  \
     } mgMultiGrid2D_##R;                                                                                 \
     int mgMultiGrid2D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXY[2], const real range[4],     \
                                    const real* A, int A_size, int alfa, mgMultiGrid2D_##R** out);        \

@@ -93,6 +93,10 @@ int mgx_ctx_check(mgx_ctx* ctx);
  * tiles <= CUs x occupancy).  A process that shares the GPU with other contexts or processes sets "gpu.exclusive" to 0
  * (mgx_ctx_set_param): they are then never launched.  "sync.spin_limit" (default 2^21 polls, ~2 s) bounds every wait. */
 int mgx_ctx_clear_abort(mgx_ctx* ctx, int reenable);
+/* *generation counts the changes to what the context launches: it grows with every mgx_ctx_set_param call, when
+ * mgx_ctx_check finds a given-up wait (the context stops launching those kernels) and with every mgx_ctx_clear_abort.  A
+ * captured cycle of the host layer (use_graph) is captured again when it has changed since the capture. */
+int mgx_ctx_generation(const mgx_ctx* ctx, unsigned long long* generation);
 /* allocates now what some kernels would allocate on first use (the progress words and exchange buffer of the kernels whose
  * workgroups hand data to each other, ~17 MB): the hierarchies call it when they are created, so that their first cycle can
  * be captured into a HIP graph */
@@ -154,7 +158,8 @@ int mgx_memset_zero(mgx_ctx* ctx, void* dst, size_t bytes);                     
  * enqueue on the context's compute stream is captured instead of executed and instantiated as one executable graph;
  * _launch replays it with a single launch.  The host layer's VCycle does this itself when `use_graph` is set. */
 /* A captured graph freezes the launch sequence as it was at capture time, context parameters (mgx_ctx_set_param) included:
- * change a parameter -> capture again.  The host layer re-captures when the cycle's own arguments change, not on parameters. */
+ * change a parameter -> capture again.  The host layer re-captures when the cycle's own arguments or fields change and when
+ * the context's generation (mgx_ctx_generation) has changed. */
 int mgx_graph_begin(mgx_ctx* ctx);
 int mgx_graph_end(mgx_ctx* ctx, void** graph_exec);
 int mgx_graph_launch(mgx_ctx* ctx, void* graph_exec);

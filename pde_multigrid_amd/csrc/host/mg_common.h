@@ -33,6 +33,61 @@ static inline int mg_ca_trace(void) {
     return on;
 }
 
+/* ---- use_graph: the record a captured cycle is replayed under ---------------------------------------------------------
+ * Every host-side input of a cycle's launch sequence (the device arrays and their sizes are fixed for a hierarchy's life).
+ * Fields a hierarchy does not have stay 0; flag arrays hold only the levels its cycle reads, 0 elsewhere. */
+enum { MG_GRAPH_2D = 1, MG_GRAPH_3D = 2, MG_GRAPH_PCG3D = 3, MG_GRAPH_SLAB = 4 };
+typedef struct mgGraphState {
+    unsigned kind; /* MG_GRAPH_*: which body the sequence runs */
+    int gridID, v1, v2, numGrids, residual_mode, fuse, smoother, alfa, ca_min_planes;
+    unsigned long long omega_bits;      /* bit pattern of omega (fp32: the low 32 bits) */
+    unsigned long long matrixA_bits[4]; /* 2D: bit patterns of matrixA */
+    unsigned long long extra;           /* what else the caller's body depends on */
+    unsigned long long inline_bytes;    /* slab: the inline-exchange threshold */
+    unsigned long long generation;      /* mgx_ctx_generation of the context */
+    mgGraphFlags flags;                 /* see mgGraphFlags */
+} mgGraphState;
+
+/* the bit pattern of a float or double, widened without arithmetic */
+static inline unsigned long long mg_real_bits(const void* x, size_t size) {
+    unsigned long long b = 0;
+    unsigned char* d = (unsigned char*)&b;
+    const unsigned char* s = (const unsigned char*)x;
+    for (size_t i = 0; i < size && i < sizeof b; i++) d[i] = s[i]; /* little-endian: the value's bits, high bytes 0 */
+    return b;
+}
+
+/* serialise *s into *rec: one word per int field (converted to unsigned, which is exact modulo 2^32), two per 64-bit
+ * field, four flag bytes per word.  Pure: no signed arithmetic, no padding bytes read. */
+static inline void mg_graph_record(const mgGraphState* s, mgGraphRec* rec) {
+    unsigned* w = rec->w;
+    unsigned n = 0;
+    w[n++] = s->kind;
+    w[n++] = (unsigned)s->gridID;
+    w[n++] = (unsigned)s->v1;
+    w[n++] = (unsigned)s->v2;
+    w[n++] = (unsigned)s->numGrids;
+    w[n++] = (unsigned)s->residual_mode;
+    w[n++] = (unsigned)s->fuse;
+    w[n++] = (unsigned)s->smoother;
+    w[n++] = (unsigned)s->alfa;
+    w[n++] = (unsigned)s->ca_min_planes;
+    const unsigned long long wide[8] = {s->omega_bits,     s->matrixA_bits[0], s->matrixA_bits[1], s->matrixA_bits[2],
+                                        s->matrixA_bits[3], s->extra,          s->inline_bytes,     s->generation};
+    for (unsigned i = 0; i < 8; i++) {
+        w[n++] = (unsigned)wide[i]; /* the low 32 bits */
+        w[n++] = (unsigned)(wide[i] >> 32);
+    }
+    for (unsigned a = 0; a < MG_GRAPH_FLAG_ARRAYS; a++)
+        for (unsigned l = 0; l < MG_MAX_LEVELS; l += 4)
+            w[n++] = (unsigned)s->flags.a[a][l] | (unsigned)s->flags.a[a][l + 1] << 8 | (unsigned)s->flags.a[a][l + 2] << 16 |
+                     (unsigned)s->flags.a[a][l + 3] << 24;
+}
+_Static_assert(10 + 2 * 8 + MG_GRAPH_FLAG_ARRAYS * MG_MAX_LEVELS / 4 == MG_GRAPH_REC_WORDS, "mg_graph_record fills the record");
+
+/* 1 when two records are equal word for word */
+static inline int mg_graph_rec_equal(const mgGraphRec* a, const mgGraphRec* b) { return !memcmp(a, b, sizeof *a); }
+
 #define MG_TRY(expr)            \
     do {                        \
         int st_ = (expr);       \

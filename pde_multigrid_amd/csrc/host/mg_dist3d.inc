@@ -708,9 +708,9 @@ static int MG_CAT(ca_up_, R)(MGRID* mg, int l, int v1, int v2, const REAL* coars
 
 /* VCycle with levels < numDist distributed and the rest replicated.                      N3/MultiGrid3D.cpp:623-647 */
 static int MG_CAT(dist_vcycle_body_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero);
-/* use_graph: the cycle from level 0 is captured once (compute and comm stream, collectives included) and replayed; the key
+/* use_graph: the cycle from level 0 is captured once (compute and comm stream, collectives included) and replayed; the record
  * holds every host-side input of the launch sequence, as in mgMultiGrid3D (the flags that pick kernel forms change during the
- * first cycles: a changed key captures again, and the flags a capture leaves behind are those of the cycle it recorded) */
+ * first cycles: a changed record captures again, and a replay leaves the flags as its capture did) */
 static int MG_CAT(dist_vcycle_graph_, R)(MGRID* mg, int v1, int v2) {
     MG_REQUIRE(mgx_comm_capturable(mg->ctx), MGX_ERR_INVALID, "VCycle: use_graph needs collectives that can be captured (RCCL or one rank)");
     if (!mg->graph_warm) { /* workspaces and the like are allocated on first use, which a capture does not allow */
@@ -718,15 +718,26 @@ static int MG_CAT(dist_vcycle_graph_, R)(MGRID* mg, int v1, int v2) {
         MG_TRY(MG_CAT(dist_vcycle_body_, R)(mg, 0, v1, v2, 0));
         return MG_CAT(ca_settle_, R)(mg);
     }
-    long long key = 1 + (((long long)v1 & 0xfff) | (((long long)v2 & 0xfff) << 12) | ((long long)mg->numGrids << 24) |
-                         ((long long)mg->residual_mode << 30) | ((long long)(mg->inline_bytes > 0) << 32));
-    for (int l = 0; l < mg->numDist; l++) key = key * 3 + mg->v_rim_zero[l];
-    for (int l = 0; l < mg->numDist; l++) key = key * 7 + (mg->gv[l] > 6 ? 6 : mg->gv[l]); /* an exchange is part of the sequence or not */
-    key = key * 2 + (mg->ca_min_planes > 0);
-    if (mg->tail)
-        for (int i = 0; i < mg->tail->maxGrids; i++)
-            key = key * 11 + mg->tail->f_rim_zero[i] + 2 * mg->tail->v_rim_zero[i] + 4 * mg->tail->e_rim_valid[i];
-    if (!mg->graph_exec || mg->graph_key != key) {
+    unsigned char* const flags[6] = {mg->v_rim_zero, (unsigned char*)mg->gv, (unsigned char*)mg->gf,
+                                     mg->tail ? mg->tail->f_rim_zero : NULL, mg->tail ? mg->tail->v_rim_zero : NULL,
+                                     mg->tail ? mg->tail->e_rim_valid : NULL};
+    mgGraphState s;
+    memset(&s, 0, sizeof s);
+    s.kind = MG_GRAPH_SLAB;
+    s.v1 = v1; s.v2 = v2; s.numGrids = mg->numGrids; s.residual_mode = mg->residual_mode;
+    s.ca_min_planes = mg->ca_min_planes;
+    s.inline_bytes = (unsigned long long)mg->inline_bytes;
+    s.extra = (unsigned)mg->pack_halos;
+    if (mg->tail) {
+        s.fuse = mg->tail->fuse; s.smoother = mg->tail->smoother;
+        s.omega_bits = mg_real_bits(&mg->tail->omega, sizeof(REAL));
+    }
+    MG_TRY(mgx_ctx_generation(mg->ctx, &s.generation));
+    for (int k = 0; k < 6; k++)
+        if (flags[k]) memcpy(s.flags.a[k], flags[k], MG_MAX_LEVELS);
+    mgGraphRec rec;
+    mg_graph_record(&s, &rec);
+    if (!mg->graph_exec || !mg_graph_rec_equal(&mg->graph_rec, &rec)) {
         if (mg->graph_exec) MG_TRY(mgx_graph_destroy(mg->ctx, mg->graph_exec));
         mg->graph_exec = NULL;
         MG_TRY(mgx_graph_begin(mg->ctx));
@@ -740,7 +751,16 @@ static int MG_CAT(dist_vcycle_graph_, R)(MGRID* mg, int v1, int v2) {
         }
         MG_TRY(st2);
         mg->graph_exec = exec;
-        mg->graph_key = key;
+        mg->graph_rec = rec;
+        for (int k = 0; k < 6; k++)
+            if (flags[k]) memcpy(mg->graph_post.a[k], flags[k], MG_MAX_LEVELS);
+    } else { /* the flags as the captured cycle left them */
+        for (int k = 0; k < 6; k++)
+            if (flags[k]) memcpy(flags[k], mg->graph_post.a[k], MG_MAX_LEVELS);
+        if (mg->tail && mg->numGrids > mg->numDist) {
+            mg->tail->numGrids = mg->numGrids - mg->numDist;
+            mg->tail->residual_mode = mg->residual_mode;
+        }
     }
     return mgx_graph_launch(mg->ctx, mg->graph_exec);
 }

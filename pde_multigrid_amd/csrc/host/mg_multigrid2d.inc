@@ -159,19 +159,19 @@ int FN(ApplyCorrection)(MGRID* mg, REAL* fine, const int fsizeXY[2], const REAL*
     return MGX(apply_correction)(mg->ctx, fine, fsizeXY, error, esizeXY);
 }
 
-/* use_graph: see mg_multigrid3d.inc */
+/* use_graph: see mg_multigrid3d.inc.  The body reads no rim flags in 2D. */
 static int MG_CAT(vcycle_graph2_, R)(MGRID* mg, int gridID, int v1, int v2, int (*body)(MGRID*, int, int, int)) {
-    long long obits = 0;
-    memcpy(&obits, &mg->omega, sizeof(REAL));
-    long long key = 1 + (((long long)v1 & 0xfff) | (((long long)v2 & 0xfff) << 12) | ((long long)mg->numGrids << 24) |
-                         ((long long)mg->fuse << 32) | ((long long)mg->smoother << 33) | ((long long)(mg->alfa & 0xffff) << 34)) +
-                    obits * 1000003LL;
-    for (int k = 0; k < 4; k++) {
-        long long abits = 0;
-        memcpy(&abits, &mg->matrixA[k], sizeof(REAL));
-        key = key * 31 + abits;
-    }
-    if (!mg->graph_exec[gridID] || mg->graph_key[gridID] != key) {
+    mgGraphState s;
+    memset(&s, 0, sizeof s);
+    s.kind = MG_GRAPH_2D;
+    s.gridID = gridID; s.v1 = v1; s.v2 = v2; s.numGrids = mg->numGrids;
+    s.fuse = mg->fuse; s.smoother = mg->smoother; s.alfa = mg->alfa;
+    s.omega_bits = mg_real_bits(&mg->omega, sizeof(REAL));
+    for (int k = 0; k < 4; k++) s.matrixA_bits[k] = mg_real_bits(&mg->matrixA[k], sizeof(REAL));
+    MG_TRY(mgx_ctx_generation(mg->ctx, &s.generation));
+    mgGraphRec rec;
+    mg_graph_record(&s, &rec);
+    if (!mg->graph_exec[gridID] || !mg_graph_rec_equal(&mg->graph_rec[gridID], &rec)) {
         if (mg->graph_exec[gridID]) MG_TRY(mgx_graph_destroy(mg->ctx, mg->graph_exec[gridID]));
         mg->graph_exec[gridID] = NULL;
         MG_TRY(mgx_graph_begin(mg->ctx));
@@ -186,7 +186,7 @@ static int MG_CAT(vcycle_graph2_, R)(MGRID* mg, int gridID, int v1, int v2, int 
         }
         MG_TRY(st2);
         mg->graph_exec[gridID] = exec;
-        mg->graph_key[gridID] = key;
+        mg->graph_rec[gridID] = rec;
     }
     return mgx_graph_launch(mg->ctx, mg->graph_exec[gridID]);
 }

@@ -223,19 +223,26 @@ int FN(ApplyCorrection)(MGRID* mg, REAL* fine, const int fsizeXYZ[3], const REAL
     return MGXL(mg, apply_correction)(mg->ctx, fine, fsizeXYZ, error, esizeXYZ);
 }
 
-/* use_graph: the cycle that starts at gridID is captured once into a HIP graph and replayed; the key holds every
- * host-side input of the launch sequence (the device arrays and their sizes are fixed for the hierarchy's life) */
+/* use_graph: the cycle that starts at gridID is captured once into a HIP graph and replayed while its record (mg_common.h)
+ * is unchanged: every host-side input of the launch sequence, the rim flags of levels gridID .. numGrids-1 that pick kernel
+ * forms and boundary copies, and the context's generation (its parameters) included.  The body also sets those flags; a
+ * replay sets them as its capture did. */
 static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int (*body)(MGRID*, int, int, int), void** slot_exec,
-                                     long long* slot_key, long long extra) {
-    long long obits = 0;
-    memcpy(&obits, &mg->omega, sizeof(REAL));
-    long long key = 1 + (((long long)v1 & 0xfff) | (((long long)v2 & 0xfff) << 12) | ((long long)mg->numGrids << 24) |
-                               ((long long)mg->residual_mode << 30) | ((long long)mg->fuse << 32) |
-                               ((long long)mg->smoother << 33)) + obits * 1000003LL;
-    for (int i = gridID + 1; i < mg->numGrids; i++) key = key * 5 + mg->f_rim_zero[i] + 2 * mg->v_rim_zero[i]; /* pick kernel forms */
-    for (int i = gridID; i < mg->numGrids; i++) key = key * 3 + mg->e_rim_valid[i]; /* a boundary copy is part of the sequence or not */
-    key = key * 7 + extra; /* what else the caller's body depends on */
-    if (!*slot_exec || *slot_key != key) {
+                                     mgGraphRec* slot_rec, mgGraphFlags* slot_post, unsigned kind, unsigned long long extra) {
+    unsigned char* const flags[3] = {mg->f_rim_zero, mg->v_rim_zero, mg->e_rim_valid};
+    mgGraphState s;
+    memset(&s, 0, sizeof s);
+    s.kind = kind;
+    s.gridID = gridID; s.v1 = v1; s.v2 = v2; s.numGrids = mg->numGrids;
+    s.residual_mode = mg->residual_mode; s.fuse = mg->fuse; s.smoother = mg->smoother;
+    s.omega_bits = mg_real_bits(&mg->omega, sizeof(REAL));
+    s.extra = extra; /* what else the caller's body depends on */
+    MG_TRY(mgx_ctx_generation(mg->ctx, &s.generation));
+    for (int k = 0; k < 3; k++)
+        for (int i = gridID; i < mg->numGrids; i++) s.flags.a[k][i] = flags[k][i];
+    mgGraphRec rec;
+    mg_graph_record(&s, &rec);
+    if (!*slot_exec || !mg_graph_rec_equal(slot_rec, &rec)) {
         if (*slot_exec) MG_TRY(mgx_graph_destroy(mg->ctx, *slot_exec));
         *slot_exec = NULL;
         MG_TRY(mgx_graph_begin(mg->ctx));
@@ -250,7 +257,11 @@ static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int 
         }
         MG_TRY(st2);
         *slot_exec = exec;
-        *slot_key = key;
+        *slot_rec = rec;
+        for (int k = 0; k < 3; k++) memcpy(slot_post->a[k], flags[k], MG_MAX_LEVELS);
+    } else {
+        for (int k = 0; k < 3; k++)
+            for (int i = gridID; i < mg->numGrids; i++) flags[k][i] = slot_post->a[k][i];
     }
     return mgx_graph_launch(mg->ctx, *slot_exec);
 }
@@ -348,7 +359,8 @@ int FN(VCycle)(MGRID* mg, int gridID, int v1, int v2) {
     MG_REQUIRE(gridID >= 0 && gridID < mg->numGrids, MGX_ERR_INVALID, "VCycle: bad gridID %d", gridID);
     MG_REQUIRE(v1 >= 0 && v2 >= 0, MGX_ERR_INVALID, "VCycle: negative sweep count");
     if (mg->use_graph && !mg->capturing)
-        return MG_CAT(vcycle_graph3_, R)(mg, gridID, v1, v2, FN(VCycle), &mg->graph_exec[gridID], &mg->graph_key[gridID], 0);
+        return MG_CAT(vcycle_graph3_, R)(mg, gridID, v1, v2, FN(VCycle), &mg->graph_exec[gridID], &mg->graph_rec[gridID],
+                                         &mg->graph_post[gridID], MG_GRAPH_3D, 0);
     return MG_CAT(vcycle_body3_, R)(mg, gridID, v1, v2, 0);
 }
 
@@ -480,8 +492,8 @@ static int MG_CAT(pcg_vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2) {
 /* z = M r: d_v[0] := VCycle from zero with d_f[0] = r */
 static int MG_CAT(pcg_precond3_, R)(MGRID* mg, int v1, int v2) {
     if (mg->use_graph)  /* the sequence also depends on whether d_v[0]'s boundary still has to be zeroed */
-        return MG_CAT(vcycle_graph3_, R)(mg, 0, v1, v2, MG_CAT(pcg_vcycle_body3_, R), &mg->pcg_graph_exec, &mg->pcg_graph_key,
-                                         1 + mg->v_rim_zero[0]);
+        return MG_CAT(vcycle_graph3_, R)(mg, 0, v1, v2, MG_CAT(pcg_vcycle_body3_, R), &mg->pcg_graph_exec, &mg->pcg_graph_rec,
+                                         &mg->pcg_graph_post, MG_GRAPH_PCG3D, 1 + mg->v_rim_zero[0]);
     return MG_CAT(vcycle_body3_, R)(mg, 0, v1, v2, 1);
 }
 

@@ -59,6 +59,7 @@ struct mgx_ctx {
     unsigned handoff_fault = 0;           // "test.handoff_fault": test hook, see SweepSync::fault
     int handoff_broken = 0;   // set when mgx_ctx_check has seen the abort word: the kernels whose workgroups wait for each other are not
                               // used any more on this context (colour passes instead) until mgx_ctx_clear_abort(ctx, 1)
+    unsigned long long generation = 0;  // mgx_ctx_generation: grows whenever what the context launches may have changed
     int gpu_exclusive = 1;    // "gpu.exclusive": 1 = this context has the GPU to itself (the assumption behind those kernels); 0 = the GPU
                               // is shared with other contexts / processes: they are never launched
     mutable int resident_occ = -1;  // workgroups of the resident Relax kernels per CU (occupancy API), -1 = not asked yet

@@ -3789,6 +3789,7 @@ const char* mgx_ctx_last_corr_kernel(const mgx_ctx* ctx) { return ctx ? ctx->las
 int mgx_ctx_set_param(mgx_ctx* ctx, const char* name, int value) {
     MGX_REQUIRE(ctx && name, MGX_ERR_INVALID, "set_param: NULL argument");
     MGX_USE(ctx);
+    ctx->generation++;  // also on a rejected value: a spurious re-capture is harmless
     if (!strcmp(name, "relax3d.ty")) {
         MGX_REQUIRE(value == 1 || value == 2 || value == 4 || value == 8, MGX_ERR_INVALID, "relax3d.ty (waves per block) must be 1, 2, 4 or 8");
         ctx->relax_ty = value;

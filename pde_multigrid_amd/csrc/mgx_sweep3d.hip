@@ -943,6 +943,7 @@ int mgx_ctx_check(mgx_ctx* ctx) {
     MGX_REQUIRE(ctx, MGX_ERR_INVALID, "ctx is NULL");
     if (ctx->sweep_abort && *(volatile unsigned*)ctx->sweep_abort) {
         ctx->handoff_broken = 1;  // from now on: colour passes
+        ctx->generation++;        // a captured cycle that launches those kernels is stale
         return mgx::fail(MGX_ERR_HIP, "a kernel whose workgroups wait for each other (one-launch sweep, resident Relax) gave up waiting for a "
                                       "neighbouring workgroup (is the GPU shared with another context or process? then set \"gpu.exclusive\" "
                                       "to 0); the results of that launch are invalid.  This context now runs colour passes instead; "
@@ -968,6 +969,13 @@ int mgx_ctx_clear_abort(mgx_ctx* ctx, int reenable) {
     }
     if (ctx->sweep_abort) *(volatile unsigned*)ctx->sweep_abort = 0;
     if (reenable) ctx->handoff_broken = 0;
+    ctx->generation++;
+    return MGX_OK;
+}
+
+int mgx_ctx_generation(const mgx_ctx* ctx, unsigned long long* generation) {
+    MGX_REQUIRE(ctx && generation, MGX_ERR_INVALID, "mgx_ctx_generation: NULL argument");
+    *generation = ctx->generation;
     return MGX_OK;
 }
 }

@@ -95,6 +95,12 @@ class Context:
     def set_param(self, name, value):
         check(lib.mgx_ctx_set_param(self._h, name.encode(), C.c_int(int(value))))
 
+    def generation(self):
+        """mgx_ctx_generation: grows whenever what the context launches may have changed (parameters, given-up waits)"""
+        g = C.c_ulonglong()
+        check(lib.mgx_ctx_generation(self._h, C.byref(g)))
+        return int(g.value)
+
     def clear_abort(self, reenable=False):
         """after sync() reported a given-up wait between workgroups: clear the condition (mgx_ctx_clear_abort)"""
         check(lib.mgx_ctx_clear_abort(self._h, C.c_int(1 if reenable else 0)))
@@ -550,6 +556,20 @@ ops2d = _Ops2D()
 
 
 # --------------------------------------------------------------------------- hierarchy views
+MG_GRAPH_REC_WORDS = 74  # mg_multigrid.h
+MG_GRAPH_FLAG_ARRAYS = 6
+
+
+class GraphRec(C.Structure):
+    """mgGraphRec: the record a captured cycle is replayed under (mg_common.h mg_graph_record)"""
+    _fields_ = [("w", C.c_uint * MG_GRAPH_REC_WORDS)]
+
+
+class GraphFlags(C.Structure):
+    """mgGraphFlags: the rim flags a captured cycle left behind"""
+    _fields_ = [("a", (C.c_ubyte * 32) * MG_GRAPH_FLAG_ARRAYS)]
+
+
 def _grid3_struct(ct):
     class Grid3D(C.Structure):
         _fields_ = [("h_v", C.c_void_p), ("h_f", C.c_void_p), ("d_v", C.c_void_p), ("d_f", C.c_void_p),
@@ -562,7 +582,11 @@ def _grid3_struct(ct):
                     ("ctx", C.c_void_p), ("residual_mode", C.c_int), ("fuse", C.c_int), ("layout", C.c_int),
                     ("smoother", C.c_int), ("omega", ct), ("use_graph", C.c_int), ("capturing", C.c_int),
                     ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 32), ("f_rim_zero", C.c_ubyte * 32),
-                    ("v_rim_zero", C.c_ubyte * 32), ("e_rim_valid", C.c_ubyte * 32)]
+                    ("v_rim_zero", C.c_ubyte * 32), ("e_rim_valid", C.c_ubyte * 32), ("pcg_x", C.c_void_p),
+                    ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
+                    ("pcg_work", C.c_void_p), ("pcg_graph_exec", C.c_void_p), ("pcg_graph_key", C.c_longlong),
+                    ("graph_rec", GraphRec * 32), ("graph_post", GraphFlags * 32), ("pcg_graph_rec", GraphRec),
+                    ("pcg_graph_post", GraphFlags)]
 
     return Grid3D, MultiGrid3D
 
@@ -577,7 +601,7 @@ def _grid2_struct(ct):
         _fields_ = [("grids2D", C.POINTER(C.POINTER(Grid2D))), ("numGrids", C.c_int), ("maxGrids", C.c_int),
                     ("matrixA", ct * 4), ("sizeA", C.c_int), ("alfa", C.c_int), ("ctx", C.c_void_p), ("fuse", C.c_int),
                     ("smoother", C.c_int), ("omega", ct), ("use_graph", C.c_int), ("capturing", C.c_int),
-                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 32)]
+                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 32), ("graph_rec", GraphRec * 32)]
 
     return Grid2D, MultiGrid2D
 
@@ -907,7 +931,7 @@ def _dist_struct(ct):
                     ("use_graph", C.c_int), ("graph_exec", C.c_void_p), ("graph_key", C.c_longlong), ("graph_warm", C.c_int),
                     ("pack_halos", C.c_int), ("d_stage", C.c_void_p), ("stage_half", C.c_size_t),
                     ("ca_min_planes", C.c_int), ("gv", C.c_byte * 32), ("gf", C.c_byte * 32), ("comm_pending", C.c_int),
-                    ("n_exchanges", C.c_longlong)]
+                    ("n_exchanges", C.c_longlong), ("graph_rec", GraphRec), ("graph_post", GraphFlags)]
 
     return Slab3D, DistMultiGrid3D
 
