@@ -120,6 +120,8 @@ int mgx_ctx_device(const mgx_ctx* ctx, int* device);
  * per pass; "relax3d.resident_tile" 0 (by level) / 8: tiles of 8 x 8 lines always;
  * "rr3d.black" 0 / 1 / 2: the last black pass of the pre-smoothing inside the residual+restrict launch -- off / on the
  * HBM-bound levels / wherever the geometry allows (tests), "rr3d.black_waves" 0 (by precision), 8 (two workgroups per CU), 12, 16 waves per workgroup.
+ * "relax3d.block3" 1 (default) / 0: on the levels the fused black pass takes by its own rule (fp64, from 385-point rows on), the
+ * last three colour passes before it (R, B, R) run as one launch that stores red only (mgx3dxs_relax_block3_f64) -- or as three.
  * "gpu.exclusive" 1 (default) / 0: 0 = the GPU is shared with other contexts or processes, so the kernels whose workgroups
  * wait for each other (resident Relax, one-launch sweep of 513-point rows) are never launched; "sync.spin_limit" polls (~1 us
  * each, default 2^21) before such a wait gives up (see mgx_ctx_check); "test.handoff_fault" != 0 is a TEST HOOK that makes
@@ -135,6 +137,16 @@ const char* mgx_ctx_last_rr_kernel(const mgx_ctx* ctx);
 /* name of the kernel that ran the correcting red pass (the correction read on the fly) in the most recent
  * mgx3dxs_interpolate_correct_relax_* call; "" when that call corrected in a pass of its own */
 const char* mgx_ctx_last_corr_kernel(const mgx_ctx* ctx);
+/* name of the three-pass kernel the most recent mgx3dxs_smooth_residual_restrict_* or mgx3dxs_relax_block3_f64 call launched;
+ * "" when that call ran its colour passes one launch each */
+const char* mgx_ctx_last_block3_kernel(const mgx_ctx* ctx);
+/* colour passes first_colour, 1 - first_colour, first_colour of MultiGrid3D::Relax over the interior of an n[0] x n[1] x n[2]
+ * x-split fp64 level, in one launch.  Reads colour 1 - first_colour and the faces of the grid from vin, f from f; writes the
+ * interior points of first_colour into vout (store_both != 0: of both colours, the other one as the middle pass left it).
+ * Nothing else of vout is written and no first_colour interior entry of vin is read, so vin == vout is allowed when
+ * store_both == 0; store_both needs separate arrays.  Bit-identical to the three passes. */
+int mgx3dxs_relax_block3_f64(mgx_ctx* ctx, const double* vin, double* vout, const double* f, const int n[3], const double h[3],
+                             int first_colour, int store_both);
 /* TEST HOOK, process-wide: on != 0 -> every kernel launch of the library is preceded by a launch that fills the LDS of every
  * CU with signalling-NaN patterns (a kernel that reads an LDS word before writing it then fails its parity test for certain
  * instead of depending on the previous launch's leftovers).  Costs ~15 us per launch; results are unchanged by contract. */

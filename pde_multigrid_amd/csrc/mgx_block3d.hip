@@ -1,0 +1,280 @@
+// mgx_block3d.hip -- three colour passes X, Y, X of MultiGrid3D::Relax in ONE launch (x-split layout, fp64, HBM-bound levels).
+//
+// A colour pass overwrites every point of its colour from the other colour's values and f only; the old values of its own
+// colour are never read.  So the three passes X, Y, X need colour Y's old values and f, nothing else: the launch reads Y from
+// `vin` and f, and writes the final X (and, with STORE_BOTH, the Y of the middle pass) into `vout`.  Where the launch stores
+// only X it may run in place (vin == vout): no workgroup ever reads an X value from memory, except the entries on a face of
+// the grid, which no pass writes.  That is the argument that makes relax_rr3d_xs_kernel race-free.
+//
+// On the way down (smooth_residual_restrict3d_xs) the last three passes before relax_rr3d_xs_kernel are R, B, R.  The B values
+// of the middle pass are overwritten by the rr kernel's own black pass, which reads only red: the launch stores red only and
+// streams black 0.5 + f 1.0 + red 0.5 = 2.0 words per point instead of the 4.5 of three plain passes.
+//
+// A workgroup marches its (x, y) tile through a run of z-planes with the three stages lagged one plane each:
+//
+//   iteration t:   stage 1   X at plane t       from Y (loaded) of planes t - 1, t, t + 1 and f
+//                  stage 2   Y at plane t - 1   from the stage-1 X of planes t - 2, t - 1, t and f
+//                  stage 3   X at plane t - 2   from the stage-2 Y of planes t - 3, t - 2, t - 1 and f  -> stored
+//
+// Tile edges are recomputed, not exchanged: Y is loaded three deep around the tile, stage 1 is right two deep, stage 2 one
+// deep, stage 3 on the tile.  A wave owns two rows and 64 x-pairs; lanes 0, 1, 62, 63 and the first three and last three rows
+// of a workgroup are halo (60 pairs x (2 TW - 6) rows per tile).  A run of planes starts three planes early for the same
+// reason.  Every value is computed from exactly the inputs of the separate passes with relax3d_point: bit-identical results.
+//
+// Rows of neighbouring waves go through LDS: every iteration publishes the first and last row of the Y of plane t + 1 (loaded
+// one iteration earlier), of the stage-1 X and of the stage-2 Y, and reads those of the previous iteration -- ONE barrier per
+// iteration, double-buffered.  Loads requested at the top of an iteration are waited for behind its barrier; the stores of the
+// previous iteration's results go out at the top too.
+#include <type_traits>
+
+#include "mgx_internal.hpp"
+#include "mgx_kernels3d.hpp"
+
+namespace mgx {
+
+template <class real, int COL, bool STORE_BOTH, int TW>
+__global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs, one workgroup per CU
+    relax3d_xs_block3_kernel(const real* vin, real* vout, const real* __restrict__ f, int sx, int sy, int sz, real hx2, real hy2,
+                             real hz2, int zrun, int gx, int gy, int xcd_mode) {
+    constexpr int ROWS = 2 * TW, OUTR = ROWS - 6;  // rows of a tile, of which the middle OUTR are stored
+    static_assert(OUTR % 2 == 0, "the colour parity of a wave's rows must not depend on the tile");
+    __shared__ real sY[2][TW][2][64];  // [iteration & 1][wave][first / last row][lane]: loaded Y of plane t + 1
+    __shared__ real sX[2][TW][2][64];  // stage-1 X of plane t
+    __shared__ real sZ[2][TW][2][64];  // stage-2 Y of plane t - 1
+    const Geo<XSplit, real> g(sx, sy);
+    const int lane = threadIdx.x;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.y);
+    int bx, by, bz;
+    tile_of_block(xcd_mode, gx, gy, bx, by, bz);
+    const int z0 = 1 + bz * zrun, z1 = min(z0 + zrun, sz - 1);  // planes [z0, z1) are this run's
+    if (z0 >= z1) return;  // uniform over the workgroup
+    const int PL = (int)g.PL;
+
+    const int Hn = (sx + 1) >> 1;  // x-pairs of a row (the last one has its even entry only)
+    const int pn = bx * 60 + lane - 2, p = min(max(pn, 0), Hn - 1);
+    const unsigned off0 = (unsigned)p * (unsigned)sizeof(real), off1 = (unsigned)(g.H + (p <= Hn - 2 ? p : 0)) * (unsigned)sizeof(real);
+    const bool xin0 = pn >= 1 && 2 * pn <= sx - 2, xin1 = pn >= 0 && 2 * pn + 1 <= sx - 2;  // 1 <= x <= sx - 2
+    auto off = [&](int h) { return h ? off1 : off0; };  // byte offset of the lane's entry in half h (selects: no indexed arrays)
+    auto xin = [&](int h) { return h ? xin1 : xin0; };
+    const bool xface0 = pn <= 0 || pn >= Hn - 1;  // the even entry lies on (or beyond) an x-face
+    const bool wxface = bx * 60 - 2 <= 0 || bx * 60 + 61 >= Hn - 1;  // some lane of the wave holds one (wave-uniform)
+    const bool outlane = lane >= 2 && lane <= 61;
+    int roff[2];
+    bool yin[2], outrow[2];
+#pragma unroll
+    for (int o = 0; o < 2; o++) {
+        const int y = by * OUTR - 3 + 2 * w + o;
+        roff[o] = min(max(y, 0), sy - 1) * g.P;
+        yin[o] = y >= 1 && y <= sy - 2;
+        outrow[o] = 2 * w + o >= 3 && 2 * w + o < ROWS - 3;
+    }
+    const int wU = w > 0 ? w - 1 : 0, wD = w < TW - 1 ? w + 1 : TW - 1;
+    auto zc = [&](int z) { return min(max(z, 0), sz - 1); };
+    auto plane = [&](const real* a, int z) { return plane_rsrc<real>(a + (ptrdiff_t)zc(z) * (ptrdiff_t)g.PL, PL, 1); };
+
+    // per row: loaded Y of planes t-1, t, t+1, t+2 (in flight); f (or v on a face of the grid) of X at planes t, t-1, t-2, t+1 (in
+    // flight, v of a y- / z-face); v of the even X entry at plane t+1 (in flight, x-face lanes: replaces f once it has arrived); f of Y at planes t-1, t (in flight); stage-1 X at t, t-1,
+    // t-2; stage-2 Y at t-1, t-2, t-3; stage-3 X of plane t-2, stored in the next iteration
+    real a_m[2], a_c[2], a_p[2], a_n[2], fx_c[2], fx_1[2], fx_2[2], fx_n[2], xv_n[2], fy_c[2], fy_n[2];
+    real b_c[2], b_m[2], b_mm[2], d_c[2], d_m[2], d_mm[2], x3[2];
+#pragma unroll
+    for (int o = 0; o < 2; o++)
+        a_m[o] = a_c[o] = a_p[o] = a_n[o] = fx_c[o] = fx_1[o] = fx_2[o] = fx_n[o] = xv_n[o] = fy_c[o] = fy_n[o] = b_c[o] =
+            b_m[o] = b_mm[o] = d_c[o] = d_m[o] = d_mm[o] = x3[o] = 0;
+
+    const int t0 = z0 - 2, tlast = z1 + 1;
+    // ---- set-up: Y of planes t0 - 1 .. t0 + 1, f / v of X at t0; the rows of Y at t0 published as if by iteration t0 - 1
+    {
+        const auto qm = plane(vin, t0 - 1), q0 = plane(vin, t0), qp = plane(vin, t0 + 1);
+        const bool zf = t0 <= 0 || t0 >= sz - 1;
+        const auto qf = plane(f, t0);
+#pragma unroll
+        for (int o = 0; o < 2; o++) {
+            const int hx = (COL + 1 + o + t0) & 1;  // X half of row o at plane t0
+            a_m[o] = buf_load<real>(qm, off(hx), roff[o]);
+            a_c[o] = buf_load<real>(q0, off(hx ^ 1), roff[o]);
+            a_p[o] = buf_load<real>(qp, off(hx), roff[o]);
+            fx_c[o] = buf_load<real>(zf || !yin[o] ? q0 : qf, off(hx), roff[o]);
+            if (wxface) xv_n[o] = buf_load<real>(q0, off(0), roff[o]);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+#pragma unroll
+        for (int o = 0; o < 2; o++)
+            if (wxface && ((COL + 1 + o + t0) & 1) == 0 && xface0) fx_c[o] = xv_n[o];
+        const int b = (t0 - 1) & 1;
+        sY[b][w][0][lane] = a_c[0];
+        sY[b][w][1][lane] = a_c[1];
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+
+    // one relaxed point at half h of row o (stage with in-plane values `c` of the other colour, rows above / below through LDS)
+    auto relax = [&](auto hc, int o, const real (&c)[2], real nb, real sb, real D, real U, real fv) __attribute__((always_inline)) {
+        constexpr int h = decltype(hc)::value;
+        real O, E;
+        if (h == 0) {
+            O = wave_from_prev_lane<real>(c[o]);
+            E = c[o];
+        } else {
+            O = c[o];
+            E = wave_from_next_lane<real>(c[o]);
+        }
+        const real N = o == 0 ? nb : c[0], S = o == 1 ? sb : c[1];
+        return relax3d_point<real>(O, E, N, S, D, U, fv, hx2, hy2, hz2);
+    };
+
+    auto iteration = [&](auto parity, int t) __attribute__((always_inline)) {
+        constexpr int PAR = decltype(parity)::value;  // t & 1
+        constexpr int PB = PAR ^ 1;                  // LDS buffer written by the previous iteration
+        // ---- stores of the previous iteration's results: X of plane t - 3, Y of plane t - 2 (both in half hx ^ 1)
+        const auto ro3 = plane(vout, t - 3), ro2 = plane(vout, t - 2);
+        // ---- requests: Y of plane t + 2, f (v on a face) of X at t + 1, f of Y at t
+        const auto rY = plane(vin, t + 2), rXv = plane(vin, t + 1), rFx = plane(f, t + 1), rFy = plane(f, t);
+        const bool zf = t + 1 <= 0 || t + 1 >= sz - 1;
+        __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+        for (int o = 0; o < 2; o++) {
+            const int hx = (COL + 1 + o + PAR) & 1;  // X half of row o at plane t (compile-time)
+            const bool sto = outlane && yin[o] && outrow[o];
+            if (t - 3 >= z0 && t - 3 < z1 && sto && xin(hx ^ 1)) buf_store_nt<real>(x3[o], ro3, off(hx ^ 1), roff[o]);
+            if (STORE_BOTH && t - 2 >= z0 && t - 2 < z1 && sto && xin(hx ^ 1)) buf_store_nt<real>(d_m[o], ro2, off(hx ^ 1), roff[o]);
+            a_n[o] = buf_load<real>(rY, off(hx ^ 1), roff[o]);
+            fx_n[o] = buf_load<real>(zf || !yin[o] ? rXv : rFx, off(hx ^ 1), roff[o]);
+            if ((hx ^ 1) == 0 && wxface) xv_n[o] = buf_load<real>(rXv, off(0), roff[o]);
+            fy_n[o] = buf_load<real>(rFy, off(hx ^ 1), roff[o]);
+        }
+        __builtin_amdgcn_s_setprio(0);
+        // ---- stage 1: X at plane t (half hx) from the loaded Y
+        const bool zin1 = t >= 1 && t <= sz - 2, zin2 = t - 1 >= 1 && t - 1 <= sz - 2;
+        {
+            const real nb = sY[PB][wU][1][lane], sb = sY[PB][wD][0][lane];
+#pragma unroll
+            for (int o = 0; o < 2; o++) {
+                const real v1 = (((COL + 1 + PAR) & 1) ^ o) == 0
+                                    ? relax(std::integral_constant<int, 0>{}, o, a_c, nb, sb, a_m[o], a_p[o], fx_c[o])
+                                    : relax(std::integral_constant<int, 1>{}, o, a_c, nb, sb, a_m[o], a_p[o], fx_c[o]);
+                const int hx = (COL + 1 + o + PAR) & 1;
+                b_c[o] = zin1 && yin[o] && xin(hx) ? v1 : fx_c[o];
+            }
+        }
+        // ---- stage 2: Y at plane t - 1 (half hx) from the stage-1 X
+        {
+            const real nb = sX[PB][wU][1][lane], sb = sX[PB][wD][0][lane];
+#pragma unroll
+            for (int o = 0; o < 2; o++) {
+                const real v2 = (((COL + 1 + PAR) & 1) ^ o) == 0
+                                    ? relax(std::integral_constant<int, 0>{}, o, b_m, nb, sb, b_mm[o], b_c[o], fy_c[o])
+                                    : relax(std::integral_constant<int, 1>{}, o, b_m, nb, sb, b_mm[o], b_c[o], fy_c[o]);
+                const int hx = (COL + 1 + o + PAR) & 1;
+                d_c[o] = zin2 && yin[o] && xin(hx) ? v2 : a_m[o];
+            }
+        }
+        // ---- stage 3: X at plane t - 2 (half hx) from the stage-2 Y; stored in the next iteration
+        {
+            const real nb = sZ[PB][wU][1][lane], sb = sZ[PB][wD][0][lane];
+#pragma unroll
+            for (int o = 0; o < 2; o++) {
+                x3[o] = (((COL + 1 + PAR) & 1) ^ o) == 0
+                            ? relax(std::integral_constant<int, 0>{}, o, d_m, nb, sb, d_mm[o], d_c[o], fx_2[o])
+                            : relax(std::integral_constant<int, 1>{}, o, d_m, nb, sb, d_mm[o], d_c[o], fx_2[o]);
+            }
+        }
+        // ---- publish: Y of plane t + 1, stage-1 X of plane t, stage-2 Y of plane t - 1 (first and last row)
+#pragma unroll
+        for (int o = 0; o < 2; o++) {
+            sY[PAR][w][o][lane] = a_p[o];
+            sX[PAR][w][o][lane] = b_c[o];
+            sZ[PAR][w][o][lane] = d_c[o];
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this iteration's requests have had the whole iteration
+#pragma unroll
+        for (int o = 0; o < 2; o++) {
+            a_m[o] = a_c[o]; a_c[o] = a_p[o]; a_p[o] = a_n[o];
+            fx_2[o] = fx_1[o]; fx_1[o] = fx_c[o];
+            fx_c[o] = ((COL + 1 + o + PAR) & 1) == 1 && wxface && xface0 ? xv_n[o] : fx_n[o];  // x-face lanes: v of the even X entry
+            fy_c[o] = fy_n[o];
+            b_mm[o] = b_m[o]; b_m[o] = b_c[o];
+            d_mm[o] = d_m[o]; d_m[o] = d_c[o];
+        }
+    };
+
+    int t = t0;
+    if (t & 1) iteration(std::integral_constant<int, 1>{}, t++);
+    for (;; t += 2) {
+        iteration(std::integral_constant<int, 0>{}, t);
+        if (t == tlast) break;
+        iteration(std::integral_constant<int, 1>{}, t + 1);
+        if (t + 1 == tlast) break;
+    }
+    // ---- the last X: plane z1 - 1 = tlast - 2
+    {
+        const auto ro3 = plane(vout, tlast - 2);
+#pragma unroll
+        for (int o = 0; o < 2; o++) {
+            const int hx = (COL + 1 + o + tlast) & 1;
+            if (outlane && yin[o] && outrow[o] && xin(hx)) buf_store_nt<real>(x3[o], ro3, off(hx), roff[o]);
+        }
+    }
+}
+
+// Does the three-pass launch take the level?  The levels relax_rr3d_xs_kernel takes by its own rule (fp64 from 385-point rows
+// on), not those forced into it by rr3d.black = 2; one plane addressed through a 32-bit buffer descriptor.
+bool relax_block3_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int part) {
+    if (!(ctx->block3 & part) || elem != 8) return false;
+    if ((unsigned long long)Geo<XSplit, double>(n[0], n[1]).PL * 8ull >= (1ull << 31)) return false;
+    return n[0] >= 385 && n[1] >= 129 && n[2] >= 65;
+}
+
+// colour passes first_colour, 1 - first_colour, first_colour over the interior of an (n[0], n[1], n[2]) level in one launch:
+// reads the other colour and the faces of the grid from vin, f; writes first_colour's interior points (store_both: both
+// colours') into vout.  Any size the smoother accepts.
+template <class real>
+void relax3d_xs_block3_launch(mgx_ctx* ctx, const real* vin, real* vout, const real* f, const int n[3], real hx2, real hy2, real hz2,
+                              int first_colour, bool store_both) {
+    constexpr int TW = 16;
+    const int gx = ceil_div((n[0] - 1) / 2, 60), gy = ceil_div(n[1] - 2, 2 * TW - 6);
+    const int tiles = gx * gy, planes = n[2] - 2;
+    // every workgroup takes the same time and has a CU to itself: the fewest runs that fill whole rounds to 90 %, counting the
+    // three planes a run relaxes before its first store and the one after, runs of at least 16 planes
+    int nchunks = 1;
+    double best = 0;
+    for (int c = 1; c <= 64 && (c == 1 || planes / c >= 16); c++) {
+        const long long wgs = (long long)tiles * c, cap = ctx->num_cus;
+        const double eff = (double)wgs / (double)(((wgs + cap - 1) / cap) * cap) * (double)planes / (double)(planes + 4 * c);
+        if (eff > best + 1e-9) { best = eff; nchunks = c; }
+        if (eff >= 0.9) break;
+    }
+    const int zrun = ceil_div(planes, nchunks);
+    const dim3 grid(tiles * ceil_div(planes, zrun), 1, 1), blk(64, TW, 1);
+#define MGX_B3(C, S)                                                                                                          \
+    MGX_LAUNCH((relax3d_xs_block3_kernel<real, C, S, TW>), grid, blk, 0, ctx->compute, vin, vout, f, n[0], n[1], n[2], hx2, hy2, \
+               hz2, zrun, gx, gy, 1)
+    if (first_colour == 0) {
+        if (store_both) MGX_B3(0, true); else MGX_B3(0, false);
+    } else {
+        if (store_both) MGX_B3(1, true); else MGX_B3(1, false);
+    }
+#undef MGX_B3
+    snprintf(ctx->last_block3_kernel, sizeof ctx->last_block3_kernel, "relax3d_xs_block3_kernel<%s,%d,%s,%d>",
+             sizeof(real) == 8 ? "double" : "float", first_colour, store_both ? "true" : "false", TW);
+}
+template void relax3d_xs_block3_launch<double>(mgx_ctx*, const double*, double*, const double*, const int[3], double, double, double, int,
+                                               bool);
+
+}  // namespace mgx
+
+extern "C" int mgx3dxs_relax_block3_f64(mgx_ctx* ctx, const double* vin, double* vout, const double* f, const int n[3], const double h[3],
+                                        int first_colour, int store_both) {
+    MGX_REQUIRE(ctx && vin && vout && f && n && h, MGX_ERR_INVALID, "relax_block3: NULL argument");
+    MGX_USE(ctx);
+    MGX_REQUIRE(mgx::valid_size(n[0]) && mgx::valid_size(n[1]) && mgx::valid_size(n[2]), MGX_ERR_SIZE,
+                "relax_block3: sizes %d x %d x %d are not odd and >= 3", n[0], n[1], n[2]);
+    MGX_REQUIRE(first_colour == 0 || first_colour == 1, MGX_ERR_INVALID, "relax_block3: first_colour = %d not in {0, 1}", first_colour);
+    const unsigned long long plane_bytes = (unsigned long long)mgx::Geo<mgx::XSplit, double>(n[0], n[1]).PL * 8ull;
+    MGX_REQUIRE(plane_bytes < (1ull << 31), MGX_ERR_SIZE,
+                "relax_block3: a plane of %d x %d is too large", n[0], n[1]);
+    MGX_REQUIRE(!store_both || vin != vout, MGX_ERR_INVALID, "relax_block3: store_both needs vout != vin");
+    mgx::relax3d_xs_block3_launch<double>(ctx, vin, vout, f, n, h[0] * h[0], h[1] * h[1], h[2] * h[2], first_colour, store_both != 0);
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}

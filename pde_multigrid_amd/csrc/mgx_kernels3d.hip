@@ -3011,6 +3011,13 @@ template <class real>
 bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], real hx2, real hy2, real hz2, int mode, bool rcp,
                           real* coarse_f, const int cn[3], int fzoff, int czoff, int pzbeg, int pzend);
 
+bool relax_block3_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int part);  // mgx_block3d.hip
+template <class real>
+void relax3d_xs_block3_launch(mgx_ctx* ctx, const real* vin, real* vout, const real* f, const int n[3], real hx2, real hy2, real hz2,
+                              int first_colour, bool store_both);
+template <>
+void relax3d_xs_block3_launch<float>(mgx_ctx*, const float*, float*, const float*, const int[3], float, float, float, int, bool) {}  // fp64 only: never taken
+
 // The fused launch alone on a z-slab (or the whole grid): black pass of the GLOBAL fine planes [2 pzbeg - 1, 2 pzend - 1] +
 // residual + restrict into the GLOBAL coarse planes [pzbeg, pzend).  n / cn global sizes, v / f start at global plane fzoff,
 // coarse_f at global coarse plane czoff.  Reads the red values of the fine planes [2 pzbeg - 3, 2 pzend + 1] (clipped to the
@@ -3055,6 +3062,7 @@ int smooth_residual_restrict3d_xs(mgx_ctx* ctx, real* v, const real* f, const in
     MGX_REQUIRE(mode == MGX_RESIDUAL_REF_COMPAT || mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID,
                 "smooth_residual_restrict3d: bad mode %d", mode);
     ctx->last_rr_kernel[0] = 0;
+    ctx->last_block3_kernel[0] = 0;
     if (ncycles < 1 || !relax_rr3d_xs_takes(ctx, n, cn, sizeof(real))) {
         st = from_zero ? relax3d_from_zero<real, XSplit>(ctx, v, f, n, h, ncycles, v_rim_is_zero) : relax3d<real, XSplit>(ctx, v, f, n, h, ncycles);
         if (st) return st;
@@ -3075,7 +3083,11 @@ int smooth_residual_restrict3d_xs(mgx_ctx* ctx, real* v, const real* f, const in
             MGX_TRY_RET(fill_zero(ctx, v, Geo<XSplit, real>(n[0], n[1]).PL * (size_t)n[2] * sizeof(real)));
         }
     }
-    for (; s < 2 * ncycles - 1; s++) relax3d_xs_pass<real>(ctx, v, f, n[0], n[1], 1, n[2] - 1, hx2, hy2, hz2, s & 1);
+    // the last three passes are R, B, R; the rr kernel's black pass overwrites the B values without reading them, so one launch
+    // that reads black and f and stores red only (in place) stands for the three (mgx_block3d.hip)
+    const bool b3 = !from_zero && 2 * ncycles - 1 - s >= 3 && relax_block3_takes(ctx, n, sizeof(real), 1);
+    for (; s < 2 * ncycles - 1 - (b3 ? 3 : 0); s++) relax3d_xs_pass<real>(ctx, v, f, n[0], n[1], 1, n[2] - 1, hx2, hy2, hz2, s & 1);
+    if (b3) relax3d_xs_block3_launch<real>(ctx, v, v, f, n, hx2, hy2, hz2, 0, false);
     if (!coarse_rim_is_zero) MGX_TRY_RET(fill_zero(ctx, coarse_f, Geo<XSplit, real>(cn[0], cn[1]).PL * (size_t)cn[2] * sizeof(real)));
     const bool rcp = ctx->rr_rcp && exact_reciprocal(hx2) && exact_reciprocal(hy2) && exact_reciprocal(hz2);
     MGX_REQUIRE(relax_rr3d_xs_launch<real>(ctx, v, f, n, hx2, hy2, hz2, mode, rcp, coarse_f, cn, 0, 0, 1, cn[2] - 1), MGX_ERR_INVALID,
@@ -3785,6 +3797,7 @@ MGX_DEFINE_MISC3D(f64, double)
 const char* mgx_ctx_last_relax_kernel(const mgx_ctx* ctx) { return ctx ? ctx->last_relax_kernel : ""; }
 const char* mgx_ctx_last_rr_kernel(const mgx_ctx* ctx) { return ctx ? ctx->last_rr_kernel : ""; }
 const char* mgx_ctx_last_corr_kernel(const mgx_ctx* ctx) { return ctx ? ctx->last_corr_kernel : ""; }
+const char* mgx_ctx_last_block3_kernel(const mgx_ctx* ctx) { return ctx ? ctx->last_block3_kernel : ""; }
 
 int mgx_ctx_set_param(mgx_ctx* ctx, const char* name, int value) {
     MGX_REQUIRE(ctx && name, MGX_ERR_INVALID, "set_param: NULL argument");
@@ -3918,6 +3931,9 @@ int mgx_ctx_set_param(mgx_ctx* ctx, const char* name, int value) {
         // column and f TWO steps ahead (six steps per loop trip; measured 2 % slower, kept for the record).  Default 7.
         MGX_REQUIRE(value >= 0 && value <= 31, MGX_ERR_INVALID, "set_param: relax3d.unroll = %d not in [0, 31]", value);
         ctx->pipe_unroll = value;
+    } else if (!strcmp(name, "relax3d.block3")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.block3 = %d not in {0, 1}", value);
+        ctx->block3 = value;  // bit 0: the way down runs its last three colour passes in one launch (relax3d_xs_block3_kernel)
     } else if (!strcmp(name, "relax3d.zchunk")) {
         MGX_REQUIRE(value >= 0, MGX_ERR_INVALID, "relax3d.zchunk must be >= 0 (0 = automatic)");
         ctx->relax_zchunk = value;

@@ -92,6 +92,10 @@ class Context:
         """the correcting red pass of the most recent interpolate_correct_relax call ("" = the correction was a pass of its own)"""
         return lib.mgx_ctx_last_corr_kernel(self._h).decode()
 
+    def last_block3_kernel(self):
+        """the three-pass kernel of the most recent smooth_residual_restrict / relax_block3 call ("" = passes one launch each)"""
+        return lib.mgx_ctx_last_block3_kernel(self._h).decode()
+
     def set_param(self, name, value):
         check(lib.mgx_ctx_set_param(self._h, name.encode(), C.c_int(int(value))))
 
@@ -377,6 +381,17 @@ class _Ops3D(_Ops):
         finally:
             for q in (pv, pf, pc):
                 ctx.free(q)
+
+    def relax_block3(self, ctx, vin, f, n, rng, first_colour=0, store_both=False, vout=None):
+        """x-split fp64 only: colour passes first_colour, 1 - first_colour, first_colour in one launch (mgx3dxs_relax_block3_f64).
+        Reads vin's other colour and faces and f, writes into vout (default: vin itself, in place) and returns vout"""
+        h = _rp(grid_spacing(n, rng, np.float64), C.c_double)
+        arrs = [vin, f] if vout is None else [vin, f, vout]
+        if vout is None:
+            call = lambda a, b: lib.mgx3dxs_relax_block3_f64(ctx._h, a, a, b, _ip(n), h, C.c_int(first_colour), C.c_int(int(store_both)))
+            return self._run(ctx, arrs, call, 0, _shape(n), np.float64)
+        call = lambda a, b, c: lib.mgx3dxs_relax_block3_f64(ctx._h, a, c, b, _ip(n), h, C.c_int(first_colour), C.c_int(int(store_both)))
+        return self._run(ctx, arrs, call, 2, _shape(n), np.float64)
 
     def interpolate_correct_relax(self, ctx, v, f, n, rng, coarse, ncycles, dtype=None):
         """x-split only: v += Interpolate(coarse) on the interior, then ncycles >= 1 red-black sweeps, in one call"""
