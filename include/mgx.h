@@ -122,6 +122,9 @@ int mgx_ctx_device(const mgx_ctx* ctx, int* device);
  * HBM-bound levels / wherever the geometry allows (tests), "rr3d.black_waves" 0 (by precision), 8 (two workgroups per CU), 12, 16 waves per workgroup.
  * "relax3d.block3" 1 (default) / 0: on the levels the fused black pass takes by its own rule (fp64, from 385-point rows on), the
  * last three colour passes before it (R, B, R) run as one launch that stores red only (mgx3dxs_relax_block3_f64) -- or as three.
+ * "relax3d.block3_up" 1 (default) / 0: on those levels (and where the correcting red pass runs), a post-smoothing call with a
+ * partner array (mgx3dxs_interpolate_correct_relax_pp, two sweeps or more) stores the red of that pass into the partner and runs
+ * the next three colour passes (B, R, B) as one launch that writes both colours back into v (mgx3dxs_block3_up_takes) -- or as three.
  * "gpu.exclusive" 1 (default) / 0: 0 = the GPU is shared with other contexts or processes, so the kernels whose workgroups
  * wait for each other (resident Relax, one-launch sweep of 513-point rows) are never launched; "sync.spin_limit" polls (~1 us
  * each, default 2^21) before such a wait gives up (see mgx_ctx_check); "test.handoff_fault" != 0 is a TEST HOOK that makes
@@ -137,8 +140,8 @@ const char* mgx_ctx_last_rr_kernel(const mgx_ctx* ctx);
 /* name of the kernel that ran the correcting red pass (the correction read on the fly) in the most recent
  * mgx3dxs_interpolate_correct_relax_* call; "" when that call corrected in a pass of its own */
 const char* mgx_ctx_last_corr_kernel(const mgx_ctx* ctx);
-/* name of the three-pass kernel the most recent mgx3dxs_smooth_residual_restrict_* or mgx3dxs_relax_block3_f64 call launched;
- * "" when that call ran its colour passes one launch each */
+/* name of the three-pass kernel the most recent mgx3dxs_smooth_residual_restrict_*, mgx3dxs_interpolate_correct_relax(_pp)_* or
+ * mgx3dxs_relax_block3_f64 call launched; "" when that call ran its colour passes one launch each */
 const char* mgx_ctx_last_block3_kernel(const mgx_ctx* ctx);
 /* colour passes first_colour, 1 - first_colour, first_colour of MultiGrid3D::Relax over the interior of an n[0] x n[1] x n[2]
  * x-split fp64 level, in one launch.  Reads colour 1 - first_colour and the faces of the grid from vin, f from f; writes the
@@ -398,6 +401,10 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* pass over the LOCAL planes [zbeg, zend), every other black value read through the correction; the  */ \
     /* black pass that must follow rewrites every black interior point.                                  */ \
     int mgx3dxs_corr_fused_takes_##SFX(const mgx_ctx* ctx, const int n[3], int nplanes);                \
+    /* block3_up_takes: 1 when mgx3dxs_interpolate_correct_relax_pp on a level of these sizes with      */ \
+    /* `ncycles` sweeps runs its passes B, R, B in one launch ("relax3d.block3_up"); such a call brings   */ \
+    /* w's boundary up to date (w's interior is scratch, as in relax_pp)                                  */ \
+    int mgx3dxs_block3_up_takes_##SFX(const mgx_ctx* ctx, const int n[3], int ncycles);                 \
     int mgx3dxs_correct_pset_slab_##SFX(mgx_ctx* ctx, real* v, const int n[3], int fzoff,               \
                                         const real* coarse_v, const int cn[3], int czoff, int zmin,     \
                                         int zmax);                                                      \

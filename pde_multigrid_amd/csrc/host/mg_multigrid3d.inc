@@ -341,6 +341,8 @@ static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v
                                                                     coarse->sizeXYZ, v2, mg->e_rim_valid[gridID])); /* :638-645 */
             if (MG_CAT(mgx3dxs_relax_pp_takes_, R)(mg->ctx, fine->sizeXYZ, v2) && !MG_CAT(mgx3dxs_corr_fused_takes_, R)(mg->ctx, fine->sizeXYZ, fine->sizeZ - 2))
                 mg->e_rim_valid[gridID] = 1; /* the sweeps ran on the partner array: its boundary was brought up to date */
+            if (MG_CAT(mgx3dxs_block3_up_takes_, R)(mg->ctx, fine->sizeXYZ, v2))
+                mg->e_rim_valid[gridID] = 1; /* so did the three-pass launch that reads the correcting pass's red from it */
             return MGX_OK;
         } else if (mg->fuse) {
             MG_TRY(MGXL(mg, interpolate_correct)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */

@@ -10,6 +10,10 @@
 // of the middle pass are overwritten by the rr kernel's own black pass, which reads only red: the launch stores red only and
 // streams black 0.5 + f 1.0 + red 0.5 = 2.0 words per point instead of the 4.5 of three plain passes.
 //
+// On the way up (interpolate_correct_relax3d_xs with a partner array) the passes after the correcting red pass R' are B, R, B.
+// R' stores red into the partner; the launch reads red and the faces from there and stores both colours into v: red 0.5 + f 1.0
+// in, 1.0 out = 2.5 words per point.  Storing Y cannot be done in place: a neighbouring tile still reads the old Y as halo.
+//
 // A workgroup marches its (x, y) tile through a run of z-planes with the three stages lagged one plane each:
 //
 //   iteration t:   stage 1   X at plane t       from Y (loaded) of planes t - 1, t, t + 1 and f
@@ -218,7 +222,8 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
 }
 
 // Does the three-pass launch take the level?  The levels relax_rr3d_xs_kernel takes by its own rule (fp64 from 385-point rows
-// on), not those forced into it by rr3d.black = 2; one plane addressed through a 32-bit buffer descriptor.
+// on), not those forced into it by rr3d.black = 2; one plane addressed through a 32-bit buffer descriptor.  part: bit 0 the way
+// down, bit 1 the way up (switched by relax3d.block3 / relax3d.block3_up).
 bool relax_block3_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int part) {
     if (!(ctx->block3 & part) || elem != 8) return false;
     if ((unsigned long long)Geo<XSplit, double>(n[0], n[1]).PL * 8ull >= (1ull << 31)) return false;

@@ -3325,10 +3325,12 @@ static void corr_pset_launch(mgx_ctx* ctx, real* v, int sx, int sy, int fzoff, c
 
 // the red pass through the correction over the LOCAL planes [zb, ze) of v: `coarse_sh` = the coarse array shifted so that
 // local fine plane z interpolates from its planes z >> 1 (+ 1), szl = global plane count - global index of local plane 0,
-// ckmax = last plane of coarse_sh that exists; colour = 0 + parity of the slab's global offset
+// ckmax = last plane of coarse_sh that exists; colour = 0 + parity of the slab's global offset.  vout != nullptr: the red
+// interior points go there instead of into v (nothing else of vout is written, v is only read)
 template <class real>
 static void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zb, int ze, real hx2, real hy2, real hz2, int colour,
-                            const real* coarse_sh, int cx, int cy, int szl, int ckmax, int zg0 = 0) {
+                            const real* coarse_sh, int cx, int cy, int szl, int ckmax, int zg0 = 0, real* vout = nullptr) {
+    real* const vo = vout ? vout : v;
     const int M = (sx + 1) / 2;
     int zchunk = ctx->relax_zchunk;
     if (corr_tile_pairs<real>(ctx, sx) == 256) {  // fp32, wide level: two pairs per lane
@@ -3347,7 +3349,7 @@ static void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy
             const int zce = zchunk + (zchunk & 1), q0 = (colour + 1 + zb) & 1;
             const dim3 gride((unsigned)gx2 * gy2 * ceil_div(ze - zb, zce));
 #define MGX_CU2(F, U)                                                                                                                   \
-    MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, F, 2, U>), gride, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, v, f, sx, sy, zb, ze, \
+    MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, F, 2, U>), gride, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb, ze, \
                hx2, hy2, hz2, colour, zce, gx2, gy2, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0)
             if (fnt2) { if (q0) MGX_CU2(true, 2); else MGX_CU2(true, 1); }
             else { if (q0) MGX_CU2(false, 2); else MGX_CU2(false, 1); }
@@ -3355,10 +3357,10 @@ static void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy
             return;
         }
         if (fnt2)
-            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, true, 2>), grid2, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, v, f, sx,
+            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, true, 2>), grid2, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, vo, f, sx,
                                sy, zb, ze, hx2, hy2, hz2, colour, zchunk, gx2, gy2, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0);
         else
-            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, false, 2>), grid2, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, v, f, sx,
+            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, false, 2>), grid2, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, vo, f, sx,
                                sy, zb, ze, hx2, hy2, hz2, colour, zchunk, gx2, gy2, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0);
         return;
     }
@@ -3375,10 +3377,10 @@ static void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy
         memcpy(ctx->last_corr_kernel, ctx->last_relax_kernel, sizeof ctx->last_corr_kernel);
         const dim3 gridl((unsigned)gxl * gyl * gzl);
         if (fntl)
-            MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 4, 2, true, 2>), gridl, dim3(64, 8, 1), 0, ctx->compute, (const real*)v, v, f, sx, sy, zb,
+            MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 4, 2, true, 2>), gridl, dim3(64, 8, 1), 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb,
                                ze, hx2, hy2, hz2, colour, zchunk, gxl, gyl, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0);
         else
-            MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 4, 2, false, 2>), gridl, dim3(64, 8, 1), 0, ctx->compute, (const real*)v, v, f, sx, sy, zb,
+            MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 4, 2, false, 2>), gridl, dim3(64, 8, 1), 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb,
                                ze, hx2, hy2, hz2, colour, zchunk, gxl, gyl, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0);
         return;
     }
@@ -3401,7 +3403,7 @@ static void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy
         const int zce = zchunk + (zchunk & 1), q0 = (colour + 1 + zb) & 1;
         const dim3 gride((unsigned)gx * gy * ceil_div(ze - zb, zce));
 #define MGX_CU(F, U)                                                                                                                     \
-    MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, F, 2, U>), gride, block, 0, ctx->compute, (const real*)v, v, f, sx, sy, zb, ze, hx2, hy2, \
+    MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, F, 2, U>), gride, block, 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb, ze, hx2, hy2, \
                hz2, colour, zce, gx, gy, xcd, coarse_sh, cx, cy, szl, ckmax, zg0)
         if (fnt) { if (q0) MGX_CU(true, 2); else MGX_CU(true, 1); }
         else { if (q0) MGX_CU(false, 2); else MGX_CU(false, 1); }
@@ -3409,10 +3411,10 @@ static void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy
         return;
     }
     if (fnt)
-        MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, true, 2>), grid, block, 0, ctx->compute, (const real*)v, v, f, sx, sy, zb, ze,
+        MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, true, 2>), grid, block, 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb, ze,
                            hx2, hy2, hz2, colour, zchunk, gx, gy, xcd, coarse_sh, cx, cy, szl, ckmax, zg0);
     else
-        MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, false, 2>), grid, block, 0, ctx->compute, (const real*)v, v, f, sx, sy, zb, ze,
+        MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, false, 2>), grid, block, 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb, ze,
                            hx2, hy2, hz2, colour, zchunk, gx, gy, xcd, coarse_sh, cx, cy, szl, ckmax, zg0);
 }
 
@@ -3424,8 +3426,19 @@ static void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy
 // then the sweeps.  Both give the bits of interpolate_correct + relax.
 template <class real>
 int relax3d_xs_pp(mgx_ctx* ctx, real* v, real* w, const real* f, const int n[3], const real h[3], int ncycles, int w_rim_valid);  // mgx_sweep3d.hip
+template <class real>
+void copy_rim3d_xs(mgx_ctx* ctx, const real* v, real* w, const int n[3]);  // mgx_sweep3d.hip
 
-// w != nullptr: a second array of the level's size as ping-pong partner for the sweeps (mgx3dxs_relax_pp)
+// Does a call with a partner array run the way up's passes 2, 3, 4 (B, R, B) as one launch (relax3d_xs_block3_kernel, both
+// colours stored)?  Levels that take the correcting red pass and the three-pass launch's rule (fp64, from 385-point rows on),
+// two sweeps or more.
+static bool block3_up_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int ncycles) {
+    return ncycles >= 2 && corr_fused_takes(ctx, n[0], n[1], n[2], n[2] - 2) && relax_block3_takes(ctx, n, elem, 2);
+}
+
+// w != nullptr: a second array of the level's size as ping-pong partner for the sweeps (mgx3dxs_relax_pp); on the levels
+// block3_up_takes, the scratch array between the correcting red pass and the three-pass launch.  w_rim_valid != 0: the caller
+// vouches that w's boundary entries equal v's.
 template <class real>
 int interpolate_correct_relax3d_xs(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], const real* coarse_v,
                                    const int cn[3], int ncycles, real* w = nullptr, int w_rim_valid = 0) {
@@ -3437,6 +3450,7 @@ int interpolate_correct_relax3d_xs(mgx_ctx* ctx, real* v, const real* f, const i
     if (st) return st;
     MGX_REQUIRE(ncycles >= 1, MGX_ERR_INVALID, "interpolate_correct_relax3d: ncycles = %d < 1 (use interpolate_correct)", ncycles);
     ctx->last_corr_kernel[0] = 0;
+    ctx->last_block3_kernel[0] = 0;
     const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];  // :498-500
     const int sx = n[0], sy = n[1], sz = n[2], zb = 1, ze = sz - 1;
     if (!corr_fused_takes(ctx, sx, sy, sz, ze - zb)) {
@@ -3446,8 +3460,15 @@ int interpolate_correct_relax3d_xs(mgx_ctx* ctx, real* v, const real* f, const i
         return relax3d<real, XSplit>(ctx, v, f, n, h, ncycles);
     }
     corr_pset_launch<real>(ctx, v, sx, sy, 0, coarse_v, cn, 0, 1, sz - 1);
-    corr_red_launch<real>(ctx, v, f, sx, sy, zb, ze, hx2, hy2, hz2, 0, coarse_v, cn[0], cn[1], sz, (sz - 1) >> 1);
-    for (int s = 1; s < 2 * ncycles; s++) relax3d_xs_pass<real>(ctx, v, f, sx, sy, zb, ze, hx2, hy2, hz2, s & 1);
+    // The passes after the correcting red pass R' are B, R, B, ...  B, R, B need only red and f, so R' stores red into w
+    // instead (reading black from v), and one launch reads red and the faces from w and writes both colours of every interior
+    // point into v (mgx_block3d.hip).  It stores a tile's values while the neighbouring tiles still read theirs as halo: it
+    // cannot run in place.
+    const bool b3 = w && w != v && block3_up_takes(ctx, n, sizeof(real), ncycles);
+    if (b3 && !w_rim_valid) copy_rim3d_xs<real>(ctx, v, w, n);
+    corr_red_launch<real>(ctx, v, f, sx, sy, zb, ze, hx2, hy2, hz2, 0, coarse_v, cn[0], cn[1], sz, (sz - 1) >> 1, 0, b3 ? w : nullptr);
+    if (b3) relax3d_xs_block3_launch<real>(ctx, w, v, f, n, hx2, hy2, hz2, 1, true);
+    for (int s = b3 ? 4 : 1; s < 2 * ncycles; s++) relax3d_xs_pass<real>(ctx, v, f, sx, sy, zb, ze, hx2, hy2, hz2, s & 1);
     MGX_LAUNCH_CHECK();
     return MGX_OK;
 }
@@ -3755,6 +3776,9 @@ template int relax3d_xs_from_zero<double>(mgx_ctx*, double*, const double*, cons
     int mgx3dxs_corr_fused_takes_##SFX(const mgx_ctx* ctx, const int n[3], int nplanes) {                        \
         return ctx && n && mgx::corr_fused_takes(ctx, n[0], n[1], n[2], nplanes);                                \
     }                                                                                                            \
+    int mgx3dxs_block3_up_takes_##SFX(const mgx_ctx* ctx, const int n[3], int ncycles) {                         \
+        return ctx && n && mgx::block3_up_takes(ctx, n, sizeof(real), ncycles);                                  \
+    }                                                                                                            \
     int mgx3dxs_correct_pset_slab_##SFX(mgx_ctx* ctx, real* v, const int n[3], int fzoff, const real* coarse_v,  \
                                         const int cn[3], int czoff, int zmin, int zmax) {                        \
         return mgx::correct_pset3d_slab<real>(ctx, v, n, fzoff, coarse_v, cn, czoff, zmin, zmax);                \
@@ -3933,7 +3957,10 @@ int mgx_ctx_set_param(mgx_ctx* ctx, const char* name, int value) {
         ctx->pipe_unroll = value;
     } else if (!strcmp(name, "relax3d.block3")) {
         MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.block3 = %d not in {0, 1}", value);
-        ctx->block3 = value;  // bit 0: the way down runs its last three colour passes in one launch (relax3d_xs_block3_kernel)
+        ctx->block3 = (ctx->block3 & ~1) | value;  // bit 0: the way down runs its last three colour passes in one launch (relax3d_xs_block3_kernel)
+    } else if (!strcmp(name, "relax3d.block3_up")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.block3_up = %d not in {0, 1}", value);
+        ctx->block3 = (ctx->block3 & ~2) | (value << 1);  // bit 1: the way up runs its passes B, R, B after R' in one launch
     } else if (!strcmp(name, "relax3d.zchunk")) {
         MGX_REQUIRE(value >= 0, MGX_ERR_INVALID, "relax3d.zchunk must be >= 0 (0 = automatic)");
         ctx->relax_zchunk = value;

@@ -837,6 +837,14 @@ int relax3d_xs_pp(mgx_ctx* ctx, real* v, real* w, const real* f, const int n[3],
     return MGX_OK;
 }
 
+// boundary entries of v -> w (the partner array of interpolate_correct_relax3d_xs's three-pass launch)
+template <class real>
+void copy_rim3d_xs(mgx_ctx* ctx, const real* v, real* w, const int n[3]) {
+    MGX_LAUNCH((copy_rim3d_xs_kernel<real>), dim3(n[2], 4), dim3(256), 0, ctx->compute, v, w, n[0], n[1], n[2]);
+}
+template void copy_rim3d_xs<float>(mgx_ctx*, const float*, float*, const int[3]);
+template void copy_rim3d_xs<double>(mgx_ctx*, const double*, double*, const int[3]);
+
 template int relax3d_xs_pp<float>(mgx_ctx*, float*, float*, const float*, const int[3], const float[3], int, int);
 template int relax3d_xs_pp<double>(mgx_ctx*, double*, double*, const double*, const int[3], const double[3], int, int);
 

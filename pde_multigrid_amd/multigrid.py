@@ -325,6 +325,11 @@ class _Ops3D(_Ops):
         s, _ = _ct(dtype)
         return bool(getattr(lib, "mgx3dxs_relax_pp_takes_" + s)(ctx._h, _ip(n), C.c_int(ncycles)))
 
+    def block3_up_takes(self, ctx, n, ncycles, dtype=np.float64):
+        """does interpolate_correct_relax_pp run the passes B, R, B after the correcting red pass in one launch?"""
+        s, _ = _ct(dtype)
+        return bool(getattr(lib, "mgx3dxs_block3_up_takes_" + s)(ctx._h, _ip(n), C.c_int(ncycles)))
+
     def residual(self, ctx, v, f, n, rng, mode=REF_COMPAT, dtype=None):
         dtype = dtype or v.dtype
         fn, ct = self._fn("residual", dtype)

@@ -61,5 +61,10 @@ print("  the way down in one call: Relax(2) + residual + restrict   %.4f ms  [%s
                               C.c_void_p(g1.d_f), n1, C.c_int(1)))), ctx.last_rr_kernel() or "separate launches"))
 print("  the way up in one call: interpolate + correct + Relax(2)   %.4f ms" % timed(
     lambda: P.check(icr(ctx._h, C.c_void_p(g0.d_v), C.c_void_p(g0.d_f), n0, h, C.c_void_p(g1.d_v), n1, C.c_int(2)))))
+icp = getattr(P.lib, "mgx3dxs_interpolate_correct_relax_pp_" + sfx)
+P.check(icp(ctx._h, C.c_void_p(g0.d_v), C.c_void_p(g0.d_e), C.c_void_p(g0.d_f), n0, h, C.c_void_p(g1.d_v), n1, C.c_int(2), C.c_int(0)))
+print("  the way up as the cycle calls it (d_e as partner)          %.4f ms  [%s]" % (
+    timed(lambda: P.check(icp(ctx._h, C.c_void_p(g0.d_v), C.c_void_p(g0.d_e), C.c_void_p(g0.d_f), n0, h, C.c_void_p(g1.d_v), n1,
+                              C.c_int(2), C.c_int(1)))), ctx.last_block3_kernel() or "separate launches"))
 print("  interpolate+correct (black)     %.4f ms" % timed(lambda: P.check(ic(ctx._h, C.c_void_p(g0.d_v), n0, C.c_void_p(g1.d_v), n1, C.c_int(1)))))
 print("  zero fill of the coarse v       %.4f ms" % timed(lambda: mg.setToValue_v(1, 0.0, True)))
