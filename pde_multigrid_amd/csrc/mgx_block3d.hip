@@ -241,15 +241,7 @@ void relax3d_xs_block3_launch(mgx_ctx* ctx, const real* vin, real* vout, const r
     const int tiles = gx * gy, planes = n[2] - 2;
     // every workgroup takes the same time and has a CU to itself: the fewest runs that fill whole rounds to 90 %, counting the
     // three planes a run relaxes before its first store and the one after, runs of at least 16 planes
-    int nchunks = 1;
-    double best = 0;
-    for (int c = 1; c <= 64 && (c == 1 || planes / c >= 16); c++) {
-        const long long wgs = (long long)tiles * c, cap = ctx->num_cus;
-        const double eff = (double)wgs / (double)(((wgs + cap - 1) / cap) * cap) * (double)planes / (double)(planes + 4 * c);
-        if (eff > best + 1e-9) { best = eff; nchunks = c; }
-        if (eff >= 0.9) break;
-    }
-    const int zrun = ceil_div(planes, nchunks);
+    const int zrun = ceil_div(planes, runs_filling_rounds(tiles, planes, ctx->num_cus, 64, 16, 4));
     const dim3 grid(tiles * ceil_div(planes, zrun), 1, 1), blk(64, TW, 1);
 #define MGX_B3(C, S)                                                                                                          \
     MGX_LAUNCH((relax3d_xs_block3_kernel<real, C, S, TW>), grid, blk, 0, ctx->compute, vin, vout, f, n[0], n[1], n[2], hx2, hy2, \

@@ -109,6 +109,22 @@ int fill_zero(mgx_ctx* ctx, void* dst, size_t bytes);  // dst[0, bytes) := 0 on 
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Launches whose workgroups all take the same time: the fewest runs of `planes` planes that fill whole rounds of `slots` workgroup
+// slots to 90 % with `tiles` workgroups per run, counting the `lead` planes a run processes before its first result as lost (else
+// the best count seen).  At most max_runs runs of at least min_run planes each; one run is always allowed.
+inline int runs_filling_rounds(long long tiles, int planes, long long slots, int max_runs, int min_run, int lead) {
+    int runs = 1;
+    double best = 0;
+    for (int c = 1; c <= max_runs && (c == 1 || planes / c >= min_run); c++) {
+        const long long wgs = tiles * c;
+        double eff = (double)wgs / (double)(((wgs + slots - 1) / slots) * slots);
+        if (lead > 0) eff = eff * (double)planes / (double)(planes + lead * c);
+        if (eff > best + 1e-9) { best = eff; runs = c; }
+        if (eff >= 0.9) break;
+    }
+    return runs;
+}
+
 template <class real>
 inline void note_relax_kernel(mgx_ctx* ctx, const char* name, int a, int b, int c, bool fnt = false) {
     snprintf(ctx->last_relax_kernel, sizeof ctx->last_relax_kernel, "%s<%s,%d,%d,%d%s>", name, sizeof(real) == 8 ? "double" : "float",

@@ -2317,12 +2317,6 @@ __global__ void __launch_bounds__(1024) residual_sumsq_final_kernel(const double
 
 // =========================================================================== host side
 static inline dim3 blk() { return dim3(64, 4, 1); }
-// the kernels that address planes through buffer descriptors (the unrolled step loops: mgx_pipe_step.inc) cover up to four planes with
-// one 32-bit range: levels whose planes are larger than that stay on the rolled kernels (64-bit pointers)
-template <class real>
-static inline bool planes_fit_descriptor(int sx, int sy) {
-    return (unsigned long long)Geo<XSplit, real>(sx, sy).PL * sizeof(real) * 4ull < (1ull << 32);
-}
 static inline dim3 grd(int nx, int ny, int nz) { return dim3(ceil_div(nx, 64), ceil_div(ny, 4), nz); }
 
 static int check_n3(const int n[3], const char* what) {
@@ -2387,71 +2381,6 @@ static void launch_xs_rows(mgx_ctx* ctx, real* v, const real* f, int sx, int sy,
     }
 }
 
-// kind: 1 = relax3d_xs_pipe_kernel, 2 = the same with non-temporal loads of f (2 x 8 waves of 2 rows only),
-// 0 = relax3d_xs_lds_kernel (diagnostic builds)
-template <class real, int WX, int WY, int R>
-static void launch_xs_lds(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zbeg, int zend, real hx2, real hy2,
-                          real hz2, int colour, int zchunk, int kind) {
-    const int M = (sx + 1) / 2;
-    const int gx = ceil_div(M - 1, 64 * WX), gy = ceil_div(sy - 2, WY * R), gz = ceil_div(zend - zbeg, zchunk);
-    const dim3 grid((unsigned)gx * gy * gz), block(64, WX * WY, 1);
-    const int xcd = ctx->relax_xcd == 1 ? 1 : 0;
-    note_relax_kernel<real>(ctx, kind ? "relax3d_xs_pipe_kernel" : "relax3d_xs_lds_kernel", WX, WY, R, kind == 2 && R == 2 && WX * WY == 16);
-    // the shapes the automatic choice takes (2 x 8 and 2 x 4 waves of 2 rows): the step loop unrolled four times (see the kernel); the
-    // launch hands every run an even number of planes so that all runs start with the row parity the instantiation is compiled for
-#ifdef MGX_DIAGNOSTICS
-    constexpr bool full_row_shape = WX == 4 && WY == 4;  // tiles of 256 pairs x 8 rows: timing experiments only
-#else
-    constexpr bool full_row_shape = false;
-#endif
-    if constexpr (R == 2 && ((WX == 2 && (WY == 8 || WY == 4)) || full_row_shape)) {
-        if (kind >= 1 && (ctx->pipe_unroll & 2) && (sizeof(real) == 8 || (ctx->pipe_unroll & 8)) && planes_fit_descriptor<real>(sx, sy)) {
-            const int zce = zchunk + (zchunk & 1), q0 = (colour + 1 + zbeg) & 1;
-            const dim3 gride((unsigned)gx * gy * ceil_div(zend - zbeg, zce));
-            // the name rocprofv3 shows carries <..., VAR = 0, UNR = 1 / 2 by q0 (3 / 4: two steps ahead), CSP = 0>
-            snprintf(ctx->last_relax_kernel, sizeof ctx->last_relax_kernel, "relax3d_xs_pipe_kernel<%s,%d,%d,2,%s,0,unrolled%s>", sizeof(real) == 8 ? "double" : "float",
-                     WX, WY, kind == 2 && WY == 8 ? "true" : "false", (ctx->pipe_unroll & 16) ? " depth 2" : "");
-#ifdef MGX_DIAGNOSTICS
-            const int xcda = xcd | ((ctx->relax_ablate >= 100 ? ctx->relax_ablate - 100 : 0) << 4);  // "relax3d.ablate" = 100 + bits: see the kernel
-#else
-            const int xcda = xcd;
-#endif
-#define MGX_PU(F, U)                                                                                                                    \
-    MGX_LAUNCH((relax3d_xs_pipe_kernel<real, WX, WY, 2, F, 0, U>), gride, block, 0, ctx->compute, (const real*)v, v, f, sx, sy, zbeg, zend, hx2, \
-               hy2, hz2, colour, zce, gx, gy, xcda)
-            // bit 4: DEPTH 2 (the column and f requested two steps ahead: twice the bytes in flight)
-#ifdef MGX_DIAGNOSTICS
-            if (ctx->relax_ablate == 77) {  // TIMING ONLY: the access pattern of a colour-contiguous layout (wrong results)
-                if (kind == 2 && WY == 8) MGX_LAUNCH((relax3d_xs_pipe_kernel<real, WX, WY, 2, true, 0, 1, 1>), gride, block, 0, ctx->compute, (const real*)v, v, f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour, zce, gx, gy, xcd);
-                else MGX_LAUNCH((relax3d_xs_pipe_kernel<real, WX, WY, 2, false, 0, 1, 1>), gride, block, 0, ctx->compute, (const real*)v, v, f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour, zce, gx, gy, xcd);
-                return;
-            }
-#endif
-#define MGX_PUQ(F)                                                              \
-    do {                                                                        \
-        if (ctx->pipe_unroll & 16) { if (q0) MGX_PU(F, 4); else MGX_PU(F, 3); } \
-        else { if (q0) MGX_PU(F, 2); else MGX_PU(F, 1); }                       \
-    } while (0)
-            if (kind == 2 && WY == 8) MGX_PUQ(true);
-            else MGX_PUQ(false);
-#undef MGX_PUQ
-#undef MGX_PU
-            return;
-        }
-    }
-    if (kind == 2 && R == 2 && WX * WY == 16)  // f is read once per pass: non-temporal loads
-        MGX_LAUNCH((relax3d_xs_pipe_kernel<real, WX, WY, (R == 2 && WX * WY == 16 ? R : 2), true>), grid, block, 0,
-                           ctx->compute, (const real*)v, v, f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour, zchunk, gx, gy, xcd);
-#ifdef MGX_DIAGNOSTICS
-    else if (kind == 0)
-        MGX_LAUNCH((relax3d_xs_lds_kernel<real, WX, WY, R>), grid, block, 0, ctx->compute, (const real*)v, v, f, sx, sy,
-                           zbeg, zend, hx2, hy2, hz2, colour, zchunk, gx, gy, xcd);
-#endif
-    else
-        MGX_LAUNCH((relax3d_xs_pipe_kernel<real, WX, WY, R>), grid, block, 0, ctx->compute, (const real*)v, v, f, sx, sy,
-                           zbeg, zend, hx2, hy2, hz2, colour, zchunk, gx, gy, xcd);
-}
-
 // workgroup shapes 100*WX + 10*WY + R compiled into the library (diagnostic builds carry the whole sweep of round 1)
 #ifdef MGX_DIAGNOSTICS
 #define MGX_LDS_SHAPES(X)                                                                                          \
@@ -2467,8 +2396,6 @@ static bool relax3d_lds_shape_known(int shape) {
     return false;
 }
 
-// LDS-exchange smoother: "relax3d.lds" = 1000 + 100*WX + 10*WY + R picks the workgroup shape (+ 2000: non-temporal f).
-// Returns false when the level is too small for the shape (the caller falls back to relax3d_xs_kernel).
 // the shortest run of planes the automatic choice hands to the pipelined kernel.  Its launch has a floor (one workgroup per tile
 // column filling and draining its pipeline: ~20 us at 1025-point rows, 17 us at 513, 11.5 us at 257) under which
 // relax3d_xs_kernel's many small workgroups win; measured per plane size and run length with tools/slab_pass_time.py
@@ -2492,79 +2419,203 @@ static bool pipe_v2_takes(const mgx_ctx* ctx, int sx) {
     return sizeof(real) == 4 && ctx->relax_v2 && pairs >= 256 && pairs % 2 == 0;
 }
 
+// ---- the pipelined smoother, relax3d_xs_pipe_kernel and relax3d_xs_pipe_v2_kernel: pipe_plan decides how a pass launches,
+// pipe_launch launches it
+enum class PipePass { Plain, Zero, Corr };  // a colour pass; the first sweep from zero (VAR = 3); the correcting red pass (VAR = 2)
+
+struct PipePlan {
+    bool v2 = false;            // relax3d_xs_pipe_v2_kernel (two x-pairs per lane)
+    int WX = 2, WY = 8, R = 2;  // waves across x and y, rows per wave
+    bool fnt = false;           // non-temporal loads of f
+    int unr = 0;                // 0: the rolled step loop; unrolled four times: 1 + q0 (entry row parity q0), 3 + q0 requesting two steps ahead
+    int zchunk = 0;             // planes per run (even when unrolled)
+    int gx = 0, gy = 0;         // tiles across x and y
+    dim3 grid, block;
+    int xcd = 0;
+    // the correcting pass corrects every value it reads from a neighbouring tile itself: no set P beforehand
+    bool corrects_edges() const { return !v2 || unr; }
+};
+
+// the shapes with an unrolled step loop: those of the automatic choice (2 x 8 and 2 x 4 waves of 2 rows) and, in diagnostic builds,
+// tiles of 256 pairs x 8 rows (timing experiments only)
+static constexpr bool pipe_shape_unrolls(int WX, int WY, int R) {
+#ifdef MGX_DIAGNOSTICS
+    if (WX == 4 && WY == 4 && R == 2) return true;
+#endif
+    return R == 2 && WX == 2 && (WY == 8 || WY == 4);
+}
+
+// The launch of a pass over the planes [zbeg, zend) of a level of sy rows of sx points, colour = the colour it updates.  Returns
+// false when the pipelined kernels do not take the level (the correcting pass: the caller has asked corr_fused_takes).
 template <class real>
-static bool relax3d_xs_pass_lds(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zbeg, int zend, real hx2, real hy2,
-                                real hz2, int colour) {
-    const int M = (sx + 1) / 2;
-    int zchunk = ctx->relax_zchunk;
-    int code = ctx->relax_lds;
-    if (code < 0 && pipe_v2_takes<real>(ctx, sx) && sy - 2 >= 64 && zend - zbeg >= 8) {
-        // fp32 on wide levels: two pairs per lane (8-byte loads), 2 x 8 waves of 2 rows over 256 pairs x 16 rows
-        if (zchunk <= 0) {
-            const int tiles = ceil_div(M - 1, 256) * ceil_div(sy - 2, 16);
-            const int nchunks = max(1, (ctx->num_cus + tiles / 2) / tiles);  // one resident round of workgroups, as in fp64 (measured)
-            zchunk = max(8, ceil_div(zend - zbeg, nchunks));
+static bool pipe_plan(const mgx_ctx* ctx, PipePass pass, int sx, int sy, int zbeg, int zend, int colour, PipePlan& p) {
+    const int M = (sx + 1) / 2, planes = zend - zbeg, u = ctx->pipe_unroll;
+    const bool fp64 = sizeof(real) == 8;
+    // f is read exactly once per pass: load it non-temporally when the pass is too large to stay in the 256 MiB Infinity Cache
+    // anyway (+1.5 % at 513^3 and 1025^3); a cache-resident level (257^3) is 5 % faster without
+    const bool big = (size_t)sx * sy * (size_t)planes * sizeof(real) > ((size_t)256 << 20);
+    int target = 0;       // > 0: runs of planes that make one resident round of `target` workgroups
+    bool unroll = false;  // relax3d.unroll has the pass's bit set (one-pair fp32: and bit 8)
+    p = PipePlan();
+    p.fnt = big;
+    if (pass == PipePass::Corr) {
+        if (ctx->corr_v2 && pipe_v2_takes<real>(ctx, sx)) {  // fp32, wide level: two pairs per lane
+            p.v2 = true;
+            target = ctx->num_cus;
+            unroll = u & 4;
+        } else if (ctx->corr_low && fp64) {  // EXPERIMENT: 8-wave workgroups (tiles of 8 rows), two to a CU; rolled only
+            p.WY = 4;
+            target = 2 * ctx->num_cus;
+        } else {
+            target = ctx->num_cus * (fp64 ? 1 : 8);
+            unroll = (u & 1) && (fp64 || (u & 8));
         }
-        const int gx2 = ceil_div(M - 1, 256), gy2 = ceil_div(sy - 2, 16), gz2 = ceil_div(zend - zbeg, zchunk);
-        const bool fnt = (size_t)sx * sy * (size_t)(zend - zbeg) * sizeof(real) > ((size_t)256 << 20);
-        const int xcd = ctx->relax_xcd == 1 ? 1 : 0;
-        const dim3 grid2((unsigned)gx2 * gy2 * gz2);
-        note_relax_kernel<real>(ctx, "relax3d_xs_pipe_v2_kernel", 2, 8, 2, fnt);
-        if ((ctx->pipe_unroll & 4) && planes_fit_descriptor<real>(sx, sy)) {  // the step loop unrolled four times (runs of an even number of planes, entry parity q0)
-            const int zce = zchunk + (zchunk & 1), q0 = (colour + 1 + zbeg) & 1;
-            const dim3 gride((unsigned)gx2 * gy2 * ceil_div(zend - zbeg, zce));
-#define MGX_PU2(F, U)                                                                                                                  \
-    MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, F, 0, U>), gride, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, v, f, sx, sy, zbeg, \
-               zend, hx2, hy2, hz2, colour, zce, gx2, gy2, xcd)
-            if (fnt) { if (q0) MGX_PU2(true, 2); else MGX_PU2(true, 1); }
-            else { if (q0) MGX_PU2(false, 2); else MGX_PU2(false, 1); }
-#undef MGX_PU2
-            return true;
-        }
-        if (fnt)
-            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, true>), grid2, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, v, f, sx, sy,
-                               zbeg, zend, hx2, hy2, hz2, colour, zchunk, gx2, gy2, xcd);
-        else
-            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, false>), grid2, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, v, f, sx, sy,
-                               zbeg, zend, hx2, hy2, hz2, colour, zchunk, gx2, gy2, xcd);
-        return true;
-    }
-    if (code < 0) {
+    } else if (pass == PipePass::Plain && ctx->relax_lds < 0 && pipe_v2_takes<real>(ctx, sx)) {
+        // fp32 on wide levels: two pairs per lane (8-byte loads), 2 x 8 waves of 2 rows over 256 pairs x 16 rows, one resident round
+        // of workgroups as in fp64 (measured)
+        if (sy - 2 < 64 || planes < 8) return false;
+        p.v2 = true;
+        target = ctx->num_cus;
+        unroll = u & 4;
+    } else if (pass == PipePass::Zero || ctx->relax_lds < 0) {
         // automatic (the default).  Measured on MI355X (tools/sweep_pipe.py, profiles/r01_sweep_pipe_*.txt): the
         // pipelined kernel with 2 x 8 waves of 2 rows wins from 257^3 up when the launch is ONE resident round of
         // workgroups -- about one 16-wave workgroup per CU, each streaming a long run of planes (fp32 moves half the
         // bytes per wave and wants 8 x as many, shorter runs); below 257^2 rows, or for runs of a few planes (the
-        // edge planes of a z-slab), relax3d_xs_kernel is faster.
-        if (M - 1 < 128 || sy - 2 < 64 || zend - zbeg < pipe_min_planes<real>(sx)) return false;
-        // f is read exactly once per pass: load it non-temporally when the pass is too large to stay in the 256 MiB
-        // Infinity Cache anyway (+1.5 % at 513^3 and 1025^3); a cache-resident level (257^3) is 5 % faster without
-        code = (size_t)sx * sy * (size_t)(zend - zbeg) * sizeof(real) > ((size_t)256 << 20) ? 3282 : 1282;
+        // edge planes of a z-slab), relax3d_xs_kernel is faster.  The first sweep from zero takes the same levels from 8 planes on,
+        // except fp32 levels wide enough for the two-pairs-per-lane kernel.
+        if (pass == PipePass::Zero ? !ctx->relax_zero_sweep || ctx->relax_lds != -1 || pipe_v2_takes<real>(ctx, sx) || planes < 8
+                                   : planes < pipe_min_planes<real>(sx))
+            return false;
+        if (M - 1 < 128 || sy - 2 < 64) return false;
         // up to 257 rows (fp64): 2 x 4 waves over 8 rows, two 8-wave workgroups per CU -- twice the tiles, so runs of 16
         // instead of 8 planes (the three planes a run loads before its first result weigh half as much): 37.3 against
         // 39.4 us per pass at 257^3
-        const bool low = sizeof(real) == 8 && sy - 2 <= 256 && code == 1282;
-        if (low) code = 1242;
-        if (zchunk <= 0) {
-            const int tiles = ceil_div(M - 1, 128) * ceil_div(sy - 2, low ? 8 : 16);
-            const int target = ctx->num_cus * (sizeof(real) == 4 ? 8 : (low ? 2 : 1));
-            const int nchunks = max(1, (target + tiles / 2) / tiles);
-            zchunk = max(8, ceil_div(zend - zbeg, nchunks));
+        const bool low = fp64 && sy - 2 <= 256 && !big;
+        if (low) p.WY = 4;
+        target = ctx->num_cus * (fp64 ? (low ? 2 : 1) : 8);
+        unroll = (u & 2) && (fp64 || (u & 8));
+    } else {  // "relax3d.lds" = 1000 + 100*WX + 10*WY + R (+ 2000: non-temporal f; below 1000: relax3d_xs_lds_kernel, diagnostic builds)
+        const int code = ctx->relax_lds % 1000;
+        p.WX = code / 100;
+        p.WY = (code / 10) % 10;
+        p.R = code % 10;
+        if (M - 1 < 64 * p.WX || sy - 2 < p.WY * p.R) return false;
+        p.fnt = ctx->relax_lds >= 3000 && p.R == 2 && p.WX * p.WY == 16;
+        unroll = ctx->relax_lds >= 1000 && pipe_shape_unrolls(p.WX, p.WY, p.R) && (u & 2) && (fp64 || (u & 8));
+    }
+    p.gx = ceil_div(M - 1, 64 * p.WX * (p.v2 ? 2 : 1));
+    p.gy = ceil_div(sy - 2, p.WY * p.R);
+    int zchunk = ctx->relax_zchunk;
+    if (zchunk <= 0 && target > 0) {
+        const int tiles = p.gx * p.gy;
+        const int nchunks = max(1, (target + tiles / 2) / tiles);
+        zchunk = max(8, ceil_div(planes, nchunks));
+    } else if (zchunk <= 0) {  // shape codes: runs of 16 planes, halved while the launch has fewer than 32 waves per CU
+        const long long tiles = (long long)p.gx * p.gy;
+        zchunk = 16;
+        while (zchunk > 2 && tiles * ceil_div(planes, zchunk) * p.WX * p.WY < 32LL * ctx->num_cus) zchunk >>= 1;
+    }
+    if (unroll && planes_fit_descriptor<real>(sx, sy)) {
+        // the step loop unrolled four times, register roles and row parity fixed per step: runs of an even number of planes, so
+        // that every run starts with the row parity q0 the instantiation is compiled for.  relax3d.unroll bit 16 (plain one-pair
+        // passes): the column and f requested two steps ahead, twice the bytes in flight
+        const int q0 = (colour + 1 + zbeg) & 1;
+        zchunk += zchunk & 1;
+        p.unr = 1 + q0 + (pass == PipePass::Plain && !p.v2 && (u & 16) ? 2 : 0);
+        if (p.WY != 8) p.fnt = false;  // the unrolled 4 x 4 shape of diagnostic builds reads f through the caches
+    }
+    p.zchunk = zchunk;
+    p.grid = dim3((unsigned)p.gx * p.gy * ceil_div(planes, zchunk));
+    p.block = dim3(64, p.WX * p.WY, 1);
+    p.xcd = ctx->relax_xcd == 1 ? 1 : 0;
+    return true;
+}
+
+// The one launch of both kernels: the instantiation for the plan's FNT and UNR (those that exist are listed in unr_max and fnt_ok;
+// a plan asks for no other).  Records the launch as the context's last_relax_kernel: the template arguments up to VAR, in the
+// kernel's order (callers and tests read the pass kind from the end of the name; the rolled or unrolled form is not part of it).
+template <class real, bool V2, int WX, int WY, int R, int VAR>
+static void pipe_launch(mgx_ctx* ctx, const PipePlan& p, const real* vin, real* vout, const real* f, int sx, int sy, int zbeg, int zend,
+                        real hx2, real hy2, real hz2, int colour, const real* coarse = nullptr, int cx = 0, int cy = 0, int szg = 0,
+                        int ckmax = 0, int zg0 = 0) {
+    // UNR 3 / 4: the plain one-pair pass only; the correcting pass in 8-wave workgroups: rolled only
+    constexpr int unr_max = V2 || VAR == 3 ? 2 : VAR == 2 ? (WY == 8 ? 2 : 0) : (pipe_shape_unrolls(WX, WY, R) ? 4 : 0);
+    constexpr bool fnt_ok = !(VAR == 3 && WY == 4);  // the first sweep from zero in 8-wave workgroups: cache-resident levels only
+    snprintf(ctx->last_relax_kernel, sizeof ctx->last_relax_kernel, "%s<%s,%d,%d,%d,%s,%d>",
+             V2 ? "relax3d_xs_pipe_v2_kernel" : "relax3d_xs_pipe_kernel", sizeof(real) == 8 ? "double" : "float", WX, WY, R,
+             p.fnt ? "true" : "false", VAR);
+    const auto launch = [&](auto fnt, auto unr) {
+        constexpr bool F = decltype(fnt)::value;
+        constexpr int U = decltype(unr)::value;
+        if constexpr ((F && !fnt_ok) || U > unr_max) {
+            return;
+        } else if constexpr (V2) {
+            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, WX, WY, R, F, VAR, U>), p.grid, p.block, 0, ctx->compute, vin, vout, f, sx, sy,
+                       zbeg, zend, hx2, hy2, hz2, colour, p.zchunk, p.gx, p.gy, p.xcd, coarse, cx, cy, szg, ckmax, zg0);
+        } else {  // non-temporal f is compiled for two rows per wave (a plan asks for it with R = 2 only)
+            MGX_LAUNCH((relax3d_xs_pipe_kernel<real, WX, WY, F ? 2 : R, F, VAR, U>), p.grid, p.block, 0, ctx->compute, vin, vout, f, sx,
+                       sy, zbeg, zend, hx2, hy2, hz2, colour, p.zchunk, p.gx, p.gy, p.xcd, coarse, cx, cy, szg, ckmax, zg0);
+        }
+    };
+    const auto by_unr = [&](auto fnt) {
+        switch (p.unr) {
+            case 0: launch(fnt, std::integral_constant<int, 0>()); break;
+            case 1: launch(fnt, std::integral_constant<int, 1>()); break;
+            case 2: launch(fnt, std::integral_constant<int, 2>()); break;
+            case 3: launch(fnt, std::integral_constant<int, 3>()); break;
+            default: launch(fnt, std::integral_constant<int, 4>()); break;
+        }
+    };
+    if (p.fnt) by_unr(std::true_type());
+    else by_unr(std::false_type());
+}
+
+// a plain colour pass of relax3d_xs_pipe_kernel in the shape WX x WY x R (diagnostic builds: and its timing variants)
+template <class real, int WX, int WY, int R>
+static void pipe_pass_shape(mgx_ctx* ctx, PipePlan p, real* v, const real* f, int sx, int sy, int zbeg, int zend, real hx2, real hy2,
+                            real hz2, int colour) {
+#ifdef MGX_DIAGNOSTICS
+    if (ctx->relax_lds > 0 && ctx->relax_lds < 1000) {  // relax3d_xs_lds_kernel: no software pipeline
+        note_relax_kernel<real>(ctx, "relax3d_xs_lds_kernel", WX, WY, R);
+        MGX_LAUNCH((relax3d_xs_lds_kernel<real, WX, WY, R>), p.grid, p.block, 0, ctx->compute, (const real*)v, v, f, sx, sy, zbeg, zend,
+                   hx2, hy2, hz2, colour, p.zchunk, p.gx, p.gy, p.xcd);
+        return;
+    }
+    if constexpr (pipe_shape_unrolls(WX, WY, R)) {
+        if (p.unr && ctx->relax_ablate == 77) {  // TIMING ONLY: the access pattern of a colour-contiguous layout (wrong results)
+            snprintf(ctx->last_relax_kernel, sizeof ctx->last_relax_kernel, "relax3d_xs_pipe_kernel<%s,%d,%d,2,%s,0,1,1>",
+                     sizeof(real) == 8 ? "double" : "float", WX, WY, p.fnt ? "true" : "false");
+            if (p.fnt)
+                MGX_LAUNCH((relax3d_xs_pipe_kernel<real, WX, WY, 2, true, 0, 1, 1>), p.grid, p.block, 0, ctx->compute, (const real*)v, v,
+                           f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour, p.zchunk, p.gx, p.gy, p.xcd);
+            else
+                MGX_LAUNCH((relax3d_xs_pipe_kernel<real, WX, WY, 2, false, 0, 1, 1>), p.grid, p.block, 0, ctx->compute, (const real*)v, v,
+                           f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour, p.zchunk, p.gx, p.gy, p.xcd);
+            return;
         }
     }
-    const int kind = code >= 3000 ? 2 : (code >= 1000 ? 1 : 0);
-    code %= 1000;
-    const int WX = code / 100, WY = (code / 10) % 10, R = code % 10;
-    if (M - 1 < 64 * WX || sy - 2 < WY * R) return false;
-    if (zchunk <= 0) {
-        const long long tiles = (long long)ceil_div(M - 1, 64 * WX) * ceil_div(sy - 2, WY * R);
-        zchunk = 16;
-        while (zchunk > 2 && tiles * ceil_div(zend - zbeg, zchunk) * WX * WY < 32LL * ctx->num_cus) zchunk >>= 1;
-    }
-#define MGX_X(X, Y, RR)                                                                                  \
-    case 100 * X + 10 * Y + RR:                                                                          \
-        launch_xs_lds<real, X, Y, RR>(ctx, v, f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour, zchunk, kind); \
+    if (p.unr) p.xcd |= (ctx->relax_ablate >= 100 ? ctx->relax_ablate - 100 : 0) << 4;  // "relax3d.ablate" = 100 + bits: see the kernel
+#endif
+    pipe_launch<real, false, WX, WY, R, 0>(ctx, p, v, v, f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour);
+}
+
+// one colour pass on the pipelined kernels: the automatic choice, or the shape code "relax3d.lds".  Returns false when the level is
+// not taken (the caller falls back to relax3d_xs_kernel).
+template <class real>
+static bool relax3d_xs_pass_lds(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zbeg, int zend, real hx2, real hy2,
+                                real hz2, int colour) {
+    PipePlan p;
+    if (!pipe_plan<real>(ctx, PipePass::Plain, sx, sy, zbeg, zend, colour, p)) return false;
+    if (p.v2) {
+        pipe_launch<real, true, 2, 8, 2, 0>(ctx, p, v, v, f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour);
         return true;
-    switch (code) {
+    }
+#define MGX_X(X, Y, RR)                                                                                         \
+    case 100 * X + 10 * Y + RR:                                                                                 \
+        pipe_pass_shape<real, X, Y, RR>(ctx, p, v, f, sx, sy, zbeg, zend, hx2, hy2, hz2, colour); \
+        return true;
+    switch (100 * p.WX + 10 * p.WY + p.R) {
         MGX_LDS_SHAPES(MGX_X)
         default: return false;
     }
@@ -2572,44 +2623,15 @@ static bool relax3d_xs_pass_lds(mgx_ctx* ctx, real* v, const real* f, int sx, in
 }
 
 // The FIRST SWEEP of a level that counts as all zeros (boundary entries zero in memory) in one launch: the black pass with the
-// red pass folded in (relax3d_xs_pipe_kernel, VAR = 3: f in, red and black out).  Levels and shapes as the automatic choice of
-// relax3d_xs_pass_lds makes them for a colour pass (fp32 levels wide enough for the two-pairs-per-lane kernel: not taken).
+// red pass folded in (relax3d_xs_pipe_kernel, VAR = 3: f in, red and black out).
 template <class real>
 static bool relax3d_xs_first_sweep_zero(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int sz, real hx2, real hy2, real hz2) {
-    const int M = (sx + 1) / 2, zbeg = 1, zend = sz - 1;
-    if (!ctx->relax_zero_sweep || ctx->relax_lds != -1 || M - 1 < 128 || sy - 2 < 64 || zend - zbeg < 8) return false;
-    if (pipe_v2_takes<real>(ctx, sx)) return false;
-    const bool fnt = (size_t)sx * sy * (size_t)(zend - zbeg) * sizeof(real) > ((size_t)256 << 20);
-    const bool low = sizeof(real) == 8 && sy - 2 <= 256 && !fnt;
-    int zchunk = ctx->relax_zchunk;
-    if (zchunk <= 0) {
-        const int tiles = ceil_div(M - 1, 128) * ceil_div(sy - 2, low ? 8 : 16);
-        const int target = ctx->num_cus * (sizeof(real) == 4 ? 8 : (low ? 2 : 1));
-        const int nchunks = max(1, (target + tiles / 2) / tiles);
-        zchunk = max(8, ceil_div(zend - zbeg, nchunks));
-    }
-    const int gx = ceil_div(M - 1, 128), gy = ceil_div(sy - 2, low ? 8 : 16), gz = ceil_div(zend - zbeg, zchunk);
-    const dim3 grid((unsigned)gx * gy * gz);
-    const int xcd = ctx->relax_xcd == 1 ? 1 : 0;
-    snprintf(ctx->last_relax_kernel, sizeof ctx->last_relax_kernel, "relax3d_xs_pipe_kernel<%s,2,%d,2,%s,3>", sizeof(real) == 8 ? "double" : "float",
-             low ? 4 : 8, fnt ? "true" : "false");
-#define MGX_Z1(WYY, F)                                                                                                           \
-    MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, WYY, 2, F, 3>), grid, dim3(64, 2 * WYY, 1), 0, ctx->compute, f, v, f, sx, sy, zbeg, zend, \
-                       hx2, hy2, hz2, 1, zchunk, gx, gy, xcd, (const real*)nullptr, 0, 0, sz, 0)
-#define MGX_Z1U(WYY, F, U)                                                                                                         \
-    MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, WYY, 2, F, 3, U>), gride, dim3(64, 2 * WYY, 1), 0, ctx->compute, f, v, f, sx, sy, zbeg, zend, \
-                       hx2, hy2, hz2, 1, zce, gx, gy, xcd, (const real*)nullptr, 0, 0, sz, 0)
-    if ((ctx->pipe_unroll & 2) && (sizeof(real) == 8 || (ctx->pipe_unroll & 8)) && planes_fit_descriptor<real>(sx, sy)) {  // the step loop unrolled four times: runs of an even number of planes, entry parity (colour 1 + 1 + zbeg) & 1
-        const int zce = zchunk + (zchunk & 1), q0 = (1 + 1 + zbeg) & 1;
-        const dim3 gride((unsigned)gx * gy * ceil_div(zend - zbeg, zce));
-        if (low) { if (q0) MGX_Z1U(4, false, 2); else MGX_Z1U(4, false, 1); }
-        else if (fnt) { if (q0) MGX_Z1U(8, true, 2); else MGX_Z1U(8, true, 1); }
-        else { if (q0) MGX_Z1U(8, false, 2); else MGX_Z1U(8, false, 1); }
-    } else if (low) MGX_Z1(4, false);
-    else if (fnt) MGX_Z1(8, true);
-    else MGX_Z1(8, false);
-#undef MGX_Z1U
-#undef MGX_Z1
+    PipePlan p;
+    if (!pipe_plan<real>(ctx, PipePass::Zero, sx, sy, 1, sz - 1, 1, p)) return false;
+    if (p.WY == 4)
+        pipe_launch<real, false, 2, 4, 2, 3>(ctx, p, f, v, f, sx, sy, 1, sz - 1, hx2, hy2, hz2, 1, nullptr, 0, 0, sz, 0);
+    else
+        pipe_launch<real, false, 2, 8, 2, 3>(ctx, p, f, v, f, sx, sy, 1, sz - 1, hx2, hy2, hz2, 1, nullptr, 0, 0, sz, 0);
     return true;
 }
 
@@ -2911,19 +2933,9 @@ static int residual_restrict3d_xs_launch(mgx_ctx* ctx, const real* v, const real
             // kernels; ONE for the 16-wave kernel (one workgroup per CU: 513^3 = 85 tiles x 3 runs of 85 coarse planes -- the
             // three planes a run loads before its first result then weigh 2 % instead of 5 %: 512 against 540 us)
             const int tiles = gx * gy;
-            int nchunks;
-            if (T == 16) {  // the fewest runs that fill whole rounds to 90 % (1025^3: 315 tiles x 3 = 945 of 1024 slots)
-                nchunks = 1;
-                double best = 0;
-                for (int c = 1; c <= 12; c++) {
-                    const long long w = (long long)tiles * c, cap = ctx->num_cus;
-                    const double eff = (double)w / (double)(((w + cap - 1) / cap) * cap);
-                    if (eff > best + 1e-9) { best = eff; nchunks = c; }
-                    if (eff >= 0.9) { nchunks = c; break; }
-                }
-            } else {
-                nchunks = max(1, (3 * ctx->num_cus + tiles / 2) / tiles);
-            }
+            // T == 16: the fewest runs that fill whole rounds to 90 % (1025^3: 315 tiles x 3 = 945 of 1024 slots)
+            const int nchunks = T == 16 ? runs_filling_rounds(tiles, pzend - pzbeg, ctx->num_cus, 12, 0, 0)
+                                        : max(1, (3 * ctx->num_cus + tiles / 2) / tiles);
             pzc = max(4, ceil_div(pzend - pzbeg, nchunks));
         }
         dim3 g(gx * gy * ceil_div(pzend - pzbeg, pzc), 1, 1);
@@ -3299,28 +3311,23 @@ static bool corr_fused_takes(const mgx_ctx* ctx, int sx, int sy, int sz_global, 
 // the set P (tile-edge cells of that pass) corrected in place: the coarse cells covering the GLOBAL fine planes [zmin, zmax),
 // which are the only ones written.  v / coarse_v are local arrays starting at the global planes fzoff / czoff; every coarse
 // plane a written fine plane interpolates from must exist locally.
-// pairs per tile of the correcting red pass on a level of sx-point rows
-template <class real>
-static int corr_tile_pairs(const mgx_ctx* ctx, int sx) {
-    return ctx->corr_v2 && pipe_v2_takes<real>(ctx, sx) ? 256 : 128;
-}
 template <class real>
 static void corr_pset_launch(mgx_ctx* ctx, real* v, int sx, int sy, int fzoff, const real* coarse_v, const int cn[3], int czoff, int zmin,
                              int zmax) {
+    PipePlan p;
+    pipe_plan<real>(ctx, PipePass::Corr, sx, sy, zmin, zmax, 0, p);
     // the tile of the correcting pass: 128 pairs x 16 rows (relax3d_xs_pipe_kernel<real, 2, 8, 2>) or, fp32 on wide levels,
     // 256 pairs x 16 rows (relax3d_xs_pipe_v2_kernel<real, 2, 8, 2>)
-    const int PW = corr_tile_pairs<real>(ctx, sx);
+    const int PW = p.v2 ? 256 : 128;
     constexpr int PH = 8;
     const int M = (sx + 1) / 2;
     const int pzbeg = zmin / 2, pzend = (zmax - 1) / 2 + 1;
     if (pzend <= pzbeg) return;
     const int nk = (cn[1] - 2) / PH + 1;
-    if (PW != 256) return;  // relax3d_xs_pipe_kernel<.., 2> corrects everything it reads itself: its set P is empty
-    if ((ctx->pipe_unroll & 4) && planes_fit_descriptor<real>(sx, sy)) return;  // and so does the unrolled two-pair kernel (mgx_pipe2_step.inc)
+    // relax3d_xs_pipe_kernel<.., 2> and the unrolled two-pair kernel (mgx_pipe2_step.inc) correct everything they read themselves
+    if (p.corrects_edges()) return;
     MGX_LAUNCH((correct_pset3d_xs_kernel<real>), dim3(ceil_div(M - 1, 64), ceil_div(nk, 4), pzend - pzbeg), blk(), 0, ctx->compute, v,
                        sx, sy, coarse_v, cn[0], cn[1], PW, PH, 0, fzoff, czoff, pzbeg, zmin, zmax);
-    // no column part any more: both correcting kernels correct the values they take from the neighbouring tile themselves
-    (void)M;
 }
 
 // the red pass through the correction over the LOCAL planes [zb, ze) of v: `coarse_sh` = the coarse array shifted so that
@@ -3331,91 +3338,15 @@ template <class real>
 static void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zb, int ze, real hx2, real hy2, real hz2, int colour,
                             const real* coarse_sh, int cx, int cy, int szl, int ckmax, int zg0 = 0, real* vout = nullptr) {
     real* const vo = vout ? vout : v;
-    const int M = (sx + 1) / 2;
-    int zchunk = ctx->relax_zchunk;
-    if (corr_tile_pairs<real>(ctx, sx) == 256) {  // fp32, wide level: two pairs per lane
-        if (zchunk <= 0) {
-            const int tiles = ceil_div(M - 1, 256) * ceil_div(sy - 2, 16);
-            const int nchunks = max(1, (ctx->num_cus + tiles / 2) / tiles);
-            zchunk = max(8, ceil_div(ze - zb, nchunks));
-        }
-        const int gx2 = ceil_div(M - 1, 256), gy2 = ceil_div(sy - 2, 16), gz2 = ceil_div(ze - zb, zchunk);
-        const bool fnt2 = (size_t)sx * sy * (size_t)(ze - zb) * sizeof(real) > ((size_t)256 << 20);
-        snprintf(ctx->last_relax_kernel, sizeof ctx->last_relax_kernel, "relax3d_xs_pipe_v2_kernel<%s,2,8,2,%s,2>", sizeof(real) == 8 ? "double" : "float",
-                 fnt2 ? "true" : "false");
-        memcpy(ctx->last_corr_kernel, ctx->last_relax_kernel, sizeof ctx->last_corr_kernel);
-        const dim3 grid2((unsigned)gx2 * gy2 * gz2);
-        if ((ctx->pipe_unroll & 4) && planes_fit_descriptor<real>(sx, sy)) {
-            const int zce = zchunk + (zchunk & 1), q0 = (colour + 1 + zb) & 1;
-            const dim3 gride((unsigned)gx2 * gy2 * ceil_div(ze - zb, zce));
-#define MGX_CU2(F, U)                                                                                                                   \
-    MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, F, 2, U>), gride, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb, ze, \
-               hx2, hy2, hz2, colour, zce, gx2, gy2, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0)
-            if (fnt2) { if (q0) MGX_CU2(true, 2); else MGX_CU2(true, 1); }
-            else { if (q0) MGX_CU2(false, 2); else MGX_CU2(false, 1); }
-#undef MGX_CU2
-            return;
-        }
-        if (fnt2)
-            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, true, 2>), grid2, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, vo, f, sx,
-                               sy, zb, ze, hx2, hy2, hz2, colour, zchunk, gx2, gy2, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0);
-        else
-            MGX_LAUNCH((relax3d_xs_pipe_v2_kernel<real, 2, 8, 2, false, 2>), grid2, dim3(64, 16, 1), 0, ctx->compute, (const real*)v, vo, f, sx,
-                               sy, zb, ze, hx2, hy2, hz2, colour, zchunk, gx2, gy2, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0);
-        return;
-    }
-    if (ctx->corr_low && sizeof(real) == 8) {  // EXPERIMENT: 8-wave workgroups (tiles of 8 rows), two to a CU
-        if (zchunk <= 0) {
-            const int tiles = ceil_div(M - 1, 128) * ceil_div(sy - 2, 8);
-            const int nchunks = max(1, (2 * ctx->num_cus + tiles / 2) / tiles);
-            zchunk = max(8, ceil_div(ze - zb, nchunks));
-        }
-        const int gxl = ceil_div(M - 1, 128), gyl = ceil_div(sy - 2, 8), gzl = ceil_div(ze - zb, zchunk);
-        const bool fntl = (size_t)sx * sy * (size_t)(ze - zb) * sizeof(real) > ((size_t)256 << 20);
-        snprintf(ctx->last_relax_kernel, sizeof ctx->last_relax_kernel, "relax3d_xs_pipe_kernel<%s,2,4,2,%s,2>", sizeof(real) == 8 ? "double" : "float",
-                 fntl ? "true" : "false");
-        memcpy(ctx->last_corr_kernel, ctx->last_relax_kernel, sizeof ctx->last_corr_kernel);
-        const dim3 gridl((unsigned)gxl * gyl * gzl);
-        if (fntl)
-            MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 4, 2, true, 2>), gridl, dim3(64, 8, 1), 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb,
-                               ze, hx2, hy2, hz2, colour, zchunk, gxl, gyl, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0);
-        else
-            MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 4, 2, false, 2>), gridl, dim3(64, 8, 1), 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb,
-                               ze, hx2, hy2, hz2, colour, zchunk, gxl, gyl, ctx->relax_xcd == 1 ? 1 : 0, coarse_sh, cx, cy, szl, ckmax, zg0);
-        return;
-    }
-    if (zchunk <= 0) {  // one resident round of 16-wave workgroups as in relax3d_xs_pass_lds
-        const int tiles = ceil_div(M - 1, 128) * ceil_div(sy - 2, 16);
-        const int target = ctx->num_cus * (sizeof(real) == 4 ? 8 : 1);
-        const int nchunks = max(1, (target + tiles / 2) / tiles);
-        zchunk = max(8, ceil_div(ze - zb, nchunks));
-    }
-    const int gx = ceil_div(M - 1, 128), gy = ceil_div(sy - 2, 16), gz = ceil_div(ze - zb, zchunk);
-    const dim3 grid((unsigned)gx * gy * gz), block(64, 16, 1);
-    const int xcd = ctx->relax_xcd == 1 ? 1 : 0;
-    const bool fnt = (size_t)sx * sy * (size_t)(ze - zb) * sizeof(real) > ((size_t)256 << 20);
-    snprintf(ctx->last_relax_kernel, sizeof ctx->last_relax_kernel, "relax3d_xs_pipe_kernel<%s,2,8,2,%s,2>", sizeof(real) == 8 ? "double" : "float",
-             fnt ? "true" : "false");
-    memcpy(ctx->last_corr_kernel, ctx->last_relax_kernel, sizeof ctx->last_corr_kernel);
-    if ((ctx->pipe_unroll & 1) && (sizeof(real) == 8 || (ctx->pipe_unroll & 8)) && planes_fit_descriptor<real>(sx, sy)) {
-        // the step loop unrolled four times, register roles and row parity fixed per step: runs of an even number of planes, so
-        // that every run starts with the row parity q0 the instantiation is compiled for
-        const int zce = zchunk + (zchunk & 1), q0 = (colour + 1 + zb) & 1;
-        const dim3 gride((unsigned)gx * gy * ceil_div(ze - zb, zce));
-#define MGX_CU(F, U)                                                                                                                     \
-    MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, F, 2, U>), gride, block, 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb, ze, hx2, hy2, \
-               hz2, colour, zce, gx, gy, xcd, coarse_sh, cx, cy, szl, ckmax, zg0)
-        if (fnt) { if (q0) MGX_CU(true, 2); else MGX_CU(true, 1); }
-        else { if (q0) MGX_CU(false, 2); else MGX_CU(false, 1); }
-#undef MGX_CU
-        return;
-    }
-    if (fnt)
-        MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, true, 2>), grid, block, 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb, ze,
-                           hx2, hy2, hz2, colour, zchunk, gx, gy, xcd, coarse_sh, cx, cy, szl, ckmax, zg0);
+    PipePlan p;
+    pipe_plan<real>(ctx, PipePass::Corr, sx, sy, zb, ze, colour, p);
+    if (p.v2)
+        pipe_launch<real, true, 2, 8, 2, 2>(ctx, p, v, vo, f, sx, sy, zb, ze, hx2, hy2, hz2, colour, coarse_sh, cx, cy, szl, ckmax, zg0);
+    else if (p.WY == 4)
+        pipe_launch<real, false, 2, 4, 2, 2>(ctx, p, v, vo, f, sx, sy, zb, ze, hx2, hy2, hz2, colour, coarse_sh, cx, cy, szl, ckmax, zg0);
     else
-        MGX_LAUNCH((relax3d_xs_pipe_kernel<real, 2, 8, 2, false, 2>), grid, block, 0, ctx->compute, (const real*)v, vo, f, sx, sy, zb, ze,
-                           hx2, hy2, hz2, colour, zchunk, gx, gy, xcd, coarse_sh, cx, cy, szl, ckmax, zg0);
+        pipe_launch<real, false, 2, 8, 2, 2>(ctx, p, v, vo, f, sx, sy, zb, ze, hx2, hy2, hz2, colour, coarse_sh, cx, cy, szl, ckmax, zg0);
+    memcpy(ctx->last_corr_kernel, ctx->last_relax_kernel, sizeof ctx->last_corr_kernel);
 }
 
 // v += Interpolate(coarse_v) on the interior, then `ncycles` >= 1 red-black sweeps (N3/MultiGrid3D.cpp:638-645), x-split

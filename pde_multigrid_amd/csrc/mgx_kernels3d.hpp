@@ -45,6 +45,13 @@ struct Geo {
     __host__ __device__ __forceinline__ int pos(int x) const { return L::pos(x, H); }
 };
 
+// the kernels that address planes through buffer descriptors (the unrolled step loops: mgx_pipe_step.inc; relax_rr3d_xs_kernel) cover
+// up to four planes with one 32-bit range: levels whose planes are larger than that stay on kernels with 64-bit pointers
+template <class real>
+inline bool planes_fit_descriptor(int sx, int sy) {
+    return (unsigned long long)Geo<XSplit, real>(sx, sy).PL * sizeof(real) * 4ull < (1ull << 32);
+}
+
 // two consecutive elements of `real` as one vector value
 template <class real>
 struct Vec2T {

@@ -290,8 +290,8 @@ __global__ void __launch_bounds__(64 * TYW, 4)  // four waves per SIMD (128 VGPR
 // fp32 moves half the bytes with the same instructions and is no faster than its separate launches (513^3: 0.91 / 0.87 ms).
 bool relax_rr3d_xs_takes(const mgx_ctx* ctx, const int n[3], const int cn[3], size_t elem) {
     if (!ctx->rr_black || cn[0] < 3 || cn[1] < 3 || cn[2] < 3) return false;
-    // the kernel addresses up to four fine planes through one buffer descriptor (a 32-bit range)
-    if ((unsigned long long)(elem == 8 ? Geo<XSplit, double>(n[0], n[1]).PL : Geo<XSplit, float>(n[0], n[1]).PL) * elem * 4ull >= (1ull << 32)) return false;
+    // the kernel addresses up to four fine planes through one buffer descriptor
+    if (!(elem == 8 ? planes_fit_descriptor<double>(n[0], n[1]) : planes_fit_descriptor<float>(n[0], n[1]))) return false;
     return ctx->rr_black == 2 || (elem == 8 && n[0] >= 385 && n[1] >= 129 && n[2] >= 65);
 }
 
@@ -309,15 +309,7 @@ bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], 
     if (pzc <= 0) {
         // all workgroups take the same time and one fits a CU: the fewest runs that fill whole rounds to 90 %, runs of at least
         // 8 coarse planes (the two planes a run relaxes before its first residual)
-        int nchunks = 1;
-        double best = 0;
-        for (int c = 1; c <= 16 && planes / c >= 8; c++) {
-            const long long wgs = (long long)tiles * c, cap = (long long)ctx->num_cus * wg_per_cu;
-            const double eff = (double)wgs / (double)(((wgs + cap - 1) / cap) * cap) * (double)planes / (double)(planes + 2 * c);
-            if (eff > best + 1e-9) { best = eff; nchunks = c; }
-            if (eff >= 0.9) break;
-        }
-        pzc = ceil_div(planes, nchunks);
+        pzc = ceil_div(planes, runs_filling_rounds(tiles, planes, (long long)ctx->num_cus * wg_per_cu, 16, 8, 2));
     }
     dim3 g(tiles * ceil_div(planes, pzc), 1, 1);
     real qx = hx2, qy = hy2, qz = hz2;
