@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "mgx.h"
 
@@ -123,6 +124,14 @@ inline int runs_filling_rounds(long long tiles, int planes, long long slots, int
         if (eff >= 0.9) break;
     }
     return runs;
+}
+
+// A runtime value as a template argument: f(std::integral_constant<int, V>()) for the V of Vs equal to v, no call if none is.  The
+// caller keeps instantiations that do not exist out with `if constexpr`.
+template <int V0, int... Vs, class F>
+__attribute__((visibility("hidden"))) inline void with_value(int v, F&& f) {
+    if (v == V0) f(std::integral_constant<int, V0>());
+    else if constexpr (sizeof...(Vs) > 0) with_value<Vs...>(v, f);
 }
 
 template <class real>

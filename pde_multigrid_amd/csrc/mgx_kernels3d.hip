@@ -2778,21 +2778,11 @@ int residual3d(mgx_ctx* ctx, const real* v, const real* f, real* r, const int n[
     int st = check_n3(n, "residual3d");
     if (st) return st;
     MGX_REQUIRE(mode == MGX_RESIDUAL_REF_COMPAT || mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "residual3d: bad mode %d", mode);
-    real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];  // N3/MultiGrid3D.cpp:687-689
-    const bool rcp = ctx->rr_rcp && exact_reciprocal(hx2) && exact_reciprocal(hy2) && exact_reciprocal(hz2);  // residual3d_point
-    if (rcp) {
-        hx2 = (real)1 / hx2;
-        hy2 = (real)1 / hy2;
-        hz2 = (real)1 / hz2;
-    }
-#define MGX_RES(M) \
-    MGX_LAUNCH((residual3d_kernel<real, L, M>), grd(n[0], n[1], n[2]), blk(), 0, ctx->compute, v, f, r, n[0], n[1], n[2], hx2, hy2, hz2)
-    if (mode == MGX_RESIDUAL_REF_COMPAT) {
-        if (rcp) MGX_RES(2); else MGX_RES(0);
-    } else {
-        if (rcp) MGX_RES(3); else MGX_RES(1);
-    }
-#undef MGX_RES
+    const ResidualScale<real> s = residual_scale<real>(ctx, h, mode);
+    with_value<0, 1, 2, 3>(s.mode, [&](auto m) __attribute__((always_inline)) {
+        MGX_LAUNCH((residual3d_kernel<real, L, decltype(m)::value>), grd(n[0], n[1], n[2]), blk(), 0, ctx->compute, v, f, r, n[0], n[1],
+                   n[2], s.qx, s.qy, s.qz);
+    });
     MGX_LAUNCH_CHECK();
     return MGX_OK;
 }
@@ -2896,132 +2886,155 @@ int set3d_slab(mgx_ctx* ctx, real* g, int sx, int sy, int zbeg, int zend, real v
     return MGX_OK;
 }
 
-// streaming x-split residual+restrict over the global coarse planes [pzbeg, pzend): zero them (boundary coarse
-// points stay 0), then one launch of residual_restrict3d_xs_kernel
-template <class real>
-static int residual_restrict3d_xs_launch(mgx_ctx* ctx, const real* v, const real* f, const int n[3], real hx2, real hy2,
-                                         real hz2, int mode, real* coarse_f, const int cn[3], int fzoff, int czoff, int pzbeg,
-                                         int pzend, bool rim_is_zero = false) {
-    const Geo<XSplit, real> gc(cn[0], cn[1]);
-    // the kernels write every interior coarse point of the planes and nothing else: boundary points and pad entries
-    // are zeroed here unless the caller vouches that they already are (they stay zero from one cycle to the next)
-    if (!rim_is_zero)
-        MGX_TRY_RET(fill_zero(ctx, coarse_f + gc.PL * (size_t)(pzbeg - czoff), gc.PL * (size_t)(pzend - pzbeg) * sizeof(real)));
-    if (cn[0] < 3 || cn[1] < 3) return MGX_OK;
-    // power-of-two spacings: multiply by the exact reciprocals instead of dividing (residual3d_point, MODE | 2)
-    const bool rcp = ctx->rr_rcp && exact_reciprocal(hx2) && exact_reciprocal(hy2) && exact_reciprocal(hz2);
-    if (rcp) {
-        hx2 = (real)1 / hx2;
-        hy2 = (real)1 / hy2;
-        hz2 = (real)1 / hz2;
-    }
+// the checks every entry of the residual+restrict family begins with (each entry checks its residual mode itself)
+static int check_rr_args(mgx_ctx* ctx, bool nonnull, const int n[3], const int cn[3], const char* what) {
+    MGX_REQUIRE(nonnull, MGX_ERR_INVALID, "%s: NULL argument", what);
+    MGX_USE(ctx);
+    MGX_TRY_RET(check_n3(n, what));
+    return check_coarse3(n, cn, what);
+}
+
+// ---- residual+restrict: rr_plan decides how a launch over a run of coarse planes goes; rr_launch launches the window, shuffle
+// and pipelined kernels, relax_rr3d_xs_launch (mgx_relax_rr3d.hip) the fused black one
+
+// The launch over `planes` coarse planes of a level of n fine points (cn coarse): the fused black kernel, the window kernel (the
+// natural layout, or residual_restrict3d.stream = 0) or the x-split kernel of residual_restrict3d.stream.  Returns false when
+// there is nothing to launch: the x-split kernels on a level of fewer than 3 coarse points across x or y.
+bool rr_plan(const mgx_ctx* ctx, bool xsplit, bool black, const int n[3], const int cn[3], int planes, RRPlan& p) {
+    p = RRPlan();
+    // runs of 8 coarse planes (residual_restrict3d.pzchunk), halved while the launch has fewer than four workgroups per CU
+    const auto halved_runs = [&](long long tiles) {
+        int pzc = ctx->rr_pzchunk > 0 ? ctx->rr_pzchunk : 8;
+        while (pzc > 1 && tiles * ceil_div(planes, pzc) < 4LL * ctx->num_cus) pzc >>= 1;
+        return pzc;
+    };
     // rr_stream 3 (default): the pipelined kernel on levels of at least 129 x 65 rows and 8 coarse planes (with two rows per
     // wave it wins from 129^3 on: 18 against 25 us there, 75 against 97 us at 257^3; at 65^3 the streaming kernel's 6 us stand)
-    const bool big = n[0] >= 129 && n[1] >= 65 && pzend - pzbeg >= 8;
-    if (ctx->rr_stream == 2 || (ctx->rr_stream == 3 && big)) {  // residual_restrict3d_xs_pipe_kernel
+    const bool big = n[0] >= 129 && n[1] >= 65 && planes >= 8;
+    p.kernel = black ? RRKernel::Black : !xsplit || !ctx->rr_stream ? RRKernel::Window
+             : ctx->rr_stream == 2 || (ctx->rr_stream == 3 && big) ? RRKernel::Pipe : RRKernel::Shuffle;
+    if (p.kernel == RRKernel::Window) {  // tiles of 32 x 8 coarse points (one extra fine plane per run)
+        p.gx = ceil_div(cn[0], 32), p.gy = ceil_div(cn[1], 8);
+        p.pzchunk = halved_runs((long long)p.gx * p.gy);
+        p.grid = dim3(p.gx, p.gy, ceil_div(planes, p.pzchunk));
+        p.block = blk();
+        return true;
+    }
+    if (cn[0] < 3 || cn[1] < 3) return false;
+    // XCD-aware tile order (residual_restrict3d.xcd): 1 = the pipelined and the fused kernel, 2 = the shuffle kernel too
+    if (p.kernel == RRKernel::Black) {
+        p.T = ctx->rr_black_waves == 12 ? 12 : ctx->rr_black_waves == 8 ? 8 : 16;
+        p.gx = ceil_div(cn[0] - 2, 61);
+        p.gy = ceil_div(cn[1] - 2, p.T - 2);
+        // all workgroups take the same time and one fits a CU (two of 8 waves): the fewest runs that fill whole rounds to 90 %, runs
+        // of at least 8 coarse planes (the two planes a run relaxes before its first residual)
+        const int tiles = p.gx * p.gy;
+        p.pzchunk = ctx->rr_pzchunk > 0 ? ctx->rr_pzchunk
+                                        : ceil_div(planes, runs_filling_rounds(tiles, planes, (long long)ctx->num_cus * (p.T == 8 ? 2 : 1), 16, 8, 2));
+        p.xcd = ctx->rr_xcd >= 1;
+    } else if (p.kernel == RRKernel::Pipe) {
         // fine rows per wave: 2 (sixteen waves of <= 128 VGPRs per workgroup; 513^3: 474-486 us against 562-569 us with 4
         // rows = eight waves of 240 VGPRs; 1025^3: 3.49 against 3.76 ms -- once the runs fill whole rounds, see below)
-        const int own = ctx->rr_rows ? ctx->rr_rows : 2;
+        p.OWN = ctx->rr_rows ? ctx->rr_rows : 2;
         // two rows per wave: sixteen waves per workgroup, eight on levels of at most 257 rows (more tiles, so longer runs:
         // 69 against 76 us at 257^3)
-        const int T = own == 2 ? ((ctx->rr_stream == 3 ? n[1] <= 257 : ctx->rr_tyw == 8) ? 8 : 16)
-                               : (ctx->rr_stream == 3 ? 8 : (ctx->rr_tyw == 8 ? 8 : (ctx->rr_tyw == 2 ? 2 : 4)));
-        const int gx = ceil_div(cn[0] - 2, 62), gy = ceil_div(cn[1] - 2, (own / 2) * (T - 1));  // the last wave is a halo wave
-        int pzc = ctx->rr_pzchunk;
-        if (pzc <= 0) {
-            // whole resident rounds of workgroups, because all workgroups take the same time: three rounds for the 8-wave
-            // kernels; ONE for the 16-wave kernel (one workgroup per CU: 513^3 = 85 tiles x 3 runs of 85 coarse planes -- the
-            // three planes a run loads before its first result then weigh 2 % instead of 5 %: 512 against 540 us)
-            const int tiles = gx * gy;
-            // T == 16: the fewest runs that fill whole rounds to 90 % (1025^3: 315 tiles x 3 = 945 of 1024 slots)
-            const int nchunks = T == 16 ? runs_filling_rounds(tiles, pzend - pzbeg, ctx->num_cus, 12, 0, 0)
-                                        : max(1, (3 * ctx->num_cus + tiles / 2) / tiles);
-            pzc = max(4, ceil_div(pzend - pzbeg, nchunks));
-        }
-        dim3 g(gx * gy * ceil_div(pzend - pzbeg, pzc), 1, 1);
-#define MGX_RRP(M, W, OW)                                                                                                \
-    MGX_LAUNCH((residual_restrict3d_xs_pipe_kernel<real, M, W, OW>), g, dim3(64, W, 1), 0, ctx->compute, v, f,    \
-                       n[0], n[1], n[2], hx2, hy2, hz2, coarse_f, cn[0], cn[1], cn[2], pzc, fzoff, czoff, pzbeg, pzend,   \
-                       gx, gy, ctx->rr_xcd >= 1)
-#define MGX_RRP_W(M)                                                                                                     \
-    do {                                                                                                                 \
-        if (T == 16) MGX_RRP(M, 16, 2); else if (T == 8 && own == 2) MGX_RRP(M, 8, 2); else if (T == 8) MGX_RRP(M, 8, 4); else if (T == 2) MGX_RRP(M, 2, 4); else MGX_RRP(M, 4, 4); \
-    } while (0)
-        if (mode == MGX_RESIDUAL_REF_COMPAT) {
-            if (rcp) MGX_RRP_W(2); else MGX_RRP_W(0);
-        } else {
-            if (rcp) MGX_RRP_W(3); else MGX_RRP_W(1);
-        }
-#undef MGX_RRP_W
-#undef MGX_RRP
-        return MGX_OK;
-    }
-    // one coarse row per lane on the launch-bound levels (<= 65^3: 3-4 us faster, more waves), two above
-    const int CRr = ctx->rr_cr == 1 || (ctx->rr_cr == 0 && n[0] <= 65) ? 1 : 2;
-    const int TYWr = ctx->rr_tyw == 8 ? 8 : (ctx->rr_tyw == 2 ? 2 : 4);
-    const int gx = ceil_div(cn[0], 63), gy = ceil_div(cn[1] - 2, CRr * TYWr);
-    int pzchunk = ctx->rr_pzchunk > 0 ? ctx->rr_pzchunk : 8;
-    while (pzchunk > 1 && (long long)gx * gy * ceil_div(pzend - pzbeg, pzchunk) < 4LL * ctx->num_cus) pzchunk >>= 1;
-    dim3 g(gx * gy * ceil_div(pzend - pzbeg, pzchunk), 1, 1);
-#define MGX_RR(M, C, W)                                                                                                  \
-    MGX_LAUNCH((residual_restrict3d_xs_kernel<real, M, C, W>), g, dim3(64, W, 1), 0, ctx->compute, v, f, n[0], n[1], \
-                       n[2], hx2, hy2, hz2, coarse_f, cn[0], cn[1], cn[2], pzchunk, fzoff, czoff, pzbeg, pzend, gx, gy,      \
-                       ctx->rr_xcd >= 2)
-#define MGX_RR_W(M, C)                             \
-    do {                                           \
-        if (TYWr == 8) MGX_RR(M, C, 8);            \
-        else if (TYWr == 2) MGX_RR(M, C, 2);       \
-        else MGX_RR(M, C, 4);                      \
-    } while (0)
-    if (mode == MGX_RESIDUAL_REF_COMPAT) {
-        if (rcp) { if (CRr == 1) MGX_RR_W(2, 1); else MGX_RR_W(2, 2); }
-        else { if (CRr == 1) MGX_RR_W(0, 1); else MGX_RR_W(0, 2); }
+        const bool by_level = ctx->rr_stream == 3;
+        p.T = p.OWN == 2 ? ((by_level ? n[1] <= 257 : ctx->rr_tyw == 8) ? 8 : 16) : (by_level ? 8 : ctx->rr_tyw);
+        p.gx = ceil_div(cn[0] - 2, 62);
+        p.gy = ceil_div(cn[1] - 2, (p.OWN / 2) * (p.T - 1));  // the last wave is a halo wave
+        const int tiles = p.gx * p.gy;
+        // whole resident rounds of workgroups, because all workgroups take the same time: three rounds for the 8-wave
+        // kernels; ONE for the 16-wave kernel (one workgroup per CU: 513^3 = 85 tiles x 3 runs of 85 coarse planes -- the
+        // three planes a run loads before its first result then weigh 2 % instead of 5 %: 512 against 540 us)
+        // T == 16: the fewest runs that fill whole rounds to 90 % (1025^3: 315 tiles x 3 = 945 of 1024 slots)
+        const int runs = p.T == 16 ? runs_filling_rounds(tiles, planes, ctx->num_cus, 12, 0, 0) : max(1, (3 * ctx->num_cus + tiles / 2) / tiles);
+        p.pzchunk = ctx->rr_pzchunk > 0 ? ctx->rr_pzchunk : max(4, ceil_div(planes, runs));
+        p.xcd = ctx->rr_xcd >= 1;
     } else {
-        if (rcp) { if (CRr == 1) MGX_RR_W(3, 1); else MGX_RR_W(3, 2); }
-        else { if (CRr == 1) MGX_RR_W(1, 1); else MGX_RR_W(1, 2); }
+        // one coarse row per lane on the launch-bound levels (<= 65^3: 3-4 us faster, more waves), two above
+        p.CR = ctx->rr_cr == 1 || (ctx->rr_cr == 0 && n[0] <= 65) ? 1 : 2;
+        p.T = ctx->rr_tyw;
+        p.gx = ceil_div(cn[0], 63);
+        p.gy = ceil_div(cn[1] - 2, p.CR * p.T);
+        p.pzchunk = halved_runs((long long)p.gx * p.gy);
+        p.xcd = ctx->rr_xcd >= 2;
     }
-#undef MGX_RR_W
-#undef MGX_RR
+    p.grid = dim3(p.gx * p.gy * ceil_div(planes, p.pzchunk), 1, 1);
+    p.block = dim3(64, p.T, 1);
+    return true;
+}
+
+// The one launch of the window, shuffle and pipelined kernels: the instantiation for the plan's shape and the MODE of s (the
+// window kernel ignores rcp: MODE 0 / 1 with the squared spacings).  The coarse planes [pzbeg, pzend) are global; v / f start
+// at global fine plane fzoff, coarse at global coarse plane czoff.  Returns false when no instantiation has the plan's shape.
+template <class real, class L>
+static bool rr_launch(mgx_ctx* ctx, const RRPlan& p, const ResidualScale<real>& s, const real* v, const real* f, const int n[3],
+                      real* coarse, const int cn[3], int fzoff, int czoff, int pzbeg, int pzend) {
+    const bool window = p.kernel == RRKernel::Window;
+    bool done = false;
+    with_value<0, 1, 2, 3>(window ? s.mode & 1 : s.mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (window) {
+            if constexpr (M < 2) {
+                MGX_LAUNCH((residual_restrict3d_kernel<real, L, M, 32, 8>), p.grid, p.block, 0, ctx->compute, v, f, n[0], n[1], n[2], s.hx2,
+                           s.hy2, s.hz2, coarse, cn[0], cn[1], cn[2], p.pzchunk, fzoff, czoff, pzbeg, pzend);
+                done = true;
+            }
+        } else if (p.kernel == RRKernel::Shuffle) {
+            with_value<1, 2>(p.CR, [&](auto cr) {
+                with_value<8, 2, 4>(p.T, [&](auto tyw) {
+                    MGX_LAUNCH((residual_restrict3d_xs_kernel<real, M, decltype(cr)::value, decltype(tyw)::value>), p.grid, p.block, 0,
+                               ctx->compute, v, f, n[0], n[1], n[2], s.qx, s.qy, s.qz, coarse, cn[0], cn[1], cn[2], p.pzchunk, fzoff,
+                               czoff, pzbeg, pzend, p.gx, p.gy, p.xcd);
+                    done = true;
+                });
+            });
+        } else {  // the pipelined shapes: 16 waves of 2 rows, 8 of 2 or 4, 2 and 4 waves of 4 rows
+            with_value<16, 8, 2, 4>(p.T, [&](auto tyw) {
+                with_value<2, 4>(p.OWN, [&](auto own) {
+                    constexpr int W = decltype(tyw)::value, OW = decltype(own)::value;
+                    if constexpr (W == 8 || (W == 16) == (OW == 2)) {
+                        MGX_LAUNCH((residual_restrict3d_xs_pipe_kernel<real, M, W, OW>), p.grid, p.block, 0, ctx->compute, v, f, n[0],
+                                   n[1], n[2], s.qx, s.qy, s.qz, coarse, cn[0], cn[1], cn[2], p.pzchunk, fzoff, czoff, pzbeg, pzend, p.gx,
+                                   p.gy, p.xcd);
+                        done = true;
+                    }
+                });
+            });
+        }
+    });
+    return done;
+}
+
+// Residual+restrict into the GLOBAL coarse planes [pzbeg, pzend) (the whole grid: fzoff = czoff = pzbeg = 0, pzend = cn[2]).
+// n / cn global sizes, v / f start at global fine plane fzoff, coarse_f at global coarse plane czoff.
+template <class real, class L>
+static int residual_restrict3d_range(mgx_ctx* ctx, const real* v, const real* f, const int n[3], int fzoff, const real h[3], int mode,
+                                     real* coarse_f, const int cn[3], int czoff, int pzbeg, int pzend, bool rim_is_zero) {
+    if (pzbeg == pzend) return MGX_OK;
+    RRPlan p;
+    const bool launch = rr_plan(ctx, L::xsplit, false, n, cn, pzend - pzbeg, p);
+    // the x-split kernels write every interior coarse point of the planes and nothing else: boundary points and pad entries
+    // are zeroed here unless the caller vouches that they already are (they stay zero from one cycle to the next)
+    const Geo<XSplit, real> gc(cn[0], cn[1]);
+    if (p.kernel != RRKernel::Window && !rim_is_zero)
+        MGX_TRY_RET(fill_zero(ctx, coarse_f + gc.PL * (size_t)(pzbeg - czoff), gc.PL * (size_t)(pzend - pzbeg) * sizeof(real)));
+    MGX_REQUIRE((!launch || rr_launch<real, L>(ctx, p, residual_scale<real>(ctx, h, mode), v, f, n, coarse_f, cn, fzoff, czoff, pzbeg, pzend)),
+                MGX_ERR_INVALID, "residual_restrict: no kernel of the planned shape (T %d, CR %d, OWN %d)", p.T, p.CR, p.OWN);
+    MGX_LAUNCH_CHECK();
     return MGX_OK;
 }
 
 template <class real, class L>
 int residual_restrict3d(mgx_ctx* ctx, const real* v, const real* f, const int n[3], const real h[3], int mode,
                         real* coarse_f, const int cn[3], bool rim_is_zero = false) {
-    MGX_REQUIRE(ctx && v && f && h && coarse_f, MGX_ERR_INVALID, "residual_restrict3d: NULL argument");
-    MGX_USE(ctx);
-    int st = check_n3(n, "residual_restrict3d");
-    if (st) return st;
-    st = check_coarse3(n, cn, "residual_restrict3d");
-    if (st) return st;
+    MGX_TRY_RET(check_rr_args(ctx, ctx && v && f && h && coarse_f, n, cn, "residual_restrict3d"));
     MGX_REQUIRE(mode == MGX_RESIDUAL_REF_COMPAT || mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID,
                 "residual_restrict3d: bad mode %d", mode);
-    const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
-    if (L::xsplit && ctx->rr_stream) {
-        st = residual_restrict3d_xs_launch<real>(ctx, v, f, n, hx2, hy2, hz2, mode, coarse_f, cn, 0, 0, 0, cn[2], rim_is_zero);
-        if (st) return st;
-        MGX_LAUNCH_CHECK();
-        return MGX_OK;
-    }
-    constexpr int CTX = 32, CTY = 8;
-    const int tiles = ceil_div(cn[0], CTX) * ceil_div(cn[1], CTY);
-    int pzchunk = ctx->rr_pzchunk > 0 ? ctx->rr_pzchunk : 8;  // coarse planes per block (1 extra fine plane per chunk)
-    while (pzchunk > 1 && (long long)tiles * ceil_div(cn[2], pzchunk) < 4LL * ctx->num_cus) pzchunk >>= 1;
-    dim3 g(ceil_div(cn[0], CTX), ceil_div(cn[1], CTY), ceil_div(cn[2], pzchunk));
-    if (mode == MGX_RESIDUAL_REF_COMPAT)
-        MGX_LAUNCH((residual_restrict3d_kernel<real, L, 0, CTX, CTY>), g, blk(), 0, ctx->compute, v, f, n[0], n[1],
-                           n[2], hx2, hy2, hz2, coarse_f, cn[0], cn[1], cn[2], pzchunk, 0, 0, 0, cn[2]);
-    else
-        MGX_LAUNCH((residual_restrict3d_kernel<real, L, 1, CTX, CTY>), g, blk(), 0, ctx->compute, v, f, n[0], n[1],
-                           n[2], hx2, hy2, hz2, coarse_f, cn[0], cn[1], cn[2], pzchunk, 0, 0, 0, cn[2]);
-    MGX_LAUNCH_CHECK();
-    return MGX_OK;
+    return residual_restrict3d_range<real, L>(ctx, v, f, n, 0, h, mode, coarse_f, cn, 0, 0, cn[2], rim_is_zero);
 }
 
 bool relax_rr3d_xs_takes(const mgx_ctx* ctx, const int n[3], const int cn[3], size_t elem);  // mgx_relax_rr3d.hip
-template <class real>
-bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], real hx2, real hy2, real hz2, int mode, bool rcp,
-                          real* coarse_f, const int cn[3], int fzoff, int czoff, int pzbeg, int pzend);
 
 bool relax_block3_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int part);  // mgx_block3d.hip
 template <class real>
@@ -3037,22 +3050,15 @@ void relax3d_xs_block3_launch<float>(mgx_ctx*, const float*, float*, const float
 template <class real>
 int relax_rr3d_slab(mgx_ctx* ctx, real* v, const real* f, const int n[3], int fzoff, const real h[3], int mode, real* coarse_f,
                     const int cn[3], int czoff, int pzbeg, int pzend) {
-    MGX_REQUIRE(ctx && v && f && h && coarse_f, MGX_ERR_INVALID, "relax_rr_slab: NULL argument");
-    MGX_USE(ctx);
-    int st = check_n3(n, "relax_rr_slab");
-    if (st) return st;
-    st = check_coarse3(n, cn, "relax_rr_slab");
-    if (st) return st;
+    MGX_TRY_RET(check_rr_args(ctx, ctx && v && f && h && coarse_f, n, cn, "relax_rr_slab"));
     MGX_REQUIRE(mode == MGX_RESIDUAL_REF_COMPAT || mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "relax_rr_slab: bad mode %d", mode);
     MGX_REQUIRE(pzbeg >= 1 && pzend <= cn[2] - 1 && pzbeg < pzend && czoff >= 0 && czoff <= pzbeg && fzoff >= 0 && (fzoff & 1) == 0 &&
                     fzoff <= (2 * pzbeg - 3 > 0 ? 2 * pzbeg - 3 : 0),
                 MGX_ERR_INVALID, "relax_rr_slab: coarse planes [%d, %d) with offsets %d / %d", pzbeg, pzend, fzoff, czoff);
     MGX_REQUIRE(relax_rr3d_xs_takes(ctx, n, cn, sizeof(real)), MGX_ERR_INVALID, "relax_rr_slab: the level is not taken (ask relax_rr_takes)");
-    const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
     const Geo<XSplit, real> gc(cn[0], cn[1]);
     MGX_TRY_RET(fill_zero(ctx, coarse_f + gc.PL * (size_t)(pzbeg - czoff), gc.PL * (size_t)(pzend - pzbeg) * sizeof(real)));
-    const bool rcp = ctx->rr_rcp && exact_reciprocal(hx2) && exact_reciprocal(hy2) && exact_reciprocal(hz2);
-    MGX_REQUIRE(relax_rr3d_xs_launch<real>(ctx, v, f, n, hx2, hy2, hz2, mode, rcp, coarse_f, cn, fzoff, czoff, pzbeg, pzend), MGX_ERR_INVALID,
+    MGX_REQUIRE(relax_rr3d_xs_launch<real>(ctx, v, f, n, h, mode, coarse_f, cn, fzoff, czoff, pzbeg, pzend), MGX_ERR_INVALID,
                 "relax_rr_slab: launch refused");
     MGX_LAUNCH_CHECK();
     return MGX_OK;
@@ -3064,20 +3070,14 @@ int relax_rr3d_slab(mgx_ctx* ctx, real* v, const real* f, const int n[3], int fz
 template <class real>
 int smooth_residual_restrict3d_xs(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int ncycles, int from_zero,
                                   int v_rim_is_zero, int mode, real* coarse_f, const int cn[3], int coarse_rim_is_zero) {
-    MGX_REQUIRE(ctx && v && f && h && coarse_f, MGX_ERR_INVALID, "smooth_residual_restrict3d: NULL argument");
-    MGX_USE(ctx);
-    int st = check_n3(n, "smooth_residual_restrict3d");
-    if (st) return st;
-    st = check_coarse3(n, cn, "smooth_residual_restrict3d");
-    if (st) return st;
+    MGX_TRY_RET(check_rr_args(ctx, ctx && v && f && h && coarse_f, n, cn, "smooth_residual_restrict3d"));
     MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "smooth_residual_restrict3d: ncycles = %d < 0", ncycles);
     MGX_REQUIRE(mode == MGX_RESIDUAL_REF_COMPAT || mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID,
                 "smooth_residual_restrict3d: bad mode %d", mode);
     ctx->last_rr_kernel[0] = 0;
     ctx->last_block3_kernel[0] = 0;
     if (ncycles < 1 || !relax_rr3d_xs_takes(ctx, n, cn, sizeof(real))) {
-        st = from_zero ? relax3d_from_zero<real, XSplit>(ctx, v, f, n, h, ncycles, v_rim_is_zero) : relax3d<real, XSplit>(ctx, v, f, n, h, ncycles);
-        if (st) return st;
+        MGX_TRY_RET((from_zero ? relax3d_from_zero<real, XSplit>(ctx, v, f, n, h, ncycles, v_rim_is_zero) : relax3d<real, XSplit>(ctx, v, f, n, h, ncycles)));
         return residual_restrict3d<real, XSplit>(ctx, v, f, n, h, mode, coarse_f, cn, coarse_rim_is_zero != 0);
     }
     const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];  // :498-500
@@ -3101,8 +3101,7 @@ int smooth_residual_restrict3d_xs(mgx_ctx* ctx, real* v, const real* f, const in
     for (; s < 2 * ncycles - 1 - (b3 ? 3 : 0); s++) relax3d_xs_pass<real>(ctx, v, f, n[0], n[1], 1, n[2] - 1, hx2, hy2, hz2, s & 1);
     if (b3) relax3d_xs_block3_launch<real>(ctx, v, v, f, n, hx2, hy2, hz2, 0, false);
     if (!coarse_rim_is_zero) MGX_TRY_RET(fill_zero(ctx, coarse_f, Geo<XSplit, real>(cn[0], cn[1]).PL * (size_t)cn[2] * sizeof(real)));
-    const bool rcp = ctx->rr_rcp && exact_reciprocal(hx2) && exact_reciprocal(hy2) && exact_reciprocal(hz2);
-    MGX_REQUIRE(relax_rr3d_xs_launch<real>(ctx, v, f, n, hx2, hy2, hz2, mode, rcp, coarse_f, cn, 0, 0, 1, cn[2] - 1), MGX_ERR_INVALID,
+    MGX_REQUIRE(relax_rr3d_xs_launch<real>(ctx, v, f, n, h, mode, coarse_f, cn, 0, 0, 1, cn[2] - 1), MGX_ERR_INVALID,
                 "smooth_residual_restrict3d: the fused launch refused a level it had accepted");
     MGX_LAUNCH_CHECK();
     return MGX_OK;
@@ -3197,36 +3196,11 @@ int relax3d_zero_colour_slab(mgx_ctx* ctx, real* v, const real* f, int sx, int s
 template <class real>
 int residual_restrict3d_slab(mgx_ctx* ctx, const real* v, const real* f, const int n[3], int fzoff, const real h[3],
                              int mode, real* coarse_f, const int cn[3], int czoff, int pzbeg, int pzend) {
-    MGX_REQUIRE(ctx && v && f && h && coarse_f, MGX_ERR_INVALID, "residual_restrict_slab: NULL argument");
-    MGX_USE(ctx);
-    int st = check_n3(n, "residual_restrict_slab");
-    if (st) return st;
-    st = check_coarse3(n, cn, "residual_restrict_slab");
-    if (st) return st;
+    MGX_TRY_RET(check_rr_args(ctx, ctx && v && f && h && coarse_f, n, cn, "residual_restrict_slab"));
     MGX_REQUIRE(mode == MGX_RESIDUAL_REF_COMPAT || mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "bad residual mode %d", mode);
     MGX_REQUIRE(pzbeg >= 0 && pzend <= cn[2] && pzbeg <= pzend && fzoff >= 0 && czoff >= 0 && czoff <= pzbeg, MGX_ERR_INVALID,
                 "residual_restrict_slab: bad plane range");
-    if (pzbeg == pzend) return MGX_OK;
-    const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
-    if (ctx->rr_stream) {
-        st = residual_restrict3d_xs_launch<real>(ctx, v, f, n, hx2, hy2, hz2, mode, coarse_f, cn, fzoff, czoff, pzbeg, pzend);
-        if (st) return st;
-        MGX_LAUNCH_CHECK();
-        return MGX_OK;
-    }
-    constexpr int CTX = 32, CTY = 8;
-    const int tiles = ceil_div(cn[0], CTX) * ceil_div(cn[1], CTY);
-    int pzchunk = ctx->rr_pzchunk > 0 ? ctx->rr_pzchunk : 8;
-    while (pzchunk > 1 && (long long)tiles * ceil_div(pzend - pzbeg, pzchunk) < 4LL * ctx->num_cus) pzchunk >>= 1;
-    dim3 g(ceil_div(cn[0], CTX), ceil_div(cn[1], CTY), ceil_div(pzend - pzbeg, pzchunk));
-    if (mode == MGX_RESIDUAL_REF_COMPAT)
-        MGX_LAUNCH((residual_restrict3d_kernel<real, XSplit, 0, CTX, CTY>), g, blk(), 0, ctx->compute, v, f, n[0],
-                           n[1], n[2], hx2, hy2, hz2, coarse_f, cn[0], cn[1], cn[2], pzchunk, fzoff, czoff, pzbeg, pzend);
-    else
-        MGX_LAUNCH((residual_restrict3d_kernel<real, XSplit, 1, CTX, CTY>), g, blk(), 0, ctx->compute, v, f, n[0],
-                           n[1], n[2], hx2, hy2, hz2, coarse_f, cn[0], cn[1], cn[2], pzchunk, fzoff, czoff, pzbeg, pzend);
-    MGX_LAUNCH_CHECK();
-    return MGX_OK;
+    return residual_restrict3d_range<real, XSplit>(ctx, v, f, n, fzoff, h, mode, coarse_f, cn, czoff, pzbeg, pzend, false);
 }
 
 // sum over the (x, y)-interior points of the local planes [zbeg, zend) of the squared residual -> *dev_out (a device
@@ -3243,26 +3217,15 @@ int residual_sumsq3d_slab(mgx_ctx* ctx, const real* v, const real* f, int sx, in
         MGX_HIP(hipMemsetAsync(dev_out, 0, sizeof(double), ctx->compute));
         return MGX_OK;
     }
-    real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
-    const bool rcp = ctx->rr_rcp && exact_reciprocal(hx2) && exact_reciprocal(hy2) && exact_reciprocal(hz2);  // residual3d_point
-    if (rcp) {
-        hx2 = (real)1 / hx2;
-        hy2 = (real)1 / hy2;
-        hz2 = (real)1 / hz2;
-    }
+    const ResidualScale<real> s = residual_scale<real>(ctx, h, mode);
     const size_t rows = (size_t)(sy - 2) * (size_t)(zend - zbeg);
     void* ws = nullptr;
     MGX_TRY_RET(workspace(ctx, rows * sizeof(double), &ws));
     const dim3 g(sy - 2, zend - zbeg);
-#define MGX_RES(M)                                                                                                            \
-    MGX_LAUNCH((residual_sumsq3d_kernel<real, XSplit, M>), g, dim3(256), 0, ctx->compute, v, f, sx, sy, zbeg, hx2, hy2, \
-                       hz2, (double*)ws)
-    if (mode == MGX_RESIDUAL_REF_COMPAT) {
-        if (rcp) MGX_RES(2); else MGX_RES(0);
-    } else {
-        if (rcp) MGX_RES(3); else MGX_RES(1);
-    }
-#undef MGX_RES
+    with_value<0, 1, 2, 3>(s.mode, [&](auto m) __attribute__((always_inline)) {
+        MGX_LAUNCH((residual_sumsq3d_kernel<real, XSplit, decltype(m)::value>), g, dim3(256), 0, ctx->compute, v, f, sx, sy, zbeg, s.qx,
+                   s.qy, s.qz, (double*)ws);
+    });
     MGX_LAUNCH(residual_sumsq_final_kernel, dim3(1), dim3(1024), 0, ctx->compute, (const double*)ws, rows, dev_out);
     MGX_LAUNCH_CHECK();
     return MGX_OK;
@@ -3533,9 +3496,8 @@ int cycle3d_tail(mgx_ctx* ctx, int nlev, real* const* v, real* const* f, const i
     const size_t lds = elems * sizeof(real);
     if (lds > 64 * 1024)
         MGX_HIP(hipFuncSetAttribute((const void*)cycle3d_tail_kernel<real, L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    bool rcp = ctx->rr_rcp != 0;
-    for (int l = 0; l < nlev && rcp; l++)
-        rcp = exact_reciprocal(T.hx[l] * T.hx[l]) && exact_reciprocal(T.hy[l] * T.hy[l]) && exact_reciprocal(T.hz[l] * T.hz[l]);
+    bool rcp = ctx->rr_rcp != 0;  // residual_scale's rule, on every level
+    for (int l = 0; l < nlev && rcp; l++) rcp = exact_reciprocals(h + 3 * l);
     MGX_LAUNCH((cycle3d_tail_kernel<real, L>), dim3(1), dim3(1024), lds, ctx->compute, T, v1, v2, mode | (rcp ? 2 : 0), top_zero);
     MGX_LAUNCH_CHECK();
     return MGX_OK;

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mgx.h"
+#include "mgx_internal.hpp"
 
 namespace mgx {
 
@@ -51,6 +52,24 @@ template <class real>
 inline bool planes_fit_descriptor(int sx, int sy) {
     return (unsigned long long)Geo<XSplit, real>(sx, sy).PL * sizeof(real) * 4ull < (1ull << 32);
 }
+
+// How a residual+restrict launch runs (rr_plan in mgx_kernels3d.hip decides it).  The kernels: the LDS rolling window
+// (residual_restrict3d_kernel), the streaming shuffle kernel (residual_restrict3d_xs_kernel), the pipelined kernel
+// (residual_restrict3d_xs_pipe_kernel) and the fused black pass + residual + restrict (relax_rr3d_xs_kernel, mgx_relax_rr3d.hip).
+enum class RRKernel { Window, Shuffle, Pipe, Black };
+struct RRPlan {
+    RRKernel kernel = RRKernel::Window;
+    int T = 4, CR = 1, OWN = 4;       // waves per workgroup (TYW, T); Shuffle: coarse rows per lane; Pipe: fine rows per wave
+    int gx = 0, gy = 0, pzchunk = 0;  // tiles across x and y, coarse planes per run
+    dim3 grid, block;
+    int xcd = 0;
+};
+// (shared by two files of the library, not part of its interface: hidden from the symbol table of the shared object)
+__attribute__((visibility("hidden"))) bool rr_plan(const mgx_ctx* ctx, bool xsplit, bool black, const int n[3], const int cn[3], int planes,
+                                                   RRPlan& p);
+template <class real>  // mgx_relax_rr3d.hip
+__attribute__((visibility("hidden"))) bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int mode,
+                                                                real* coarse_f, const int cn[3], int fzoff, int czoff, int pzbeg, int pzend);
 
 // two consecutive elements of `real` as one vector value
 template <class real>
@@ -132,6 +151,26 @@ template <class real>
 static inline bool exact_reciprocal(real h) {
     int e;
     return h > 0 && std::isnormal(h) && std::frexp(h, &e) == (real)0.5 && std::isnormal((real)1 / h);
+}
+// ... for all three squared spacings of a level with spacings h
+template <class real>
+static inline bool exact_reciprocals(const real h[3]) {
+    return exact_reciprocal(h[0] * h[0]) && exact_reciprocal(h[1] * h[1]) && exact_reciprocal(h[2] * h[2]);
+}
+
+// What every host caller gives the residual kernels for a level with spacings h: the squared spacings hx2 .. (N3/MultiGrid3D.cpp:
+// 687-689, as the smoother uses them); the residual's qx .. = the squares or, where residual_restrict3d.rcp is on and all three are
+// powers of two, their exact reciprocals (residual3d_point, MODE | 2); and the kernels' MODE = residual mode | rcp << 1.
+template <class real>
+struct ResidualScale {
+    real hx2, hy2, hz2, qx, qy, qz;
+    int mode;
+};
+template <class real>
+static inline ResidualScale<real> residual_scale(const mgx_ctx* ctx, const real h[3], int mode) {
+    const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
+    if (!ctx->rr_rcp || !exact_reciprocals(h)) return {hx2, hy2, hz2, hx2, hy2, hz2, mode};
+    return {hx2, hy2, hz2, (real)1 / hx2, (real)1 / hy2, (real)1 / hz2, mode | 2};
 }
 
 // MultiGrid3D::Restrict interior formula.                   N3/MultiGrid3D.cpp:122-180

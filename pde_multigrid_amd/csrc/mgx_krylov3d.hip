@@ -257,16 +257,12 @@ int laplace_dot3d(mgx_ctx* ctx, const real* p, real* q, const int n[3], const re
     MGX_REQUIRE(ctx && p && q && h && dev_work && dev_sum, MGX_ERR_INVALID, "laplace_dot: NULL argument");
     MGX_USE(ctx);
     MGX_TRY_RET(krylov_check(n, "laplace_dot"));
-    real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];  // as mgx3dxs_residual forms them
-    const bool rcp = ctx->rr_rcp && exact_reciprocal(hx2) && exact_reciprocal(hy2) && exact_reciprocal(hz2);  // residual3d_point
-    if (rcp) {
-        hx2 = (real)1 / hx2;
-        hy2 = (real)1 / hy2;
-        hz2 = (real)1 / hz2;
-    }
+    const ResidualScale<real> s = residual_scale<real>(ctx, h, MGX_RESIDUAL_CORRECT);  // as mgx3dxs_residual forms them: MODE 1 or 3
     const dim3 g = krylov_grid(n);
-    if (rcp) MGX_LAUNCH((laplace_dot3d_xs_kernel<real, 3>), g, krylov_block(), 0, ctx->compute, p, q, n[0], n[1], hx2, hy2, hz2, dev_work);
-    else MGX_LAUNCH((laplace_dot3d_xs_kernel<real, 1>), g, krylov_block(), 0, ctx->compute, p, q, n[0], n[1], hx2, hy2, hz2, dev_work);
+    with_value<1, 3>(s.mode, [&](auto m) __attribute__((always_inline)) {
+        MGX_LAUNCH((laplace_dot3d_xs_kernel<real, decltype(m)::value>), g, krylov_block(), 0, ctx->compute, p, q, n[0], n[1], s.qx, s.qy,
+                   s.qz, dev_work);
+    });
     MGX_LAUNCH_CHECK();
     return krylov_final(ctx, dev_work, (size_t)g.x * g.y, 1, dev_sum);
 }

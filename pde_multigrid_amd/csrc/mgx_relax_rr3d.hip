@@ -283,8 +283,8 @@ __global__ void __launch_bounds__(64 * TYW, 4)  // four waves per SIMD (128 VGPR
     if (!(A & 32)) complete(pz1 - 1);
 }
 
-// One launch: black pass + residual + restrict over the whole level.  hx2 .. : squared spacings; rcp: the residual multiplies by
-// their exact reciprocals.  Returns false when the level is not taken (too small for the tile shape).
+// One launch: black pass + residual + restrict over the whole level.  Returns false when the level is not taken (too small for the
+// tile shape).
 // Automatic choice (measured, tools/rr_black_time.py): fp64 from 513-point rows on (513^3: 0.55 against 0.71 ms for the black
 // pass + residual + restrict, 1025^3: 11.5 against 13.6 ms with the two red+black sweeps before; 257^3: equal, left alone);
 // fp32 moves half the bytes with the same instructions and is no faster than its separate launches (513^3: 0.91 / 0.87 ms).
@@ -296,56 +296,38 @@ bool relax_rr3d_xs_takes(const mgx_ctx* ctx, const int n[3], const int cn[3], si
 }
 
 template <class real>
-bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], real hx2, real hy2, real hz2, int mode, bool rcp,
-                          real* coarse_f, const int cn[3], int fzoff, int czoff, int pzbeg, int pzend) {
+bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int mode, real* coarse_f, const int cn[3],
+                          int fzoff, int czoff, int pzbeg, int pzend) {
     // n, cn: GLOBAL sizes; v / f start at global fine plane fzoff, coarse_f at global coarse plane czoff; the launch relaxes
     // the black points of the fine planes [2 pzbeg - 1, 2 pzend - 1] and forms the coarse planes [pzbeg, pzend)
     if (!relax_rr3d_xs_takes(ctx, n, cn, sizeof(real)) || pzbeg < 1 || pzend > cn[2] - 1 || pzend <= pzbeg) return false;
-    const int T = ctx->rr_black_waves == 12 ? 12 : ctx->rr_black_waves == 8 ? 8 : 16;
-    const int wg_per_cu = T == 8 ? 2 : 1;
-    const int gx = ceil_div(cn[0] - 2, 61), gy = ceil_div(cn[1] - 2, T - 2);
-    const int tiles = gx * gy, planes = pzend - pzbeg;
-    int pzc = ctx->rr_pzchunk;
-    if (pzc <= 0) {
-        // all workgroups take the same time and one fits a CU: the fewest runs that fill whole rounds to 90 %, runs of at least
-        // 8 coarse planes (the two planes a run relaxes before its first residual)
-        pzc = ceil_div(planes, runs_filling_rounds(tiles, planes, (long long)ctx->num_cus * wg_per_cu, 16, 8, 2));
-    }
-    dim3 g(tiles * ceil_div(planes, pzc), 1, 1);
-    real qx = hx2, qy = hy2, qz = hz2;
-    if (rcp) {
-        qx = (real)1 / hx2;
-        qy = (real)1 / hy2;
-        qz = (real)1 / hz2;
-    }
-#define MGX_BRR_D(M, W, D)                                                                                                     \
-    MGX_LAUNCH((relax_rr3d_xs_kernel<real, M, W, D>), g, dim3(64, W, 1), 0, ctx->compute, (const real*)v, v, f, n[0], n[1], \
-                       n[2], hx2, hy2, hz2, qx, qy, qz, coarse_f, cn[0], cn[1], cn[2], pzc, gx, gy, ctx->rr_xcd >= 1, pzbeg, pzend, fzoff,   \
-                       czoff, ctx->rr_black_abl)
+    RRPlan p;
+    rr_plan(ctx, true, true, n, cn, pzend - pzbeg, p);
+    // the relaxation uses the squared spacings, the residual s.qx .. (the exact reciprocals under MODE | 2)
+    const ResidualScale<real> s = residual_scale<real>(ctx, h, mode);
+    bool done = false;
+    const auto launch = [&](auto m, auto waves, auto dbg) {
+        done = true;
+        MGX_LAUNCH((relax_rr3d_xs_kernel<real, decltype(m)::value, decltype(waves)::value, decltype(dbg)::value>), p.grid, p.block, 0,
+                   ctx->compute, (const real*)v, v, f, n[0], n[1], n[2], s.hx2, s.hy2, s.hz2, s.qx, s.qy, s.qz, coarse_f, cn[0], cn[1],
+                   cn[2], p.pzchunk, p.gx, p.gy, p.xcd, pzbeg, pzend, fzoff, czoff, ctx->rr_black_abl);
+    };
+    with_value<0, 1, 2, 3>(s.mode, [&](auto m) {
+        with_value<16, 12, 8>(p.T, [&](auto waves) {
 #ifdef MGX_DIAGNOSTICS
-#define MGX_BRR(M, W) do { if (ctx->rr_black_abl) MGX_BRR_D(M, W, 1); else MGX_BRR_D(M, W, 0); } while (0)
-#else
-#define MGX_BRR(M, W) MGX_BRR_D(M, W, 0)
+            if (ctx->rr_black_abl) return launch(m, waves, std::integral_constant<int, 1>());
 #endif
-#define MGX_BRR_W(M)                              \
-    do {                                          \
-        if (T == 16) MGX_BRR(M, 16); else if (T == 12) MGX_BRR(M, 12); else MGX_BRR(M, 8); \
-    } while (0)
-    if (mode == MGX_RESIDUAL_REF_COMPAT) {
-        if (rcp) MGX_BRR_W(2); else MGX_BRR_W(0);
-    } else {
-        if (rcp) MGX_BRR_W(3); else MGX_BRR_W(1);
-    }
-#undef MGX_BRR_W
-#undef MGX_BRR
-#undef MGX_BRR_D
+            launch(m, waves, std::integral_constant<int, 0>());
+        });
+    });
+    if (!done) return false;  // no instantiation has the planned shape
     snprintf(ctx->last_rr_kernel, sizeof ctx->last_rr_kernel, "relax_rr3d_xs_kernel<%s,%d,%d>", sizeof(real) == 8 ? "double" : "float",
-             (mode == MGX_RESIDUAL_REF_COMPAT ? 0 : 1) + (rcp ? 2 : 0), T);
+             s.mode, p.T);
     return true;
 }
-template bool relax_rr3d_xs_launch<float>(mgx_ctx*, float*, const float*, const int[3], float, float, float, int, bool, float*, const int[3],
-                                          int, int, int, int);
-template bool relax_rr3d_xs_launch<double>(mgx_ctx*, double*, const double*, const int[3], double, double, double, int, bool, double*,
-                                           const int[3], int, int, int, int);
+template bool relax_rr3d_xs_launch<float>(mgx_ctx*, float*, const float*, const int[3], const float[3], int, float*, const int[3], int, int,
+                                          int, int);
+template bool relax_rr3d_xs_launch<double>(mgx_ctx*, double*, const double*, const int[3], const double[3], int, double*, const int[3], int,
+                                           int, int, int);
 
 }  // namespace mgx
