@@ -129,6 +129,9 @@ typedef struct mgGraphFlags {
         mgGraphFlags graph_post[MG_MAX_LEVELS];                                                          \
         mgGraphRec pcg_graph_rec;                                                                        \
         mgGraphFlags pcg_graph_post;                                                                     \
+        /* internal: state of PCG_mixed (fp64 only; NULL until its first call, freed by _destroy): the  */ \
+        /* fp32 twin hierarchy that runs the preconditioning V-cycle, and the mixed kernels' scratch     */ \
+        void* pcg_mixed;                                                                                 \
     } mgMultiGrid3D_##R;                                                                                 \
     int mgMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6],     \
                                    mgMultiGrid3D_##R** out);                                             \
@@ -381,6 +384,22 @@ typedef struct mgGraphFlags {
 
 MG_DECLARE(f32, float)
 MG_DECLARE(f64, double)
+
+/* PCG_mixed (an addition): mgMultiGrid3D_f64_PCG with the preconditioner in fp32.  The same contract in every respect -- arguments,
+ * error codes, layout = 1 and MGX_RESIDUAL_CORRECT, d_v[0] the guess with its Dirichlet boundary, d_f[0] restored bit for bit,
+ * *rel_res the TRUE fp64 relative residual of the result, a breakdown returns MGX_OK with *converged = 0, use_graph captures the
+ * preconditioning cycle -- but the iterate, the residual and the stopping test stay fp64 while the preconditioner is one fp32
+ * VCycle(0, v1, v2) from zero on an fp32 twin hierarchy (same sizes, the range converted to float, x-split, CORRECT), built on
+ * the first call, given numGrids and use_graph of this hierarchy on every call, rebuilt when numGrids exceeds its levels and
+ * freed by _destroy.  The twin is new device memory: four fp32 arrays per level, 2,645,596,160 bytes at 513^3.
+ * krylov = 0: defect correction, x += M32(r) with r = b - A x, every residual of host_hist the true one; krylov != 0: the
+ * flexible CG of PCG with z = M32(r).  M32(r) = (double)V32((float)(r s)) / s with s = 2^-floor(log2(rms of the last residual
+ * read)), a power of two, so the scale changes no bits; it keeps fp32 out of underflow and overflow. */
+int mgMultiGrid3D_f64_PCG_mixed(mgMultiGrid3D_f64* mg, int v1, int v2, double tol, int maxit, int krylov, int* iters,
+                                double* rel_res, int* converged, double* host_hist, int hist_cap);
+/* mg3d_solve_pcg_f64 with PCG_mixed */
+int mg3d_solve_pcg_mixed_f64(mgx_ctx* ctx, double* grid, const double* rhs, const int sizeXYZ[3], const double range[6], int nlevels,
+                             int v1, int v2, double tol, int maxit, int krylov, int* iters, double* rel_res, int* converged);
 
 /* numGrids = (int)log2(minSize - 1)            N3/MultiGrid3D.cpp:33-34 */
 int mg_num_grids(int minSize);

@@ -500,6 +500,33 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)
 
+/* ---- vector kernels of the mixed-precision solve (mgMultiGrid3D_f64_PCG_mixed), x-split layout ----------------------------
+ * fp64 arrays (x, b, r, p, q) next to fp32 arrays of the same grid (r32, z32: the fp32 twin hierarchy's d_f[0] / d_v[0]), each in
+ * the x-split geometry of its own precision.  The contract of the kernels above: interior points only, sums in double in a fixed
+ * order, dev_work of mgx3dxs_mixed_work_elems_f64 doubles, asynchronous on the compute stream.  s (and inv_s = 1 / s) is meant to
+ * be a power of two: r32 = (float)(r s) and z = (double)z32 * inv_s then rescale exactly.  An addition: the reference has no
+ * Krylov solver. */
+size_t mgx3dxs_mixed_work_elems_f64(const int n[3]);
+/* correct_residual_demote: with z32, xo = x + (double)z32 * inv_sz on the interior (xo != x: the pass is out of place, and xo's
+ * boundary is left as it is), then r = b - A xo; without (z32 = NULL, xo unused) r = b - A x.  r (bit-identical to
+ * mgx3dxs_residual_f64(..., MGX_RESIDUAL_CORRECT)) is not stored: r32 = (float)(r s) is, and *dev_sum = <r, r>.  One z-marching
+ * launch, or two where the context's "mixed3d.fused" is 0 (a streaming correction into xo, then the pass on xo, which then
+ * takes the boundary values from xo: the same bits when xo's boundary is x's). */
+int mgx3dxs_correct_residual_demote_f64(mgx_ctx* ctx, const double* x, double* xo, const double* b, const float* z32, double inv_sz,
+                                        float* r32, double s, const int n[3], const double h[3], double* dev_work, double* dev_sum);
+/* demote: r32 = (float)(r s) */
+int mgx3dxs_demote_f64(mgx_ctx* ctx, const double* r, float* r32, double s, const int n[3]);
+/* cg_update_demote: x += a p (skipped when x is NULL), r -= a q with a = *dev_alpha, r32 = (float)(r s); *dev_sum = <r, r> */
+int mgx3dxs_cg_update_demote_f64(mgx_ctx* ctx, double* x, const double* p, double* r, const double* q, float* r32, double s,
+                                 const int n[3], const double* dev_alpha, double* dev_work, double* dev_sum);
+/* dot2_mixed: dev_sum[0] = <z, b> and, unless c is NULL, dev_sum[1] = <z, c>, with z = (double)z32 * inv_s */
+int mgx3dxs_dot2_mixed_f64(mgx_ctx* ctx, const float* z32, double inv_s, const double* b, const double* c, const int n[3],
+                           double* dev_work, double* dev_sum);
+/* cg_direction_mixed: x += *dev_alpha * p with the old p (skipped when x is NULL), then p = z + *dev_beta * p, or p = z when
+ * dev_beta is NULL, with z = (double)z32 * inv_s */
+int mgx3dxs_cg_direction_mixed_f64(mgx_ctx* ctx, double* x, double* p, const float* z32, double inv_s, const int n[3],
+                                   const double* dev_alpha, const double* dev_beta);
+
 /* State vector of the flexible CG solve, MGX_CG_STATE device doubles, and its scalar steps (one thread, on the compute stream):
  *   step 0: alpha = RZ / PQ; NaN when PQ is 0 or alpha or PQ is not finite (a breakdown: the following cg_update then
  *           reports a NaN norm);

@@ -52,6 +52,9 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out) {
     return MGX_OK;
 }
 
+/* the state of mgMultiGrid3D_f64_PCG_mixed (mg_mixed3d.inc): freed by either instantiation's _destroy, NULL in fp32 */
+static void mg_mixed3d_free(mgx_ctx* ctx, void* state);
+
 #define REAL float
 #define R f32
 #define MG_EXP(x) expf(x) /* exp(float) resolves to the float overload in the reference */
@@ -73,3 +76,5 @@ int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out) {
 #undef REAL
 #undef R
 #undef MG_EXP
+
+#include "mg_mixed3d.inc"

@@ -143,6 +143,7 @@ void FN(destroy)(MGRID* mg) {
     if (mg->pcg_graph_exec) mgx_graph_destroy(mg->ctx, mg->pcg_graph_exec);
     mgx_free(mg->ctx, mg->pcg_x); mgx_free(mg->ctx, mg->pcg_b); mgx_free(mg->ctx, mg->pcg_p); mgx_free(mg->ctx, mg->pcg_q);
     mgx_free(mg->ctx, mg->pcg_state); mgx_free(mg->ctx, mg->pcg_work);
+    mg_mixed3d_free(mg->ctx, mg->pcg_mixed);
     if (mg->grids3D)
         for (int i = 0; i < mg->maxGrids; i++) MG_CAT(grid3_free_, R)(mg->ctx, mg->grids3D[i]);
     free(mg->grids3D);

@@ -21,6 +21,10 @@ struct mgx_ctx {
     int relax_xcd = 1;     // XCD-aware block -> tile mapping
     int rr_rows = 0;       // fine rows per wave of the pipelined residual+restrict kernel (0: by level size; 2: sixteen waves)
     int rr_rcp = 1;        // residual: multiply by exact reciprocals when the squared spacings are powers of two
+    int mixed_fused = 0;   // mixed-precision defect correction: correction + residual + demote in one z-marching launch (1) or
+                           // a streaming correction first (0, the two-launch form; default: measured faster at 513^3)
+    int mixed_rows = 4;    // rows per wave of that z-marching pass (2, 4 or 8)
+    int mixed_zchunk = 0;  // its planes per workgroup, 0 = automatic
     int rr_xcd = 1;        // the same for residual+restrict: 1 = the pipelined kernel only (measured: -2 % at 513^3, +14 % with
                            // the streaming kernel at 257^3), 2 = both kernels, 0 = plain order
     int relax_rows = 4;    // consecutive rows per lane (register blocking in y) of relax3d_xs_kernel

@@ -3742,6 +3742,15 @@ int mgx_ctx_set_param(mgx_ctx* ctx, const char* name, int value) {
     } else if (!strcmp(name, "residual_restrict3d.rcp")) {
         MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "residual_restrict3d.rcp must be 0 or 1");
         ctx->rr_rcp = value;
+    } else if (!strcmp(name, "mixed3d.fused")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "mixed3d.fused must be 0 or 1");
+        ctx->mixed_fused = value;
+    } else if (!strcmp(name, "mixed3d.rows")) {
+        MGX_REQUIRE(value == 2 || value == 4 || value == 8, MGX_ERR_INVALID, "mixed3d.rows must be 2, 4 or 8");
+        ctx->mixed_rows = value;
+    } else if (!strcmp(name, "mixed3d.zchunk")) {
+        MGX_REQUIRE(value >= 0, MGX_ERR_INVALID, "mixed3d.zchunk must be >= 0 (0 = automatic)");
+        ctx->mixed_zchunk = value;
     } else if (!strcmp(name, "residual_restrict3d.xcd")) {
         MGX_REQUIRE(value >= 0 && value <= 2, MGX_ERR_INVALID, "residual_restrict3d.xcd must be 0, 1 or 2");
         ctx->rr_xcd = value;

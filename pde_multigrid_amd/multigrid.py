@@ -486,6 +486,67 @@ class _Ops3D(_Ops):
         (xo, po, _), _ = self._krylov(ctx, n, [x, p, z], [float(alpha or 0.0), float(beta or 0.0)], call, dtype, 0)
         return xo, po
 
+    # ---- vector kernels of the mixed-precision solve (fp64 only): fp64 arrays and fp32 arrays (r32, z32) packed (x-split), each
+    # in its own precision's geometry; s / inv_s are applied as given (the solver passes powers of two)
+    def _mixed(self, ctx, n, arrays, scalars, call, nsum):
+        """upload arrays (each in its own dtype) and the device doubles `scalars`, run call(work, *scalar ptrs, *array ptrs),
+        return (arrays as stored, sums)"""
+        assert self.xsplit, "the mixed kernels exist for the x-split layout only"
+        fn = lib.mgx3dxs_mixed_work_elems_f64
+        fn.restype = C.c_size_t
+        work = ctx.to_device(np.zeros(max(int(fn(_ip(n))), 1), np.float64))
+        dev = ctx.to_device(np.array(scalars + [0.0] * nsum + [0.0], np.float64))
+        ptrs = [ctx.to_device(a) if a is not None else None for a in arrays]
+        try:
+            sp = [C.c_void_p(dev.value + 8 * i) for i in range(len(scalars) + nsum)]
+            check(call(work, *sp, *ptrs))
+            sums = ctx.to_host(dev, (len(scalars) + nsum,), np.float64)[len(scalars):]
+            return [ctx.to_host(p, a.shape, a.dtype) if p is not None else None for p, a in zip(ptrs, arrays)], sums
+        finally:
+            for p in ptrs + [dev, work]:
+                if p is not None:
+                    ctx.free(p)
+
+    def correct_residual_demote(self, ctx, x, b, r32, n, rng, s, z=None, inv_sz=1.0, xo=None):
+        """[xo = x + float64(z) * inv_sz;] r = b - A xo (A x without z); r32 = float32(r s); returns (xo or None, r32, <r, r>).
+        xo: the array corrected into (default: a copy of x, so its boundary and pads are x's)"""
+        h = _rp(grid_spacing(n, rng, np.float64), C.c_double)
+        if z is not None and xo is None:
+            xo = x.copy()
+        fn = lib.mgx3dxs_correct_residual_demote_f64
+
+        def call(w, s0, xp, op, bp, zp, rp):
+            return fn(ctx._h, xp, op, bp, zp, C.c_double(inv_sz), rp, C.c_double(s), _ip(n), h, w, s0)
+        (_, xo_, _, _, ro), sums = self._mixed(ctx, n, [x, xo if z is not None else None, b, z, r32], [], call, 1)
+        return xo_, ro, float(sums[0])
+
+    def demote(self, ctx, r, r32, n, s):
+        """r32 = float32(r s) on the interior; returns r32"""
+        (_, ro), _ = self._mixed(ctx, n, [r, r32], [], lambda w, rp, op: lib.mgx3dxs_demote_f64(ctx._h, rp, op, C.c_double(s), _ip(n)), 0)
+        return ro
+
+    def cg_update_demote(self, ctx, x, p, r, q, r32, n, alpha, s):
+        """x += alpha p (x None: skipped); r -= alpha q; r32 = float32(r s).  Returns (x, r, r32, <r, r>)."""
+        def call(w, a, s0, xp, pp, rp, qp, op):
+            return lib.mgx3dxs_cg_update_demote_f64(ctx._h, xp, pp, rp, qp, op, C.c_double(s), _ip(n), a, w, s0)
+        (xo, _, ro, _, o32), sums = self._mixed(ctx, n, [x, p, r, q, r32], [float(alpha)], call, 1)
+        return xo, ro, o32, float(sums[0])
+
+    def dot2_mixed(self, ctx, z32, inv_s, b, c, n):
+        """(<z, b>, <z, c>) with z = float64(z32) * inv_s (c None: <z, c> is None)"""
+        def call(w, s0, s1, zp, bp, cp):
+            return lib.mgx3dxs_dot2_mixed_f64(ctx._h, zp, C.c_double(inv_s), bp, cp, _ip(n), w, s0)
+        _, sums = self._mixed(ctx, n, [z32, b, c], [], call, 2)
+        return float(sums[0]), (float(sums[1]) if c is not None else None)
+
+    def cg_direction_mixed(self, ctx, x, p, z32, inv_s, n, alpha=None, beta=None):
+        """x += alpha p (x None: skipped); p = z + beta p, or p = z when beta is None, z = float64(z32) * inv_s.  Returns (x, p)."""
+        def call(w, a, b, xp, pp, zp):
+            return lib.mgx3dxs_cg_direction_mixed_f64(ctx._h, xp, pp, zp, C.c_double(inv_s), _ip(n), a if alpha is not None else None,
+                                                      b if beta is not None else None)
+        (xo, po, _), _ = self._mixed(ctx, n, [x, p, z32], [float(alpha or 0.0), float(beta or 0.0)], call, 0)
+        return xo, po
+
 
 class _Ops2D(_Ops):
     def __init__(self):
@@ -606,7 +667,7 @@ def _grid3_struct(ct):
                     ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
                     ("pcg_work", C.c_void_p), ("pcg_graph_exec", C.c_void_p), ("pcg_graph_key", C.c_longlong),
                     ("graph_rec", GraphRec * 32), ("graph_post", GraphFlags * 32), ("pcg_graph_rec", GraphRec),
-                    ("pcg_graph_post", GraphFlags)]
+                    ("pcg_graph_post", GraphFlags), ("pcg_mixed", C.c_void_p)]
 
     return Grid3D, MultiGrid3D
 
@@ -768,16 +829,27 @@ class MultiGrid3D(_MGBase):
         self._call("download_f", C.c_int(gridID), out.ctypes.data_as(C.c_void_p))
         return out
 
-    def PCG(self, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True):
+    def PCG(self, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64"):
         """Solve on level 0 to a relative residual < tol from the guess in v[0] (its boundary = the Dirichlet data): flexible CG
         preconditioned by one V(v1, v2) cycle from zero per iteration, or plain V-cycles with krylov=False.  Needs the x-split
         layout and residual_mode=CORRECT.  Returns (iters, rel_res, converged, history): rel_res is the TRUE relative
-        residual of the result, history one relative residual per iteration."""
+        residual of the result, history one relative residual per iteration.
+
+        fp32 cannot reach tolerances much below 1e-6 and fp64 cycles stream twice the bytes: an fp64 hierarchy with
+        precond="f32" (mgMultiGrid3D_f64_PCG_mixed) keeps the iterate, the residual and the stopping test in fp64 and runs
+        the V-cycle in fp32 on a twin hierarchy it builds on first use -- fp64 tolerances in close to fp32 time, for the
+        twin's extra device memory (four fp32 arrays per level).  With krylov=False that is defect correction, whose
+        history holds true residuals."""
+        if precond not in ("f64", "f32"):
+            raise ValueError("precond must be 'f64' or 'f32', not %r" % (precond,))
+        if precond == "f32" and self.dtype != np.float64:
+            raise ValueError("precond='f32' needs an fp64 hierarchy (the fp32 one already runs its V-cycle in fp32)")
         it, conv = C.c_int(), C.c_int()
         rel = C.c_double()
         hist = np.zeros(int(maxit), np.float64)
-        self._call("PCG", C.c_int(v1), C.c_int(v2), C.c_double(tol), C.c_int(maxit), C.c_int(int(bool(krylov))), C.byref(it),
-                   C.byref(rel), C.byref(conv), hist.ctypes.data_as(C.c_void_p), C.c_int(len(hist)))
+        self._call("PCG_mixed" if precond == "f32" else "PCG", C.c_int(v1), C.c_int(v2), C.c_double(tol), C.c_int(maxit),
+                   C.c_int(int(bool(krylov))), C.byref(it), C.byref(rel), C.byref(conv), hist.ctypes.data_as(C.c_void_p),
+                   C.c_int(len(hist)))
         return int(it.value), float(rel.value), bool(conv.value), hist[:it.value].copy()
 
 
@@ -1091,10 +1163,17 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
     return out
 
 
-def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True):
-    """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged)"""
+def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64"):
+    """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
+    precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG)"""
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
+    if precond not in ("f64", "f32"):
+        raise ValueError("precond must be 'f64' or 'f32', not %r" % (precond,))
+    if precond == "f32" and s != "f64":
+        raise ValueError("precond='f32' needs an fp64 grid")
+    if precond == "f32":
+        s = "mixed_f64"
     r = np.ascontiguousarray(rhs, grid.dtype).ctypes.data_as(C.c_void_p) if rhs is not None else None
     n = tuple(reversed(grid.shape))
     it, conv = C.c_int(), C.c_int()
