@@ -505,7 +505,10 @@ MGX_DECLARE_OPS(f64, double)
  * the x-split geometry of its own precision.  The contract of the kernels above: interior points only, sums in double in a fixed
  * order, dev_work of mgx3dxs_mixed_work_elems_f64 doubles, asynchronous on the compute stream.  s (and inv_s = 1 / s) is meant to
  * be a power of two: r32 = (float)(r s) and z = (double)z32 * inv_s then rescale exactly.  An addition: the reference has no
- * Krylov solver. */
+ * Krylov solver.
+ * mixed_work_elems: the most partials any of these kernels writes under any "mixed3d.*" setting -- the larger of the Krylov
+ * kernels' 2 * ceil((sy - 2) / 4) * (sz - 2) and the z-marching pass's count at its smallest tiles ("mixed3d.rows" = 2,
+ * "mixed3d.zchunk" = 1): ceil(((sx + 1) / 2 - 1) / 63) * ceil((sy - 2) / 8) * (sz - 2), which that setting writes exactly. */
 size_t mgx3dxs_mixed_work_elems_f64(const int n[3]);
 /* correct_residual_demote: with z32, xo = x + (double)z32 * inv_sz on the interior (xo != x: the pass is out of place, and xo's
  * boundary is left as it is), then r = b - A xo; without (z32 = NULL, xo unused) r = b - A x.  r (bit-identical to
@@ -514,6 +517,14 @@ size_t mgx3dxs_mixed_work_elems_f64(const int n[3]);
  * takes the boundary values from xo: the same bits when xo's boundary is x's). */
 int mgx3dxs_correct_residual_demote_f64(mgx_ctx* ctx, const double* x, double* xo, const double* b, const float* z32, double inv_sz,
                                         float* r32, double s, const int n[3], const double h[3], double* dev_work, double* dev_sum);
+/* correct_residual_demote_plan: what that call would launch on a level of these sizes and spacings with the context's present
+ * "mixed3d.*" parameters, without launching: out = {rows per wave, planes per run, tiles across x, tiles across y, plane runs,
+ * form of the residual (1: dividing, 3: exact reciprocals), launches (2: the streaming correction first; else 1)}.  The
+ * z-marching launch writes tiles across x * tiles across y * plane runs partials. */
+enum { MGX_CRD_ROWS = 0, MGX_CRD_ZCHUNK = 1, MGX_CRD_GX = 2, MGX_CRD_GY = 3, MGX_CRD_GZ = 4, MGX_CRD_MODE = 5, MGX_CRD_LAUNCHES = 6,
+       MGX_CRD_PLAN = 7 };
+int mgx3dxs_correct_residual_demote_plan_f64(const mgx_ctx* ctx, const int n[3], const double h[3], int with_correction,
+                                             int out[MGX_CRD_PLAN]);
 /* demote: r32 = (float)(r s) */
 int mgx3dxs_demote_f64(mgx_ctx* ctx, const double* r, float* r32, double s, const int n[3]);
 /* cg_update_demote: x += a p (skipped when x is NULL), r -= a q with a = *dev_alpha, r32 = (float)(r s); *dev_sum = <r, r> */

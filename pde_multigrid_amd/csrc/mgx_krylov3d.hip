@@ -630,10 +630,17 @@ int cg_direction3d(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3]
 struct CrdPlan {
     int TR, zchunk;
     dim3 grid, block;
+    int mode;      // MODE of the residual: 1 dividing, 3 exact reciprocals
+    int launches;  // 2: the streaming correction first, then the pass without it; 1: the pass alone (correcting, if asked to)
+    double qx, qy, qz;
 };
 constexpr int CRD_TYW = 4;
-static CrdPlan crd_plan(const mgx_ctx* ctx, const int n[3]) {
+static CrdPlan crd_plan(const mgx_ctx* ctx, const int n[3], const double h[3], bool with_correction) {
     CrdPlan p;
+    const ResidualScale<double> sc = residual_scale<double>(ctx, h, MGX_RESIDUAL_CORRECT);  // as mgx3dxs_residual forms them
+    p.mode = sc.mode;
+    p.qx = sc.qx, p.qy = sc.qy, p.qz = sc.qz;
+    p.launches = with_correction && !ctx->mixed_fused ? 2 : 1;
     p.TR = ctx->mixed_rows;
     const unsigned gx = (unsigned)ceil_div(std::max((n[0] + 1) / 2 - 1, 1), 63), gy = (unsigned)ceil_div(n[1] - 2, p.TR * CRD_TYW);
     p.zchunk = ctx->mixed_zchunk;
@@ -710,28 +717,42 @@ int correct_residual_demote3d(mgx_ctx* ctx, const double* x, double* xo, const d
     MGX_REQUIRE(!z32 || (xo && xo != x), MGX_ERR_INVALID, "correct_residual_demote: the correction needs an output array xo != x");
     MGX_USE(ctx);
     MGX_TRY_RET(krylov_check(n, "correct_residual_demote"));
-    const ResidualScale<double> sc = residual_scale<double>(ctx, h, MGX_RESIDUAL_CORRECT);  // as mgx3dxs_residual forms them
-    const CrdPlan p = crd_plan(ctx, n);
+    const CrdPlan p = crd_plan(ctx, n, h, z32 != nullptr);
     bool corr = z32 != nullptr;
-    if (corr && !ctx->mixed_fused) {  // the two-launch form: a streaming correction, then the pass without it
+    if (p.launches == 2) {  // the two-launch form: a streaming correction, then the pass without it
         MGX_LAUNCH(correct_mixed3d_xs_kernel, krylov_grid(n), krylov_block(), 0, ctx->compute, x, xo, z32, inv_sz, n[0], n[1]);
         MGX_LAUNCH_CHECK();
         x = xo;
         corr = false;
     }
-    with_value<1, 3>(sc.mode, [&](auto m) __attribute__((always_inline)) {
+    with_value<1, 3>(p.mode, [&](auto m) __attribute__((always_inline)) {
         with_value<2, 4, 8>(p.TR, [&](auto tr) __attribute__((always_inline)) {
             constexpr int M = decltype(m)::value, TR = decltype(tr)::value;
             if (corr)
                 MGX_LAUNCH((correct_residual_demote3d_xs_kernel<M, true, TR, CRD_TYW>), p.grid, p.block, 0, ctx->compute, x, xo, b, z32, r32,
-                           n[0], n[1], n[2], sc.qx, sc.qy, sc.qz, inv_sz, s, p.zchunk, dev_work);
+                           n[0], n[1], n[2], p.qx, p.qy, p.qz, inv_sz, s, p.zchunk, dev_work);
             else
                 MGX_LAUNCH((correct_residual_demote3d_xs_kernel<M, false, TR, CRD_TYW>), p.grid, p.block, 0, ctx->compute, x, xo, b, z32,
-                           r32, n[0], n[1], n[2], sc.qx, sc.qy, sc.qz, inv_sz, s, p.zchunk, dev_work);
+                           r32, n[0], n[1], n[2], p.qx, p.qy, p.qz, inv_sz, s, p.zchunk, dev_work);
         });
     });
     MGX_LAUNCH_CHECK();
     return krylov_final(ctx, dev_work, (size_t)p.grid.x * p.grid.y * p.grid.z, 1, dev_sum);
+}
+
+// what correct_residual_demote3d launches: the plan it launches from
+int correct_residual_demote_plan3d(const mgx_ctx* ctx, const int n[3], const double h[3], int with_correction, int* out) {
+    MGX_REQUIRE(ctx && h && out, MGX_ERR_INVALID, "correct_residual_demote_plan: NULL argument");
+    MGX_TRY_RET(krylov_check(n, "correct_residual_demote_plan"));
+    const CrdPlan p = crd_plan(ctx, n, h, with_correction != 0);
+    out[MGX_CRD_ROWS] = p.TR;
+    out[MGX_CRD_ZCHUNK] = p.zchunk;
+    out[MGX_CRD_GX] = (int)p.grid.x;
+    out[MGX_CRD_GY] = (int)p.grid.y;
+    out[MGX_CRD_GZ] = (int)p.grid.z;
+    out[MGX_CRD_MODE] = p.mode;
+    out[MGX_CRD_LAUNCHES] = p.launches;
+    return MGX_OK;
 }
 
 }  // namespace mgx
@@ -786,6 +807,10 @@ int mgx3dxs_cg_direction_mixed_f64(mgx_ctx* ctx, double* x, double* p, const flo
 int mgx3dxs_correct_residual_demote_f64(mgx_ctx* ctx, const double* x, double* xo, const double* b, const float* z32, double inv_sz,
                                         float* r32, double s, const int n[3], const double h[3], double* dev_work, double* dev_sum) {
     return mgx::correct_residual_demote3d(ctx, x, xo, b, z32, inv_sz, r32, s, n, h, dev_work, dev_sum);
+}
+int mgx3dxs_correct_residual_demote_plan_f64(const mgx_ctx* ctx, const int n[3], const double h[3], int with_correction,
+                                             int out[MGX_CRD_PLAN]) {
+    return mgx::correct_residual_demote_plan3d(ctx, n, h, with_correction, out);
 }
 
 }  // extern "C"

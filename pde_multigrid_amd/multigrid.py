@@ -426,22 +426,40 @@ class _Ops3D(_Ops):
 
 
     # ---- vector kernels of the preconditioned CG solve (x-split only; every array in the reference layout on the host)
+    # every work array is uploaded with WORK_GUARD sentinel doubles behind the elements the library asks for, and the
+    # sentinels are looked at after the call: a kernel that writes into the next WORK_GUARD doubles behind its work array
+    # fails the call (a write further out is not seen)
+    WORK_GUARD = 1024
+    WORK_SENTINEL = 0x7FF8C0DEC0DE0001
+
+    def _work_alloc(self, ctx, elems):
+        host = np.zeros(max(int(elems), 1) + self.WORK_GUARD, np.float64)
+        host[-self.WORK_GUARD:] = np.array(self.WORK_SENTINEL, np.uint64).view(np.float64)
+        return ctx.to_device(host), max(int(elems), 1)
+
+    def _work_check(self, ctx, work, elems):
+        tail = ctx.to_host(C.c_void_p(work.value + 8 * elems), (self.WORK_GUARD,), np.float64).view(np.uint64)
+        bad = np.nonzero(tail != self.WORK_SENTINEL)[0]
+        if bad.size:
+            raise AssertionError("work array of %d doubles: %d entries behind it were written, the first at +%d" % (elems, bad.size, bad[0]))
+
     def _krylov_work(self, ctx, n, dtype):
         s, _ = _ct(dtype)
         fn = getattr(lib, "mgx3dxs_krylov_work_elems_" + s)
         fn.restype = C.c_size_t
-        return ctx.to_device(np.zeros(max(int(fn(_ip(n))), 1), np.float64))
+        return self._work_alloc(ctx, fn(_ip(n)))
 
     def _krylov(self, ctx, n, arrays, scalars, call, dtype, nsum):
         """upload arrays (x-split) and the device doubles `scalars`, run call(work, sums, *scalar ptrs, *array ptrs), return
         (arrays as stored, padded rows, sums)"""
         assert self.xsplit, "the Krylov kernels exist for the x-split layout only"
-        work = self._krylov_work(ctx, n, dtype)
+        work, welems = self._krylov_work(ctx, n, dtype)
         dev = [ctx.to_device(np.array(scalars + [0.0] * nsum, np.float64))]
         ptrs = [ctx.to_device(a) if a is not None else None for a in arrays]
         try:
             sp = [C.c_void_p(dev[0].value + 8 * i) for i in range(len(scalars) + nsum)]
             check(call(work, *sp, *ptrs))
+            self._work_check(ctx, work, welems)
             sums = ctx.to_host(dev[0], (len(scalars) + nsum,), np.float64)[len(scalars):]
             return [ctx.to_host(p, a.shape, dtype) if p is not None else None for p, a in zip(ptrs, arrays)], sums
         finally:
@@ -494,12 +512,13 @@ class _Ops3D(_Ops):
         assert self.xsplit, "the mixed kernels exist for the x-split layout only"
         fn = lib.mgx3dxs_mixed_work_elems_f64
         fn.restype = C.c_size_t
-        work = ctx.to_device(np.zeros(max(int(fn(_ip(n))), 1), np.float64))
+        work, welems = self._work_alloc(ctx, fn(_ip(n)))
         dev = ctx.to_device(np.array(scalars + [0.0] * nsum + [0.0], np.float64))
         ptrs = [ctx.to_device(a) if a is not None else None for a in arrays]
         try:
             sp = [C.c_void_p(dev.value + 8 * i) for i in range(len(scalars) + nsum)]
             check(call(work, *sp, *ptrs))
+            self._work_check(ctx, work, welems)
             sums = ctx.to_host(dev, (len(scalars) + nsum,), np.float64)[len(scalars):]
             return [ctx.to_host(p, a.shape, a.dtype) if p is not None else None for p, a in zip(ptrs, arrays)], sums
         finally:
@@ -519,6 +538,15 @@ class _Ops3D(_Ops):
             return fn(ctx._h, xp, op, bp, zp, C.c_double(inv_sz), rp, C.c_double(s), _ip(n), h, w, s0)
         (_, xo_, _, _, ro), sums = self._mixed(ctx, n, [x, xo if z is not None else None, b, z, r32], [], call, 1)
         return xo_, ro, float(sums[0])
+
+    def correct_residual_demote_plan(self, ctx, n, rng, with_correction=False):
+        """what correct_residual_demote launches on this level with the context's present parameters: a dict of rows (per
+        wave), zchunk (planes per run), gx, gy, gz (tiles across x and y, plane runs), mode (1: dividing, 3: exact
+        reciprocals) and launches"""
+        out = (C.c_int * 7)()
+        h = _rp(grid_spacing(n, rng, np.float64), C.c_double)
+        check(lib.mgx3dxs_correct_residual_demote_plan_f64(ctx._h, _ip(n), h, C.c_int(int(with_correction)), out))
+        return dict(zip(("rows", "zchunk", "gx", "gy", "gz", "mode", "launches"), out))
 
     def demote(self, ctx, r, r32, n, s):
         """r32 = float32(r s) on the interior; returns r32"""

@@ -3,7 +3,6 @@
 The kernels are checked against numpy restatements (bit for bit where the issue fixes the expression, to 1e-13 for the sums);
 the solver against flexible CG written out in numpy below, preconditioned by the oracle's own V-cycle (the GPU V-cycle is
 bit-identical to it, so a divergence can only come from the new code)."""
-import math
 
 import numpy as np
 import pytest
@@ -13,6 +12,13 @@ import pde_multigrid_amd as P
 from conftest import bits_equal
 from odd_shapes import pack_poisoned, pads_unchanged
 from pde_multigrid_amd.multigrid import xs_unpack
+from solve_restated import boundary_mask as _boundary_mask
+from solve_restated import close as _close
+from solve_restated import fsum_dot as _fsum_dot
+from solve_restated import interior as _interior
+from solve_restated import m_cycle
+from solve_restated import problem as _problem
+import solve_restated
 
 pytestmark = pytest.mark.gpu
 RG = [-1, 1, 0, 2, 0.5, 3]
@@ -36,24 +42,6 @@ def ctx():
 
 def _rand(n3, dtype, seed):
     return np.random.default_rng(seed).uniform(-1, 1, O.shape(n3)).astype(dtype)
-
-
-def _interior(a):
-    return a[1:-1, 1:-1, 1:-1]
-
-
-def _boundary_mask(n3):
-    m = np.ones(O.shape(n3), bool)
-    m[1:-1, 1:-1, 1:-1] = False
-    return m
-
-
-def _fsum_dot(a, b):
-    return math.fsum((_interior(a).astype(np.float64) * _interior(b).astype(np.float64)).ravel())
-
-
-def _close(got, want, rtol):
-    return abs(got - want) <= rtol * max(abs(want), 1e-300)
 
 
 # ---------------------------------------------------------------------------------------------------------- kernels
@@ -141,49 +129,7 @@ def test_cg_direction(ctx, dtype, n3, form):
 # ---------------------------------------------------------------------------------------------------------- solver
 def fcg_restated(n3, rng, v0, f, v1, v2, tol, maxit, nlevels=0, dtype=np.float64):
     """flexible CG of mg_multigrid.h in numpy: A p = -residual(p, 0, CORRECT), M r = the oracle's V-cycle from zero"""
-    def A(p):
-        return -O.residual3d(n3, rng, p, np.zeros_like(p), P.CORRECT, dtype=dtype)
-
-    def M(r):
-        return O.cycle3d(n3, rng, nlevels=nlevels, mode=0, v0=1, v1=v1, v2=v2, v=np.zeros_like(r), f=r, residual_mode=O.CORRECT,
-                         dtype=dtype)
-
-    def dot(a, b):
-        return math.fsum((a.astype(np.float64) * b.astype(np.float64)).ravel())
-
-    x = v0.copy()
-    r = O.residual3d(n3, rng, x, f, P.CORRECT, dtype=dtype)
-    rr0 = dot(r, r)
-    hist, k, restart, conv = [], 0, True, False
-    while k < maxit:
-        if restart:
-            z = M(r)
-            p, rz, restart = z.copy(), dot(r, z), False
-        k += 1
-        q = A(p)
-        alpha = rz / dot(p, q)
-        x = x + dtype(alpha) * p
-        r = r - dtype(alpha) * q
-        rel = math.sqrt(dot(r, r) / rr0)
-        hist.append(rel)
-        if rel < tol:
-            r = O.residual3d(n3, rng, x, f, P.CORRECT, dtype=dtype)
-            if math.sqrt(dot(r, r) / rr0) < tol:
-                conv = True
-                break
-            restart = True
-            continue
-        z = M(r)
-        beta = -alpha * dot(z, q) / rz
-        rz = dot(r, z)
-        p = z + dtype(beta) * p
-    return x, k, np.array(hist), conv
-
-
-def _problem(n3, dtype=np.float64, seed=0):
-    f = np.zeros(O.shape(n3), dtype)
-    _interior(f)[...] = np.random.default_rng(seed).uniform(-1, 1, _interior(f).shape)
-    return f
+    return solve_restated.fcg_restated(n3, rng, v0, f, m_cycle(n3, rng, v1, v2, nlevels, dtype), tol, maxit, dtype)
 
 
 def _mg(ctx, n3, rng, dtype=np.float64, f=None, v=None, **kw):

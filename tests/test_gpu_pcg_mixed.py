@@ -3,7 +3,6 @@
 The kernels are checked against numpy restatements bit for bit (the sums to 1e-13); defect correction against its restatement
 with the oracle's fp32 V-cycle bit for bit (the scale s is a power of two, so M(s r) / s = M(r) and no scale appears in it);
 flexible CG against the flexible CG of test_gpu_pcg.py with that preconditioner."""
-import math
 import os
 import shutil
 import subprocess
@@ -14,8 +13,16 @@ import pytest
 import oracle as O
 import pde_multigrid_amd as P
 from conftest import bits_equal
-from odd_shapes import pack_poisoned, pads_unchanged
-from pde_multigrid_amd.multigrid import xs_unpack
+from odd_shapes import pack_poisoned
+from solve_restated import boundary_mask as _boundary_mask
+from solve_restated import check_out as _check_out
+from solve_restated import close as _close
+from solve_restated import fsum_dot as _fsum_dot
+from solve_restated import interior as _interior
+from solve_restated import ir_restated, m32
+from solve_restated import problem as _problem
+from solve_restated import true_rel as _true_rel
+import solve_restated
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,36 +46,10 @@ def _rand(n3, dtype, seed):
     return np.random.default_rng(seed).uniform(-1, 1, O.shape(n3)).astype(dtype)
 
 
-def _interior(a):
-    return a[1:-1, 1:-1, 1:-1]
-
-
-def _boundary_mask(n3):
-    m = np.ones(O.shape(n3), bool)
-    m[1:-1, 1:-1, 1:-1] = False
-    return m
-
-
-def _fsum_dot(a, b):
-    return math.fsum((_interior(a).astype(np.float64) * _interior(b).astype(np.float64)).ravel())
-
-
-def _close(got, want, rtol):
-    return abs(got - want) <= rtol * max(abs(want), 1e-300)
-
-
 def _on_interior(base, val):
     out = base.copy()
     _interior(out)[...] = _interior(val)
     return out
-
-
-def _check_out(n3, up, got_stored, want, was):
-    """interior = want bit for bit, boundary = was, pads as uploaded"""
-    got = xs_unpack(got_stored, n3[0])
-    assert bits_equal(_interior(got), _interior(want))
-    assert bits_equal(got[_boundary_mask(n3)], was[_boundary_mask(n3)]), "a boundary entry was written"
-    assert pads_unchanged(up, got_stored, n3[0])
 
 
 # ---------------------------------------------------------------------------------------------------------- kernels
@@ -153,12 +134,6 @@ def test_cg_direction_mixed(ctx, n3, form):
 
 
 # ---------------------------------------------------------------------------------------------------------- solver
-def _problem(n3, seed=0):
-    f = np.zeros(O.shape(n3))
-    _interior(f)[...] = np.random.default_rng(seed).uniform(-1, 1, _interior(f).shape)
-    return f
-
-
 def _mg(ctx, n3, rng, f=None, v=None, **kw):
     mg = P.MultiGrid3D(ctx, n3, rng, np.float64, residual_mode=P.CORRECT, **kw)
     mg.upload_v(0, np.zeros(O.shape(n3)) if v is None else v)
@@ -166,70 +141,9 @@ def _mg(ctx, n3, rng, f=None, v=None, **kw):
     return mg
 
 
-def _m32(n3, rng, v1, v2, nlevels=0):
-    """the preconditioner: the oracle's fp32 V-cycle from zero on float32(r), promoted"""
-    def M(r):
-        r32 = r.astype(np.float32)
-        return O.cycle3d(n3, rng, nlevels=nlevels, mode=0, v0=1, v1=v1, v2=v2, v=np.zeros_like(r32), f=r32, residual_mode=O.CORRECT,
-                         dtype=np.float32).astype(np.float64)
-    return M
-
-
-def ir_restated(n3, rng, v0, f, v1, v2, steps, nlevels=0):
-    """defect correction: x after each of `steps` steps x += M(b - A x)"""
-    M = _m32(n3, rng, v1, v2, nlevels)
-    x, out = v0.copy(), []
-    for _ in range(steps):
-        x = x + M(O.residual3d(n3, rng, x, f, P.CORRECT, dtype=np.float64))
-        out.append(x)
-    return out
-
-
 def fcg_restated(n3, rng, v0, f, v1, v2, tol, maxit, nlevels=0):
     """flexible CG of mg_multigrid.h in numpy (test_gpu_pcg.py's) with the fp32 preconditioner"""
-    dtype = np.float64
-
-    def A(p):
-        return -O.residual3d(n3, rng, p, np.zeros_like(p), P.CORRECT, dtype=dtype)
-
-    M = _m32(n3, rng, v1, v2, nlevels)
-
-    def dot(a, b):
-        return math.fsum((a.astype(np.float64) * b.astype(np.float64)).ravel())
-
-    x = v0.copy()
-    r = O.residual3d(n3, rng, x, f, P.CORRECT, dtype=dtype)
-    rr0 = dot(r, r)
-    hist, k, restart, conv = [], 0, True, False
-    while k < maxit:
-        if restart:
-            z = M(r)
-            p, rz, restart = z.copy(), dot(r, z), False
-        k += 1
-        q = A(p)
-        alpha = rz / dot(p, q)
-        x = x + dtype(alpha) * p
-        r = r - dtype(alpha) * q
-        rel = math.sqrt(dot(r, r) / rr0)
-        hist.append(rel)
-        if rel < tol:
-            r = O.residual3d(n3, rng, x, f, P.CORRECT, dtype=dtype)
-            if math.sqrt(dot(r, r) / rr0) < tol:
-                conv = True
-                break
-            restart = True
-            continue
-        z = M(r)
-        beta = -alpha * dot(z, q) / rz
-        rz = dot(r, z)
-        p = z + dtype(beta) * p
-    return x, k, np.array(hist), conv
-
-
-def _true_rel(n3, rng, x, f, v0):
-    r = O.residual3d(n3, rng, x, f, P.CORRECT, dtype=np.float64)
-    r0 = O.residual3d(n3, rng, v0, f, P.CORRECT, dtype=np.float64)
-    return np.linalg.norm(_interior(r)) / np.linalg.norm(_interior(r0))
+    return solve_restated.fcg_restated(n3, rng, v0, f, m32(n3, rng, v1, v2, nlevels), tol, maxit)
 
 
 @pytest.mark.parametrize("case", range(len(GRIDS)))
