@@ -54,6 +54,19 @@ int mg_dist_num_levels_single(int sizeZ_finest, int numGrids, int min_planes);
 int mg_slab_plan(int sizeZ_level, int rank, int nranks, mgSlabPlan* out);
 
 #define MG_MAX_LEVELS 32 /* (int)log2(size-1) of any int size */
+/* Levels of a SEMI-COARSENED 3D hierarchy (mgMultiGrid3D_<r>_create_semi): pure host arithmetic.  At a level with
+ * sizes n, h[d] = (range[2d+1] - range[2d]) / (n[d] - 1) in double; axis d is coarsenable when n[d] >= 5 && n[d] % 4 == 1 (its
+ * coarse size (n[d]-1)/2+1 is then odd and >= 3); hmin = the smallest h[d] over the coarsenable axes; mask[l] (bit 0 = x, 1 = y,
+ * 2 = z) has bit d set when d is coarsenable and h[d] <= 1.5 hmin, and level l + 1 halves those axes and keeps the others.  The
+ * plan ends at the first level without a coarsenable axis (its mask is 0), at max_levels levels when that is > 0, at
+ * MG_MAX_LEVELS in any case.  Finest sizes must be odd and >= 3 (MGX_ERR_SIZE).  A cube of 2^k+1 points with equal spacings
+ * gives the levels of _create: all masks 7, mg_num_grids levels. */
+typedef struct mgSemiPlan {
+    int nlevels;
+    int n[MG_MAX_LEVELS][3];
+    unsigned char mask[MG_MAX_LEVELS]; /* the step from level l to l + 1; 0 on the last level */
+} mgSemiPlan;
+int mg_semi_plan(const int finest[3], const double range[6], int max_levels, mgSemiPlan* out);
 /* use_graph: a captured cycle is replayed only while every host-side input of its launch sequence is what it was at
  * capture time.  Those inputs are serialised (mg_graph_record, csrc/host/mg_common.h) into a fixed-size record of
  * unsigned words, and a replay needs the caller's record to equal the capture's word for word. */
@@ -132,6 +145,9 @@ typedef struct mgGraphFlags {
         /* internal: state of PCG_mixed (fp64 only; NULL until its first call, freed by _destroy): the  */ \
         /* fp32 twin hierarchy that runs the preconditioning V-cycle, and the mixed kernels' scratch     */ \
         void* pcg_mixed;                                                                                 \
+        /* the axes halved between level l and l + 1 (bit 0 = x, 1 = y, 2 = z): 7 on every level but for */ \
+        /* _create_semi, whose masks come from mg_semi_plan.  Fixed at creation.                         */ \
+        unsigned char coarsen[MG_MAX_LEVELS];                                                            \
     } mgMultiGrid3D_##R;                                                                                 \
     int mgMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6],     \
                                    mgMultiGrid3D_##R** out);                                             \
@@ -142,6 +158,11 @@ typedef struct mgGraphFlags {
     int mgMultiGrid3D_##R##_create_levels(mgx_ctx* ctx, const int finestGridSizeXYZ[3],                  \
                                           const real range[6], int layout, int nlevels,                  \
                                           mgMultiGrid3D_##R** out);                                      \
+    /* a semi-coarsened hierarchy: the levels of mg_semi_plan(finest, (double)range, nlevels), always    */ \
+    /* x-split, numGrids = maxGrids = the plan's level count.  Every call above and below works on it;   */ \
+    /* steps whose mask is not 7 run the mgx3dxs_*_axes transfers between the existing smoother calls.   */ \
+    int mgMultiGrid3D_##R##_create_semi(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6], \
+                                        int nlevels, mgMultiGrid3D_##R** out);                           \
     void mgMultiGrid3D_##R##_destroy(mgMultiGrid3D_##R* mg);                                             \
     int mgMultiGrid3D_##R##_InitV(mgMultiGrid3D_##R* mg, int gridID);                                    \
     int mgMultiGrid3D_##R##_InitF(mgMultiGrid3D_##R* mg, int gridID);                                    \

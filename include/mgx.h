@@ -313,6 +313,23 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
                                                  real* coarse_f, const int cn[3]);                      \
     int mgx3dxs_interpolate_correct_##SFX(mgx_ctx* ctx, real* v, const int n[3], const real* coarse_v,  \
                                           const int cn[3]);                                             \
+    /* semi-coarsening (csrc/mgx_semi3d.hip): the same four transfers between levels of   */ \
+    /* which only SOME axes are halved.  The axes are read off the sizes: axis d is kept when cn[d] ==   */ \
+    /* fn[d] and halved when cn[d] == (fn[d]-1)/2+1; anything else, and no axis halved, is              */ \
+    /* MGX_ERR_SIZE; all three halved forwards to the operator above.  One halved axis a: restriction    */ \
+    /* (1/2) C + (1/4)(Ma + Pa); two, a < b: (1/4) C + (1/8)((Ma + Pa) + (Mb + Pb)) + (1/16)((MaMb +      */ \
+    /* PaMb) + (MaPb + PaPb)).  Interpolation over the odd halved axes S: c[]; (1/2)(c[] + c[a]);        */ \
+    /* (1/4)(((c[] + c[a]) + c[b]) + c[a,b]).  restrict_axes injects the coarse boundary;               */ \
+    /* residual_restrict_axes writes it as 0 unless coarse_rim_is_zero != 0 (then it is left alone).    */ \
+    int mgx3dxs_restrict_axes_##SFX(mgx_ctx* ctx, const real* fine, const int fn[3], real* coarse,      \
+                                    const int cn[3]);                                                   \
+    int mgx3dxs_interpolate_axes_##SFX(mgx_ctx* ctx, real* fine, const int fn[3], const real* coarse,   \
+                                       const int cn[3]);                                                \
+    int mgx3dxs_residual_restrict_axes_##SFX(mgx_ctx* ctx, const real* v, const real* f,                \
+                                             const int n[3], const real h[3], int mode, real* coarse_f, \
+                                             const int cn[3], int coarse_rim_is_zero);                  \
+    int mgx3dxs_interpolate_correct_axes_##SFX(mgx_ctx* ctx, real* v, const int n[3],                   \
+                                               const real* coarse_v, const int cn[3]);                  \
     int mgx3dxs_init_f_##SFX(mgx_ctx* ctx, real* f, const int n[3], double c, const double* host_tx,    \
                              const double* host_ty, const double* host_tz);                             \
     int mgx3dxs_jacobi_##SFX(mgx_ctx* ctx, real* v, real* tmp, const real* f, const int n[3],           \

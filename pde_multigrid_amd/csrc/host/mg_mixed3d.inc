@@ -35,7 +35,14 @@ static int mg_mixed3d_twin(mgMultiGrid3D_f64* mg, mgMixed3D** out) {
         const float range[6] = {(float)g->x_a, (float)g->x_b, (float)g->y_a, (float)g->y_b, (float)g->z_a, (float)g->z_b};
         m = (mgMixed3D*)calloc(1, sizeof *m);
         MG_REQUIRE(m, MGX_ERR_NOMEM, "PCG_mixed: out of host memory");
-        int st = mgMultiGrid3D_f32_create_levels(mg->ctx, g->sizeXYZ, range, 1, mg->numGrids, &m->tw);
+        int st;
+        if (semi_below3_f64(mg, 0)) { /* a semi-coarsened hierarchy: its plan copied, not recomputed in float */
+            mgSemiPlan plan;
+            plan_of3_f64(mg, &plan);
+            st = create_plan3_f32(mg->ctx, &plan, range, &m->tw);
+        } else {
+            st = mgMultiGrid3D_f32_create_levels(mg->ctx, g->sizeXYZ, range, 1, mg->numGrids, &m->tw);
+        }
         if (!st && m->tw->maxGrids < mg->numGrids)
             st = mg_fail(MGX_ERR_SIZE, "PCG_mixed: the fp32 twin has %d levels, numGrids is %d", m->tw->maxGrids, mg->numGrids);
         if (!st) st = mgx_malloc(mg->ctx, mgx3dxs_mixed_work_elems_f64(g->sizeXYZ) * sizeof(double), (void**)&m->work);

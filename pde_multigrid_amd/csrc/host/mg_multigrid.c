@@ -6,6 +6,38 @@
 int mg_num_grids(int minSize) { return (int)log2((double)(minSize - 1)); }
 int mg_coarse_size(int size) { return ((size - 1) / 2) + 1; } /* N3/MultiGrid3D.cpp:40-42 */
 
+/* ---- levels of a semi-coarsened hierarchy (mg_multigrid.h) ---- */
+int mg_semi_plan(const int finest[3], const double range[6], int max_levels, mgSemiPlan* out) {
+    if (!finest || !range || !out) return mg_fail(MGX_ERR_INVALID, "mg_semi_plan: NULL argument");
+    for (int d = 0; d < 3; d++) {
+        if (finest[d] < 3 || finest[d] % 2 == 0) return mg_fail(MGX_ERR_SIZE, "mg_semi_plan: size[%d] = %d is not odd and >= 3", d, finest[d]);
+        if (!(range[2 * d + 1] > range[2 * d])) return mg_fail(MGX_ERR_INVALID, "mg_semi_plan: empty range");
+    }
+    memset(out, 0, sizeof *out);
+    const int cap = max_levels > 0 && max_levels < MG_MAX_LEVELS ? max_levels : MG_MAX_LEVELS;
+    int n[3] = {finest[0], finest[1], finest[2]};
+    for (int l = 0;; l++) {
+        for (int d = 0; d < 3; d++) out->n[l][d] = n[d];
+        out->nlevels = l + 1;
+        if (l + 1 >= cap) break;
+        double h[3], hmin = 0.0;
+        int can[3], any = 0;
+        for (int d = 0; d < 3; d++) {
+            h[d] = (range[2 * d + 1] - range[2 * d]) / (double)(n[d] - 1);
+            can[d] = n[d] >= 5 && n[d] % 4 == 1;
+            if (can[d] && (!any || h[d] < hmin)) hmin = h[d];
+            any |= can[d];
+        }
+        if (!any) break;
+        for (int d = 0; d < 3; d++)
+            if (can[d] && h[d] <= 1.5 * hmin) {
+                out->mask[l] |= (unsigned char)(1 << d);
+                n[d] = (n[d] - 1) / 2 + 1;
+            }
+    }
+    return MGX_OK;
+}
+
 /* ---- z-slab plan: pure host arithmetic shared by the product (mg_dist3d.inc) and by the CPU/gloo
  * emulation test (tests/test_dist_gloo.py) ------------------------------------------------------------ */
 int mg_dist_num_levels(int sizeZ_finest, int nranks, int numGrids, int min_planes) {

@@ -118,6 +118,7 @@ int FN(create_levels)(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const REAL r
     mg->smoother = 0;
     mg->omega = (REAL)2 / (REAL)3;
     mg->numGrids = mg->maxGrids = mg_num_grids(minSize); /* :33-34 */
+    memset(mg->coarsen, 7, sizeof mg->coarsen);
     mg->grids3D = (GRID**)calloc((size_t)mg->maxGrids, sizeof(GRID*));
     if (!mg->grids3D) { free(mg); return mg_fail(MGX_ERR_NOMEM, "MultiGrid3D: out of host memory"); }
     int cur[3] = {finestGridSizeXYZ[0], finestGridSizeXYZ[1], finestGridSizeXYZ[2]};
@@ -134,6 +135,58 @@ int FN(create_levels)(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const REAL r
     }
     *out = mg;
     return MGX_OK;
+}
+
+/* the hierarchy of a plan (mg_semi_plan): x-split, one level per plan entry, the plan's masks */
+static int MG_CAT(create_plan3_, R)(mgx_ctx* ctx, const mgSemiPlan* plan, const REAL range[6], MGRID** out) {
+    MG_TRY(mgx_ctx_prepare(ctx));
+    MGRID* mg = (MGRID*)calloc(1, sizeof(MGRID));
+    MG_REQUIRE(mg, MGX_ERR_NOMEM, "MultiGrid3D: out of host memory");
+    mg->ctx = ctx;
+    mg->residual_mode = MGX_RESIDUAL_REF_COMPAT;
+    mg->fuse = 1;
+    mg->layout = 1;
+    mg->smoother = 0;
+    mg->omega = (REAL)2 / (REAL)3;
+    mg->numGrids = mg->maxGrids = plan->nlevels;
+    memset(mg->coarsen, 7, sizeof mg->coarsen);
+    mg->grids3D = (GRID**)calloc((size_t)mg->maxGrids, sizeof(GRID*));
+    if (!mg->grids3D) { free(mg); return mg_fail(MGX_ERR_NOMEM, "MultiGrid3D: out of host memory"); }
+    for (int i = 0; i < mg->maxGrids; i++) {
+        if (i + 1 < mg->maxGrids) mg->coarsen[i] = plan->mask[i];
+        int st = MG_CAT(grid3_new_, R)(ctx, 1, plan->n[i], range, &mg->grids3D[i]);
+        if (!st) st = FN(InitV)(mg, i);
+        if (!st) st = FN(InitF)(mg, i);
+        if (st) { FN(destroy)(mg); return st; }
+    }
+    *out = mg;
+    return MGX_OK;
+}
+
+int FN(create_semi)(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const REAL range[6], int nlevels, MGRID** out) {
+    MG_REQUIRE(ctx && finestGridSizeXYZ && range && out, MGX_ERR_INVALID, "MultiGrid3D: NULL argument");
+    *out = NULL;
+    const double drange[6] = {(double)range[0], (double)range[1], (double)range[2], (double)range[3], (double)range[4], (double)range[5]};
+    mgSemiPlan plan;
+    MG_TRY(mg_semi_plan(finestGridSizeXYZ, drange, nlevels, &plan));
+    return MG_CAT(create_plan3_, R)(ctx, &plan, range, out);
+}
+
+/* the plan a hierarchy was built from */
+static __attribute__((unused)) void MG_CAT(plan_of3_, R)(const MGRID* mg, mgSemiPlan* plan) {
+    memset(plan, 0, sizeof *plan);
+    plan->nlevels = mg->maxGrids;
+    for (int i = 0; i < mg->maxGrids; i++) {
+        for (int d = 0; d < 3; d++) plan->n[i][d] = mg->grids3D[i]->sizeXYZ[d];
+        plan->mask[i] = i + 1 < mg->maxGrids ? mg->coarsen[i] : 0;
+    }
+}
+
+/* is some step of the levels [from, numGrids) not a halving of all three axes? */
+static int MG_CAT(semi_below3_, R)(const MGRID* mg, int from) {
+    for (int i = from; i + 1 < mg->numGrids; i++)
+        if (mg->coarsen[i] != 7) return 1;
+    return 0;
 }
 
 void FN(destroy)(MGRID* mg) {
@@ -169,12 +222,16 @@ int FN(Restrict)(MGRID* mg, const REAL* fine, const int fsizeXYZ[3], REAL* coars
     MG_REQUIRE(mg, MGX_ERR_INVALID, "Restrict: NULL");
     MG_CAT(f_touched3_, R)(mg, coarse); /* boundary = injection of the fine boundary (:113-119) */
     MG_CAT(v_touched3_, R)(mg, coarse);
+    if (mg->layout && fsizeXYZ && csizeXYZ && (fsizeXYZ[0] == csizeXYZ[0] || fsizeXYZ[1] == csizeXYZ[1] || fsizeXYZ[2] == csizeXYZ[2]))
+        return MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ); /* a semi-coarsened step */
     return MGXL(mg, restrict)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ);
 }
 
 int FN(Interpolate)(MGRID* mg, REAL* fine, const int fsizeXYZ[3], const REAL* coarse, const int csizeXYZ[3]) {
     MG_REQUIRE(mg, MGX_ERR_INVALID, "Interpolate: NULL");
     /* interior points only (:202-206): no boundary entry changes */
+    if (mg->layout && fsizeXYZ && csizeXYZ && (fsizeXYZ[0] == csizeXYZ[0] || fsizeXYZ[1] == csizeXYZ[1] || fsizeXYZ[2] == csizeXYZ[2]))
+        return MG_CAT(mgx3dxs_interpolate_axes_, R)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ); /* a semi-coarsened step */
     return MGXL(mg, interpolate)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ);
 }
 
@@ -267,12 +324,39 @@ static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int 
     return mgx_graph_launch(mg->ctx, *slot_exec);
 }
 
+static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero);
+
+/* One level of the cycle whose step to the next level halves only some axes (coarsen[gridID] != 7): the smoother calls of the
+ * other steps around the mgx3dxs_*_axes transfers, nothing fused across them.  Always x-split.  The rim flags as in
+ * vcycle_body3_: the coarse f is written whole (boundary 0), the transfers write no boundary entry of v. */
+static int MG_CAT(vcycle_semi_step3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
+    GRID* fine = mg->grids3D[gridID];
+    GRID* coarse = mg->grids3D[gridID + 1];
+    const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
+    if (v_zero && mg->fuse && mg->smoother == 0 && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
+        if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
+        MG_TRY(MG_CAT(mgx3dxs_relax_from_zero_pp_, R)(mg->ctx, fine->d_v, fine->d_e, fine->d_f, fine->sizeXYZ, h, v1, mg->v_rim_zero[gridID],
+                                                      mg->e_rim_valid[gridID]));
+        if (MG_CAT(mgx3dxs_relax_from_zero_pp_takes_, R)(mg->ctx, fine->sizeXYZ, v1, mg->v_rim_zero[gridID])) mg->e_rim_valid[gridID] = 1;
+        mg->v_rim_zero[gridID] = 1;
+    } else {
+        if (v_zero) MG_TRY(FN(setToValue)(mg, fine->d_v, fine->sizeXYZ, (REAL)0, 1)); /* :634 */
+        MG_TRY(FN(Relax)(mg, fine, v1));                                              /* :626 */
+    }
+    MG_TRY(MG_CAT(mgx3dxs_residual_restrict_axes_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, mg->residual_mode, coarse->d_f,
+                                                      coarse->sizeXYZ, mg->f_rim_zero[gridID + 1])); /* :629-632 */
+    mg->f_rim_zero[gridID + 1] = 1;
+    MG_TRY(MG_CAT(vcycle_body3_, R)(mg, gridID + 1, v1, v2, 1)); /* :634-635 */
+    MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */
+    return FN(Relax)(mg, fine, v2); /* :645 */
+}
+
 /* VCycle from level gridID down.  v_zero: the level's v counts as all zeros (the coarse error of :634) but has not been
  * zeroed in memory yet -- the one-workgroup tail kernel never reads it, the other levels zero it first. */
 static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
     GRID* fine = mg->grids3D[gridID];
     const int nlev = mg->numGrids - gridID;
-    if (mg->fuse && mg->smoother == 0 && nlev <= 6) { /* levels of at most 17^3: the rest of the cycle in ONE launch */
+    if (mg->fuse && mg->smoother == 0 && nlev <= 6 && !MG_CAT(semi_below3_, R)(mg, gridID)) { /* levels of at most 17^3: the rest of the cycle in ONE launch */
         int n[18];
         REAL h[18];
         REAL *v[6], *f[6];
@@ -288,6 +372,7 @@ static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v
             return MGX_OK;
         }
     }
+    if (gridID != mg->numGrids - 1 && mg->coarsen[gridID] != 7) return MG_CAT(vcycle_semi_step3_, R)(mg, gridID, v1, v2, v_zero);
     int down_done = 0;
     if (gridID != mg->numGrids - 1 && mg->fuse && mg->layout && mg->smoother == 0 && v1 > 0 &&
         !MG_CAT(mgx3dxs_relax_pp_takes_, R)(mg->ctx, fine->sizeXYZ, v1)) {

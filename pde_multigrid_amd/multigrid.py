@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import REF_COMPAT, check, lib
+from ._lib import CORRECT, REF_COMPAT, check, lib
 
 
 def _ct(dtype):
@@ -352,6 +352,33 @@ class _Ops3D(_Ops):
         cn = coarse_size(n)
         return self._run(ctx, [v, coarse], lambda a, c: fn(ctx._h, a, _ip(n), c, _ip(cn)), 0, _shape(n), dtype)
 
+    # ---- transfers of a semi-coarsened step (x-split only): cn keeps some axes of n and halves the others
+    def restrict_axes(self, ctx, fine, n, cn, coarse=None, dtype=None):
+        """coarse: the array the call writes into (every point is written; default zeros)"""
+        dtype = dtype or fine.dtype
+        fn, _ = self._fn("restrict_axes", dtype)
+        coarse = np.zeros(_shape(cn), dtype) if coarse is None else coarse
+        return self._run(ctx, [fine, coarse], lambda f, c: fn(ctx._h, f, _ip(n), c, _ip(cn)), 1, _shape(cn), dtype)
+
+    def interpolate_axes(self, ctx, fine, n, coarse, cn, dtype=None):
+        dtype = dtype or fine.dtype
+        fn, _ = self._fn("interpolate_axes", dtype)
+        return self._run(ctx, [fine, coarse], lambda f, c: fn(ctx._h, f, _ip(n), c, _ip(cn)), 0, _shape(n), dtype)
+
+    def residual_restrict_axes(self, ctx, v, f, n, rng, cn, mode=REF_COMPAT, coarse=None, coarse_rim_is_zero=False, dtype=None):
+        """coarse: the array the call writes into (default NaN: the call has to zero the boundary itself)"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("residual_restrict_axes", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        coarse = np.full(_shape(cn), np.nan, dtype) if coarse is None else coarse
+        return self._run(ctx, [v, f, coarse], lambda a, b, c: fn(ctx._h, a, b, _ip(n), h, C.c_int(mode), c, _ip(cn),
+                                                                 C.c_int(int(coarse_rim_is_zero))), 2, _shape(cn), dtype)
+
+    def interpolate_correct_axes(self, ctx, v, n, coarse, cn, dtype=None):
+        dtype = dtype or v.dtype
+        fn, _ = self._fn("interpolate_correct_axes", dtype)
+        return self._run(ctx, [v, coarse], lambda a, c: fn(ctx._h, a, _ip(n), c, _ip(cn)), 0, _shape(n), dtype)
+
     def interpolate_correct_colour(self, ctx, v, n, coarse, colour, dtype=None):
         """x-split only: correct the points with (x+y+z) % 2 == colour (-1 = all)"""
         dtype = dtype or v.dtype
@@ -695,7 +722,7 @@ def _grid3_struct(ct):
                     ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
                     ("pcg_work", C.c_void_p), ("pcg_graph_exec", C.c_void_p), ("pcg_graph_key", C.c_longlong),
                     ("graph_rec", GraphRec * 32), ("graph_post", GraphFlags * 32), ("pcg_graph_rec", GraphRec),
-                    ("pcg_graph_post", GraphFlags), ("pcg_mixed", C.c_void_p)]
+                    ("pcg_graph_post", GraphFlags), ("pcg_mixed", C.c_void_p), ("coarsen", C.c_ubyte * 32)]
 
     return Grid3D, MultiGrid3D
 
@@ -784,17 +811,27 @@ class MultiGrid3D(_MGBase):
     _prefix = "mgMultiGrid3D"
 
     def __init__(self, ctx, finestGridSizeXYZ, rng, dtype=np.float64, nlevels=0, residual_mode=REF_COMPAT, fuse=True,
-                 layout="xsplit"):
+                 layout="xsplit", coarsening="full"):
+        """coarsening="semi": every level halves only the axes with the smallest spacing (semi_plan, mg_multigrid.h) -- the
+        hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count."""
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self._sfx, self._ct = _ct(dtype)
         self._G, self._M = _grid3_struct(self._ct)
         self._mg = C.POINTER(self._M)()
-        fn = getattr(lib, "mgMultiGrid3D_%s_create_levels" % self._sfx)
+        if coarsening not in ("full", "semi"):
+            raise ValueError("coarsening must be 'full' or 'semi', not %r" % (coarsening,))
         lay = {"natural": 0, "xsplit": 1}[layout]
-        check(fn(ctx._h, _ip(finestGridSizeXYZ), _rp(rng, self._ct), C.c_int(lay), C.c_int(int(nlevels)), C.byref(self._mg)))
-        if nlevels:
-            self.numGrids = nlevels
+        if coarsening == "semi":
+            if not lay:
+                raise ValueError("a semi-coarsened hierarchy is always x-split: layout='natural' is not available")
+            fn = getattr(lib, "mgMultiGrid3D_%s_create_semi" % self._sfx)
+            check(fn(ctx._h, _ip(finestGridSizeXYZ), _rp(rng, self._ct), C.c_int(int(nlevels)), C.byref(self._mg)))
+        else:
+            fn = getattr(lib, "mgMultiGrid3D_%s_create_levels" % self._sfx)
+            check(fn(ctx._h, _ip(finestGridSizeXYZ), _rp(rng, self._ct), C.c_int(lay), C.c_int(int(nlevels)), C.byref(self._mg)))
+            if nlevels:
+                self.numGrids = nlevels
         self._mg.contents.residual_mode = int(residual_mode)
         self._mg.contents.fuse = int(bool(fuse))
 
@@ -803,6 +840,12 @@ class MultiGrid3D(_MGBase):
 
     def size(self, gridID):
         return tuple(self.grid(gridID).sizeXYZ)
+
+    @property
+    def masks(self):
+        """the axes halved between level l and l + 1 (bit 0 = x, 1 = y, 2 = z), one entry per level, 0 for the last"""
+        k = self.maxGrids
+        return tuple(int(self._mg.contents.coarsen[l]) if l + 1 < k else 0 for l in range(k))
 
     def Relax(self, gridID, ncycles):
         self._call("Relax", self._mg.contents.grids3D[gridID], C.c_int(ncycles))
@@ -1006,6 +1049,18 @@ class SlabPlan(C.Structure):
                 ("ubeg", C.c_int), ("uend", C.c_int)]
 
 
+class SemiPlan(C.Structure):
+    _fields_ = [("nlevels", C.c_int), ("n", (C.c_int * 3) * 32), ("mask", C.c_ubyte * 32)]
+
+
+def semi_plan(n3, rng, max_levels=0):
+    """mg_semi_plan: (sizes, masks) of the semi-coarsened hierarchy of an n3 = (sx, sy, sz) grid on rng -- one (sx, sy, sz) and
+    one mask (bit 0 = x, 1 = y, 2 = z: the axes halved on the way to the next level; 0 for the last) per level"""
+    p = SemiPlan()
+    check(lib.mg_semi_plan(_ip(n3), _rp(rng, C.c_double), C.c_int(int(max_levels)), C.byref(p)))
+    return [tuple(p.n[l]) for l in range(p.nlevels)], tuple(int(p.mask[l]) for l in range(p.nlevels))
+
+
 def dist_num_levels(sizeZ, nranks, numGrids, min_planes=4):
     return lib.mg_dist_num_levels(int(sizeZ), int(nranks), int(numGrids), int(min_planes))
 
@@ -1191,15 +1246,28 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
     return out
 
 
-def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64"):
+def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full"):
     """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
-    precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG)"""
+    precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG).
+    coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call."""
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
     if precond not in ("f64", "f32"):
         raise ValueError("precond must be 'f64' or 'f32', not %r" % (precond,))
     if precond == "f32" and s != "f64":
         raise ValueError("precond='f32' needs an fp64 grid")
+    if coarsening not in ("full", "semi"):
+        raise ValueError("coarsening must be 'full' or 'semi', not %r" % (coarsening,))
+    if coarsening == "semi":
+        mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening="semi")
+        try:
+            mg.upload_v(0, grid)
+            if rhs is not None:
+                mg.upload_f(0, rhs)
+            it, rel, conv, _ = mg.PCG(v1, v2, tol, maxit, krylov, precond)
+            return mg.download_v(0), it, rel, conv
+        finally:
+            mg.close()
     if precond == "f32":
         s = "mixed_f64"
     r = np.ascontiguousarray(rhs, grid.dtype).ctypes.data_as(C.c_void_p) if rhs is not None else None
