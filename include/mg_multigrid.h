@@ -148,7 +148,21 @@ typedef struct mgGraphFlags {
         /* the axes halved between level l and l + 1 (bit 0 = x, 1 = y, 2 = z): 7 on every level but for */ \
         /* _create_semi, whose masks come from mg_semi_plan.  Fixed at creation.                         */ \
         unsigned char coarsen[MG_MAX_LEVELS];                                                            \
+        /* the shift s >= 0 of the operator (Laplacian - s) u = f (an addition; default 0 = the          */ \
+        /* reference's Poisson problem, and every call then does what it did without this member).       */ \
+        /* Non-zero: Relax, CalculateResidual (ResidualNorm, download_residual), VCycle,                 */ \
+        /* FullMultiGridVCycle and PCG use the shifted operators of mgx.h (mgx3dxs_*_shift) with this s  */ \
+        /* on every level, on full and on semi-coarsened hierarchies: per level relax_shift(_from_zero), */ \
+        /* residual_restrict_shift, the coarser levels, interpolate_correct(_axes), relax_shift -- one   */ \
+        /* launch per colour pass, none of the fused routes.  That needs layout = 1, smoother = 0 and    */ \
+        /* residual_mode = MGX_RESIDUAL_CORRECT (else MGX_ERR_INVALID); PCG_mixed and mgDistMultiGrid3D  */ \
+        /* return MGX_ERR_INVALID on a shifted hierarchy.  Set it through _set_shift, which validates.   */ \
+        /* Appended last: every older member keeps its offset.                                           */ \
+        real shift;                                                                                      \
     } mgMultiGrid3D_##R;                                                                                 \
+    /* shift must be finite and >= 0, and a non-zero one needs the settings named at the member          */ \
+    int mgMultiGrid3D_##R##_set_shift(mgMultiGrid3D_##R* mg, real shift);                                \
+    size_t mgMultiGrid3D_##R##_sizeof(void); /* sizeof(mgMultiGrid3D_<r>): for mirrors of the struct */  \
     int mgMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6],     \
                                    mgMultiGrid3D_##R** out);                                             \
     int mgMultiGrid3D_##R##_create_layout(mgx_ctx* ctx, const int finestGridSizeXYZ[3],                  \
@@ -204,6 +218,19 @@ typedef struct mgGraphFlags {
     int mgMultiGrid3D_##R##_PCG(mgMultiGrid3D_##R* mg, int v1, int v2, double tol, int maxit, int krylov, \
                                 int* iters, double* rel_res, int* converged, double* host_hist,          \
                                 int hist_cap);                                                           \
+    /* BackwardEuler (an addition): nsteps implicit steps of u_t = kappa Laplacian(u) + q on level 0,   */ \
+    /* (I - kappa dt Laplacian) u' = u + dt q, solved as (Laplacian - s) u' = -s u - q / kappa with     */ \
+    /* s = (real)(1 / (kappa dt)).  d_v[0] holds u; its boundary is the Dirichlet data, fixed in time.  */ \
+    /* d_source: q as a device array in the hierarchy's layout, or NULL.  Per step mgx3dxs_shift_rhs    */ \
+    /* writes d_f[0] (qscale = (real)(1 / kappa)) and PCG(v1, v2, tol, maxit, krylov) runs from the      */ \
+    /* guess u.  *iters_total = PCG iterations of all steps, *worst_rel_res = the largest true relative  */ \
+    /* residual of a step; it stops at the first step that does not converge, with *converged = 0.       */ \
+    /* The shift it sets STAYS SET afterwards (and d_f[0] holds the last step's right-hand side).        */ \
+    /* Needs dt > 0, kappa > 0, nsteps >= 0 and the settings of a shifted hierarchy.                     */ \
+    int mgMultiGrid3D_##R##_BackwardEuler(mgMultiGrid3D_##R* mg, int nsteps, double dt, double kappa,    \
+                                          const real* d_source, int v1, int v2, double tol, int maxit,   \
+                                          int krylov, int* iters_total, double* worst_rel_res,           \
+                                          int* converged);                                               \
     /* solve(grid, rhs, nlevels): host arrays in the reference layout; grid = initial guess incl.     */ \
     /* boundary values on input, solution on output; nlevels = 0 -> reference rule; ncycles V(v1,v2)  */ \
     /* cycles from the given guess, or one FullMultiGridVCycle(v0,v1,v2) when fmg != 0.               */ \

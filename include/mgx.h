@@ -512,7 +512,44 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* cg_direction: x += (real)*dev_alpha * p with the old p (skipped when x is NULL), then, unless z  */ \
     /* is NULL, p = z + (real)*dev_beta * p, or p = z when dev_beta is NULL                             */ \
     int mgx3dxs_cg_direction_##SFX(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3],       \
-                                   const double* dev_alpha, const double* dev_beta);
+                                   const double* dev_alpha, const double* dev_beta);                    \
+    /* ---- the shifted operator (Laplacian - s) u = f, s >= 0, x-split layout (csrc/mgx_shift3d.hip) -- */ \
+    /* An addition: the implicit step of diffusion and the screened Poisson equation.  Arithmetic, in   */ \
+    /* `real`, left to right, nothing contracted (hx2 .. = squared spacings, c = the centre value):      */ \
+    /*   smoother  v = num / den, num = the numerator of Relax's point update,                           */ \
+    /*             den = 2*(hy2*hz2 + hx2*hz2 + hx2*hy2) + s*hx2*hy2*hz2                                 */ \
+    /*   residual  r = (the MGX_RESIDUAL_CORRECT residual) + s*c on the interior, 0 on the boundary      */ \
+    /*   operator  q = A p = -(residual of p with f = 0)                                                 */ \
+    /* With s = 0 they give the bits of mgx3dxs_relax / _residual(CORRECT) / _laplace_dot.  Every entry  */ \
+    /* returns MGX_ERR_INVALID unless s is finite and >= 0, MGX_ERR_SIZE for sizes that are not odd and  */ \
+    /* >= 3; pad entries are neither written nor read as data.                                           */ \
+    /* relax_shift: ncycles red-black sweeps in place, one launch per colour; mgx_ctx_last_relax_kernel  */ \
+    /*   names the kernel.  relax_shift_from_zero: the contract of mgx3dxs_relax_from_zero (v counts as  */ \
+    /*   zero; rim_is_zero != 0: its boundary and pad entries are zero in memory, nothing is filled and  */ \
+    /*   the first red pass does not read v).                                                            */ \
+    int mgx3dxs_relax_shift_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], \
+                                  real s, int ncycles);                                                 \
+    int mgx3dxs_relax_shift_from_zero_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3],       \
+                                            const real h[3], real s, int ncycles, int rim_is_zero);     \
+    /* residual_shift: r is stored unless it is NULL; unless dev_sumsq is NULL, *dev_sumsq = the sum of  */ \
+    /*   the squared residuals in double, in a fixed order (the same bits on every run); dev_work:       */ \
+    /*   mgx3dxs_krylov_work_elems doubles (unused without dev_sumsq).  Asynchronous.                    */ \
+    int mgx3dxs_residual_shift_##SFX(mgx_ctx* ctx, const real* v, const real* f, real* r,               \
+                                     const int n[3], const real h[3], real s, double* dev_work,         \
+                                     double* dev_sumsq);                                                \
+    /* residual_restrict_shift: coarse_f = Restrict(residual), the fine residual never stored; cn halves */ \
+    /*   the axes of a mask in 1 .. 7 (as mgx3dxs_residual_restrict_axes reads it off n / cn; 7 = the    */ \
+    /*   reference's full weighting).  The coarse boundary is set to 0 unless coarse_rim_is_zero != 0.   */ \
+    int mgx3dxs_residual_restrict_shift_##SFX(mgx_ctx* ctx, const real* v, const real* f, const int n[3], \
+                                              const real h[3], real s, real* coarse_f, const int cn[3], \
+                                              int coarse_rim_is_zero);                                  \
+    /* laplace_dot_shift: mgx3dxs_laplace_dot's contract with the shifted A                              */ \
+    int mgx3dxs_laplace_dot_shift_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3],           \
+                                        const real h[3], real s, double* dev_work, double* dev_sum);    \
+    /* shift_rhs: f = (-(s*u)) - qscale*q on the interior, f = -(s*u) when q is NULL: the right-hand     */ \
+    /*   side of a backward Euler step.  The boundary and pad entries of f are not written.             */ \
+    int mgx3dxs_shift_rhs_##SFX(mgx_ctx* ctx, const real* u, const real* q, real qscale, real s,        \
+                                real* f, const int n[3]);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)

@@ -769,6 +769,7 @@ int FN(VCycle)(MGRID* mg, int gridID, int v1, int v2) {
     MG_REQUIRE(mg && mg->numGrids >= 1 && mg->numGrids <= mg->maxGrids, MGX_ERR_INVALID, "VCycle: numGrids = %d outside [1,%d]",
                mg ? mg->numGrids : -1, mg ? mg->maxGrids : -1);
     MG_REQUIRE(gridID >= 0 && gridID < mg->numGrids, MGX_ERR_INVALID, "VCycle: bad gridID %d", gridID);
+    MG_REQUIRE(!mg->tail || mg->tail->shift == 0, MGX_ERR_INVALID, "VCycle: a shifted hierarchy is not supported on slabs");
     MG_REQUIRE(v1 >= 0 && v2 >= 0, MGX_ERR_INVALID, "VCycle: negative sweep count");
     if (mg->use_graph && gridID == 0) return MG_CAT(dist_vcycle_graph_, R)(mg, v1, v2);
     MG_TRY(MG_CAT(dist_vcycle_body_, R)(mg, gridID, v1, v2, 0));
@@ -869,6 +870,7 @@ int FN(FullMultiGridVCycle)(MGRID* mg, int gridID, int v0, int v1, int v2) {
     MG_REQUIRE(mg && mg->numGrids >= 1 && mg->numGrids <= mg->maxGrids, MGX_ERR_INVALID, "FMG: numGrids = %d outside [1,%d]",
                mg ? mg->numGrids : -1, mg ? mg->maxGrids : -1);
     MG_REQUIRE(gridID >= 0 && gridID < mg->numGrids, MGX_ERR_INVALID, "FMG: bad gridID %d", gridID);
+    MG_REQUIRE(!mg->tail || mg->tail->shift == 0, MGX_ERR_INVALID, "FMG: a shifted hierarchy is not supported on slabs");
     if (gridID >= mg->numDist) {
         mg->tail->numGrids = mg->numGrids - mg->numDist;
         mg->tail->residual_mode = mg->residual_mode;

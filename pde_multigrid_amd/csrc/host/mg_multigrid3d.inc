@@ -218,6 +218,27 @@ static void MG_CAT(v_touched3_, R)(MGRID* mg, const REAL* dev) {
         }
 }
 
+/* ---------------------------------------------------------------- the shifted operator (Laplacian - shift) u = f */
+/* what a non-zero shift needs of the hierarchy (the members are public: checked where the shift is used, too) */
+static int MG_CAT(shift_ok3_, R)(const MGRID* mg, REAL shift, const char* what) {
+    MG_REQUIRE(isfinite((double)shift) && shift >= 0, MGX_ERR_INVALID, "%s: the shift %g is not finite and >= 0", what, (double)shift);
+    if (shift == 0) return MGX_OK;
+    MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "%s: a shifted hierarchy needs the x-split layout (layout = 1)", what);
+    MG_REQUIRE(mg->smoother == 0, MGX_ERR_INVALID, "%s: a shifted hierarchy needs the red-black smoother (smoother = 0)", what);
+    MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "%s: a shifted hierarchy needs residual_mode = MGX_RESIDUAL_CORRECT",
+               what);
+    return MGX_OK;
+}
+
+int FN(set_shift)(MGRID* mg, REAL shift) {
+    MG_REQUIRE(mg, MGX_ERR_INVALID, "set_shift: NULL");
+    MG_TRY(MG_CAT(shift_ok3_, R)(mg, shift, "set_shift"));
+    mg->shift = shift;
+    return MGX_OK;
+}
+
+size_t FN(sizeof)(void) { return sizeof(MGRID); }
+
 int FN(Restrict)(MGRID* mg, const REAL* fine, const int fsizeXYZ[3], REAL* coarse, const int csizeXYZ[3]) {
     MG_REQUIRE(mg, MGX_ERR_INVALID, "Restrict: NULL");
     MG_CAT(f_touched3_, R)(mg, coarse); /* boundary = injection of the fine boundary (:113-119) */
@@ -241,6 +262,10 @@ int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
     int lvl = -1;
     for (int i = 0; i < mg->maxGrids; i++)
         if (mg->grids3D[i] == curGrid) lvl = i;
+    if (mg->shift != 0) { /* one launch per colour pass; d_e is not used */
+        MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "Relax"));
+        return MG_CAT(mgx3dxs_relax_shift_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles);
+    }
     if (mg->smoother == 1) { /* weighted Jacobi: the error scratch doubles as the ping-pong array */
         if (lvl >= 0) mg->e_rim_valid[lvl] = 0;
         return MGXL(mg, jacobi)(mg->ctx, curGrid->d_v, curGrid->d_e, curGrid->d_f, curGrid->sizeXYZ, h, mg->omega, ncycles);
@@ -271,7 +296,12 @@ int FN(setToValue)(MGRID* mg, REAL* grid, const int sizeXYZ[3], REAL value, int 
 int FN(CalculateResidual)(MGRID* mg, GRID* fine, REAL** residual) {
     MG_REQUIRE(mg && fine && residual, MGX_ERR_INVALID, "CalculateResidual: NULL");
     const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
-    MG_TRY(MGXL(mg, residual)(mg->ctx, fine->d_v, fine->d_f, fine->d_r, fine->sizeXYZ, h, mg->residual_mode));
+    if (mg->shift != 0) {
+        MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "CalculateResidual"));
+        MG_TRY(MG_CAT(mgx3dxs_residual_shift_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_r, fine->sizeXYZ, h, mg->shift, NULL, NULL));
+    } else {
+        MG_TRY(MGXL(mg, residual)(mg->ctx, fine->d_v, fine->d_f, fine->d_r, fine->sizeXYZ, h, mg->residual_mode));
+    }
     *residual = fine->d_r;
     return MGX_OK;
 }
@@ -295,6 +325,7 @@ static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int 
     s.residual_mode = mg->residual_mode; s.fuse = mg->fuse; s.smoother = mg->smoother;
     s.omega_bits = mg_real_bits(&mg->omega, sizeof(REAL));
     s.extra = extra; /* what else the caller's body depends on */
+    s.matrixA_bits[0] = mg_real_bits(&mg->shift, sizeof(REAL)); /* a 3D record has no matrix: the shift's bits (0 without one) */
     MG_TRY(mgx_ctx_generation(mg->ctx, &s.generation));
     for (int k = 0; k < 3; k++)
         for (int i = gridID; i < mg->numGrids; i++) s.flags.a[k][i] = flags[k][i];
@@ -351,9 +382,40 @@ static int MG_CAT(vcycle_semi_step3_, R)(MGRID* mg, int gridID, int v1, int v2, 
     return FN(Relax)(mg, fine, v2); /* :645 */
 }
 
+/* One level of the cycle of the shifted operator (shift != 0), on full and on semi-coarsened steps alike: vcycle_semi_step3_ with
+ * the mgx3dxs_*_shift smoother and residual+restrict around the unshifted transfers (the shift only changes the operator, not how
+ * grids are transferred).  One launch per colour pass: the one-launch tail and the fused routes are not taken.  The rim flags as
+ * in vcycle_semi_step3_; d_e is never used. */
+static int MG_CAT(vcycle_shift_step3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
+    MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "VCycle"));
+    GRID* fine = mg->grids3D[gridID];
+    const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
+    if (v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
+        if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
+        MG_TRY(MG_CAT(mgx3dxs_relax_shift_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, mg->shift, v1, mg->v_rim_zero[gridID]));
+        mg->v_rim_zero[gridID] = 1;
+    } else {
+        if (v_zero) MG_TRY(FN(setToValue)(mg, fine->d_v, fine->sizeXYZ, (REAL)0, 1)); /* :634 */
+        MG_TRY(FN(Relax)(mg, fine, v1));                                              /* :626 */
+    }
+    if (gridID != mg->numGrids - 1) {
+        GRID* coarse = mg->grids3D[gridID + 1];
+        MG_TRY(MG_CAT(mgx3dxs_residual_restrict_shift_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, mg->shift, coarse->d_f,
+                                                           coarse->sizeXYZ, mg->f_rim_zero[gridID + 1])); /* :629-632 */
+        mg->f_rim_zero[gridID + 1] = 1;
+        MG_TRY(MG_CAT(vcycle_body3_, R)(mg, gridID + 1, v1, v2, 1)); /* :634-635 */
+        if (mg->coarsen[gridID] != 7)
+            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ));
+        else
+            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */
+    }
+    return FN(Relax)(mg, fine, v2); /* :645 */
+}
+
 /* VCycle from level gridID down.  v_zero: the level's v counts as all zeros (the coarse error of :634) but has not been
  * zeroed in memory yet -- the one-workgroup tail kernel never reads it, the other levels zero it first. */
 static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
+    if (mg->shift != 0) return MG_CAT(vcycle_shift_step3_, R)(mg, gridID, v1, v2, v_zero);
     GRID* fine = mg->grids3D[gridID];
     const int nlev = mg->numGrids - gridID;
     if (mg->fuse && mg->smoother == 0 && nlev <= 6 && !MG_CAT(semi_below3_, R)(mg, gridID)) { /* levels of at most 17^3: the rest of the cycle in ONE launch */
@@ -589,8 +651,11 @@ static int MG_CAT(pcg_precond3_, R)(MGRID* mg, int v1, int v2) {
 static int MG_CAT(pcg_true_sumsq3_, R)(MGRID* mg, const REAL* x, const REAL* b, double* ss) {
     GRID* g = mg->grids3D[0];
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
-    MG_TRY(MG_CAT(mgx3dxs_residual_sumsq_slab_, R)(mg->ctx, x, b, g->sizeX, g->sizeY, h, MGX_RESIDUAL_CORRECT, 1, g->sizeZ - 1,
-                                                   mg->pcg_state + MGX_CG_RR));
+    if (mg->shift != 0)
+        MG_TRY(MG_CAT(mgx3dxs_residual_shift_, R)(mg->ctx, x, b, NULL, g->sizeXYZ, h, mg->shift, mg->pcg_work, mg->pcg_state + MGX_CG_RR));
+    else
+        MG_TRY(MG_CAT(mgx3dxs_residual_sumsq_slab_, R)(mg->ctx, x, b, g->sizeX, g->sizeY, h, MGX_RESIDUAL_CORRECT, 1, g->sizeZ - 1,
+                                                       mg->pcg_state + MGX_CG_RR));
     return mgx_memcpy_d2h(mg->ctx, ss, mg->pcg_state + MGX_CG_RR, sizeof(double));
 }
 
@@ -657,9 +722,11 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
     double rr0 = 0.0, rr = 0.0;
     int pending = 0; /* x still lacks alpha p of the last iteration */
     /* r = b - A x (0 on the boundary), ||r0|| */
-    st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
+    const REAL shift = mg->shift; /* != 0: the shifted residual (with its sum) and operator */
+    if (shift != 0) st = MG_CAT(mgx3dxs_residual_shift_, R)(ctx, x, b, r, n, h, shift, w, s + MGX_CG_RR);
+    else st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
     mg->f_rim_zero[0] = 0;
-    if (!st) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
+    if (!st && shift == 0) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
     if (!st) st = mgx_memcpy_d2h(ctx, &rr0, s + MGX_CG_RR, sizeof(double));
     if (!st && rr0 == 0.0) *converged = 1;
     int restart = 1; /* z = M r, p = z, rz = <r, z> */
@@ -672,7 +739,8 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
             restart = 0;
         }
         /* q = A p, alpha = <r, z> / <p, q>; r -= alpha q */
-        if (!st) st = MG_CAT(mgx3dxs_laplace_dot_, R)(ctx, p, q, n, h, w, s + MGX_CG_PQ);
+        if (!st && shift != 0) st = MG_CAT(mgx3dxs_laplace_dot_shift_, R)(ctx, p, q, n, h, shift, w, s + MGX_CG_PQ);
+        else if (!st) st = MG_CAT(mgx3dxs_laplace_dot_, R)(ctx, p, q, n, h, w, s + MGX_CG_PQ);
         if (!st) st = mgx_cg_scalars(ctx, s, 0);
         if (!st) st = MG_CAT(mgx3dxs_cg_update_, R)(ctx, NULL, p, r, q, n, s + MGX_CG_ALPHA, w, s + MGX_CG_RR);
         if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double)); /* the one host read of the iteration */
@@ -685,8 +753,9 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
         if (rel < tol) { /* the recursive residual may have drifted from b - A x: check the true one */
             st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL);
             pending = 0;
-            if (!st) st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
-            if (!st) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
+            if (!st && shift != 0) st = MG_CAT(mgx3dxs_residual_shift_, R)(ctx, x, b, r, n, h, shift, w, s + MGX_CG_RR);
+            else if (!st) st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
+            if (!st && shift == 0) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
             if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double));
             if (!st && sqrt(rr / rr0) < tol) *converged = 1;
             restart = 1; /* otherwise go on from the true residual */
@@ -729,12 +798,39 @@ int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* i
     MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "PCG: needs residual_mode = MGX_RESIDUAL_CORRECT");
     MG_REQUIRE(tol > 0 && maxit >= 1 && v1 >= 0 && v2 >= 0 && v1 + v2 >= 1, MGX_ERR_INVALID,
                "PCG: bad arguments (tol %g, maxit %d, v1 %d, v2 %d)", tol, maxit, v1, v2);
+    MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "PCG"));
     *iters = 0;
     *rel_res = 0.0;
     *converged = 0;
     MG_TRY(MG_CAT(pcg_alloc3_, R)(mg));
     if (!krylov) return MG_CAT(pcg_plain3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);
     return MG_CAT(pcg_krylov3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);
+}
+
+/* implicit steps of u_t = kappa Laplacian(u) + q (an addition; mg_multigrid.h) */
+int FN(BackwardEuler)(MGRID* mg, int nsteps, double dt, double kappa, const REAL* d_source, int v1, int v2, double tol, int maxit, int krylov,
+                      int* iters_total, double* worst_rel_res, int* converged) {
+    MG_REQUIRE(mg && iters_total && worst_rel_res && converged, MGX_ERR_INVALID, "BackwardEuler: NULL argument");
+    MG_REQUIRE(nsteps >= 0 && dt > 0 && kappa > 0 && isfinite(dt) && isfinite(kappa), MGX_ERR_INVALID,
+               "BackwardEuler: bad arguments (nsteps %d, dt %g, kappa %g)", nsteps, dt, kappa);
+    const REAL s = (REAL)(1.0 / (kappa * dt)), qscale = (REAL)(1.0 / kappa);
+    MG_REQUIRE(s > 0, MGX_ERR_INVALID, "BackwardEuler: 1 / (kappa dt) = %g is not a positive number of the hierarchy's precision", (double)s);
+    MG_TRY(FN(set_shift)(mg, s)); /* stays set */
+    *iters_total = 0;
+    *worst_rel_res = 0.0;
+    *converged = 1;
+    GRID* g = mg->grids3D[0];
+    for (int k = 0; k < nsteps; k++) {
+        int it = 0, conv = 0;
+        double rel = 0.0;
+        /* interior only: the boundary entries of d_f[0] are read by nobody and stay as they are (f_rim_zero too) */
+        MG_TRY(MG_CAT(mgx3dxs_shift_rhs_, R)(mg->ctx, g->d_v, d_source, qscale, s, g->d_f, g->sizeXYZ));
+        MG_TRY(FN(PCG)(mg, v1, v2, tol, maxit, krylov, &it, &rel, &conv, NULL, 0));
+        *iters_total += it;
+        if (rel > *worst_rel_res || !(rel == rel)) *worst_rel_res = rel;
+        if (!conv) { *converged = 0; break; }
+    }
+    return MGX_OK;
 }
 
 int MG_CAT(mg3d_solve_pcg_, R)(mgx_ctx* ctx, REAL* grid, const REAL* rhs, const int sizeXYZ[3], const REAL range[6], int nlevels, int v1,

@@ -452,6 +452,58 @@ class _Ops3D(_Ops):
         return float(out.value)
 
 
+    # ---- the shifted operator (Laplacian - s) u = f (x-split only, mgx3dxs_*_shift)
+    def relax_shift(self, ctx, v, f, n, rng, s, ncycles, dtype=None):
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_shift", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [v, f], lambda a, b: fn(ctx._h, a, b, _ip(n), h, ct(s), C.c_int(ncycles)), 0, _shape(n), dtype)
+
+    def relax_shift_from_zero(self, ctx, v, f, n, rng, s, ncycles, rim_is_zero, dtype=None):
+        """v := 0, then ncycles sweeps; with rim_is_zero the given v must have zero boundary entries (its interior is ignored)"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_shift_from_zero", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [v, f], lambda a, b: fn(ctx._h, a, b, _ip(n), h, ct(s), C.c_int(ncycles), C.c_int(int(rim_is_zero))), 0,
+                         _shape(n), dtype)
+
+    def residual_shift(self, ctx, v, f, n, rng, s, store=True, want_sum=True, dtype=None):
+        """(r, sum of squares): r None with store=False, the sum None with want_sum=False"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("residual_shift", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        arrays = [xs_pack(np.ascontiguousarray(a, dtype)) for a in (v, f)] + [xs_pack(np.zeros(_shape(n), dtype)) if store else None]
+        (_, _, ro), sums = self._krylov(ctx, n, arrays, [],
+                                        lambda w, s0, a, b, c: fn(ctx._h, a, b, c, _ip(n), h, ct(s), w if want_sum else None,
+                                                                  s0 if want_sum else None), dtype, 1)
+        return (xs_unpack(ro, n[0]) if store else None), (float(sums[0]) if want_sum else None)
+
+    def residual_restrict_shift(self, ctx, v, f, n, rng, s, cn, coarse=None, coarse_rim_is_zero=False, dtype=None):
+        """coarse: the array the call writes into (default NaN: the call has to zero the boundary itself)"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("residual_restrict_shift", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        coarse = np.full(_shape(cn), np.nan, dtype) if coarse is None else coarse
+        return self._run(ctx, [v, f, coarse], lambda a, b, c: fn(ctx._h, a, b, _ip(n), h, ct(s), c, _ip(cn),
+                                                                 C.c_int(int(coarse_rim_is_zero))), 2, _shape(cn), dtype)
+
+    def laplace_dot_shift(self, ctx, p, n, rng, s, q=None, dtype=None):
+        """q = A p with A = Laplacian - s, and <p, q>: returns (q, pq); q: the array written into (default zeros)"""
+        dtype = dtype or p.dtype
+        fn, ct = self._fn("laplace_dot_shift", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        pp = xs_pack(np.ascontiguousarray(p, dtype))
+        qq = np.zeros_like(pp) if q is None else xs_pack(np.ascontiguousarray(q, dtype))
+        (_, qo), sums = self._krylov(ctx, n, [pp, qq], [], lambda w, s0, a, b: fn(ctx._h, a, b, _ip(n), h, ct(s), w, s0), dtype, 1)
+        return xs_unpack(qo, n[0]), float(sums[0])
+
+    def shift_rhs(self, ctx, u, q, qscale, s, n, f=None, dtype=None):
+        """f = (-(s*u)) - qscale*q on the interior (q None: -(s*u)); f: the array written into (default zeros)"""
+        dtype = dtype or u.dtype
+        fn, ct = self._fn("shift_rhs", dtype)
+        f = np.zeros(_shape(n), dtype) if f is None else f
+        return self._run(ctx, [u, q, f], lambda a, b, c: fn(ctx._h, a, b, ct(qscale), ct(s), c, _ip(n)), 2, _shape(n), dtype)
+
     # ---- vector kernels of the preconditioned CG solve (x-split only; every array in the reference layout on the host)
     # every work array is uploaded with WORK_GUARD sentinel doubles behind the elements the library asks for, and the
     # sentinels are looked at after the call: a kernel that writes into the next WORK_GUARD doubles behind its work array
@@ -722,7 +774,7 @@ def _grid3_struct(ct):
                     ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
                     ("pcg_work", C.c_void_p), ("pcg_graph_exec", C.c_void_p), ("pcg_graph_key", C.c_longlong),
                     ("graph_rec", GraphRec * 32), ("graph_post", GraphFlags * 32), ("pcg_graph_rec", GraphRec),
-                    ("pcg_graph_post", GraphFlags), ("pcg_mixed", C.c_void_p), ("coarsen", C.c_ubyte * 32)]
+                    ("pcg_graph_post", GraphFlags), ("pcg_mixed", C.c_void_p), ("coarsen", C.c_ubyte * 32), ("shift", ct)]
 
     return Grid3D, MultiGrid3D
 
@@ -811,9 +863,10 @@ class MultiGrid3D(_MGBase):
     _prefix = "mgMultiGrid3D"
 
     def __init__(self, ctx, finestGridSizeXYZ, rng, dtype=np.float64, nlevels=0, residual_mode=REF_COMPAT, fuse=True,
-                 layout="xsplit", coarsening="full"):
+                 layout="xsplit", coarsening="full", shift=0.0):
         """coarsening="semi": every level halves only the axes with the smallest spacing (semi_plan, mg_multigrid.h) -- the
-        hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count."""
+        hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count.
+        shift = s >= 0: the hierarchy of (Laplacian - s) u = f (the `shift` property)."""
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self._sfx, self._ct = _ct(dtype)
@@ -834,6 +887,43 @@ class MultiGrid3D(_MGBase):
                 self.numGrids = nlevels
         self._mg.contents.residual_mode = int(residual_mode)
         self._mg.contents.fuse = int(bool(fuse))
+        if shift != 0:  # (a NaN too: rejected by the setter)
+            try:
+                self.shift = shift
+            except Exception:
+                self.close()
+                raise
+
+    @property
+    def shift(self):
+        """s >= 0 of the operator (Laplacian - s) u = f every call of the hierarchy works with (0: the Poisson problem).  A non-zero
+        shift needs layout="xsplit", the red-black smoother and residual_mode=CORRECT; PCG(precond="f32") is not available."""
+        return float(self._mg.contents.shift)
+
+    @shift.setter
+    def shift(self, s):
+        self._call("set_shift", self._ct(s))
+
+    def BackwardEuler(self, nsteps, dt, kappa, source=None, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True):
+        """nsteps implicit steps of u_t = kappa Laplacian(u) + q on level 0: v[0] holds u (its boundary = the Dirichlet data, fixed
+        in time), source = q (reference layout) or None.  Every step is one PCG(v1, v2, tol, maxit, krylov) solve of
+        (Laplacian - s) u' = -s u - q / kappa with s = 1 / (kappa dt), which stays set as the hierarchy's shift afterwards.
+        Returns (iterations of all steps, worst true relative residual of a step, converged); it stops at the first step
+        that does not converge."""
+        src = None
+        if source is not None:
+            source = np.ascontiguousarray(source, self.dtype)
+            assert source.shape == _shape(self.size(0))
+            src = self.ctx.to_device(xs_pack(source) if self._mg.contents.layout else source)
+        it, conv = C.c_int(), C.c_int()
+        worst = C.c_double()
+        try:
+            self._call("BackwardEuler", C.c_int(int(nsteps)), C.c_double(dt), C.c_double(kappa), src, C.c_int(v1), C.c_int(v2),
+                       C.c_double(tol), C.c_int(maxit), C.c_int(int(bool(krylov))), C.byref(it), C.byref(worst), C.byref(conv))
+        finally:
+            if src is not None:
+                self.ctx.free(src)
+        return int(it.value), float(worst.value), bool(conv.value)
 
     def grid(self, gridID):
         return self._mg.contents.grids3D[gridID].contents
@@ -1246,10 +1336,12 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
     return out
 
 
-def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full"):
+def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full",
+                shift=0.0):
     """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
     precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG).
-    coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call."""
+    coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call.
+    shift = s > 0: the solve of (Laplacian - s) u = rhs (MultiGrid3D(shift=s)), on a hierarchy built here likewise."""
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
     if precond not in ("f64", "f32"):
@@ -1258,8 +1350,9 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
         raise ValueError("precond='f32' needs an fp64 grid")
     if coarsening not in ("full", "semi"):
         raise ValueError("coarsening must be 'full' or 'semi', not %r" % (coarsening,))
-    if coarsening == "semi":
-        mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening="semi")
+    if coarsening == "semi" or shift != 0:
+        mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening=coarsening,
+                         shift=shift)
         try:
             mg.upload_v(0, grid)
             if rhs is not None:
