@@ -94,7 +94,12 @@ typedef struct mgGraphFlags {
         int sizeXYZ[3];                                                                                  \
         real h_x, h_y, h_z;                                                                              \
         real x_a, x_b, y_a, y_b, z_a, z_b;                                                               \
+        /* device: the coefficient a of div(a grad u) - s u = f at ALL points of the level, or NULL (no */ \
+        /* coefficient: the constant-coefficient operators).  Owned by mgMultiGrid3D_<r>_set_coefficient */ \
+        /* and freed by _destroy.  Appended last: every older member keeps its offset.                   */ \
+        real* d_a;                                                                                       \
     } mgGrid3D_##R;                                                                                      \
+    size_t mgGrid3D_##R##_sizeof(void); /* sizeof(mgGrid3D_<r>): for mirrors of the struct */            \
     typedef struct mgMultiGrid3D_##R {                                                                   \
         mgGrid3D_##R** grids3D;                                                                          \
         int numGrids;    /* public and mutable like the reference's; 1 <= numGrids <= maxGrids */        \
@@ -163,6 +168,26 @@ typedef struct mgGraphFlags {
     /* shift must be finite and >= 0, and a non-zero one needs the settings named at the member          */ \
     int mgMultiGrid3D_##R##_set_shift(mgMultiGrid3D_##R* mg, real shift);                                \
     size_t mgMultiGrid3D_##R##_sizeof(void); /* sizeof(mgMultiGrid3D_<r>): for mirrors of the struct */  \
+    /* The variable-coefficient operator div(a grad u) - shift u = f (an addition; mgx3dxs_*_coef of     */ \
+    /* mgx.h).  host_a: a at all points of level 0, reference layout, every value finite and > 0 (else  */ \
+    /* MGX_ERR_INVALID, and the hierarchy stays as it was).  Level 0 is uploaded and a_{l+1} =          */ \
+    /* Restrict(a_l) down all maxGrids levels with mgx3dxs_restrict (mask 7) / mgx3dxs_restrict_axes:    */ \
+    /* full weighting inside, injection on the boundary, so a stays positive; the operator is           */ \
+    /* re-discretised on every level.  The arrays (one per level, grids3D[l]->d_a) are allocated on the */ \
+    /* first call and reused afterwards.  "Has a coefficient" means grids3D[0]->d_a != NULL: Relax,     */ \
+    /* CalculateResidual (ResidualNorm, download_residual), VCycle, FullMultiGridVCycle, PCG and        */ \
+    /* BackwardEuler (kappa then scales div(a grad u)) then use the _coef kernels with `shift` (0        */ \
+    /* allowed), on full and semi-coarsened hierarchies: per level relax_coef(_from_zero), residual_coef */ \
+    /* into d_r, Restrict into the coarse d_f, the coarser levels, interpolate_correct(_axes),           */ \
+    /* relax_coef -- one launch per colour pass, none of the fused routes.  That needs layout = 1,       */ \
+    /* smoother = 0 and residual_mode = MGX_RESIDUAL_CORRECT (else MGX_ERR_INVALID, here and where it   */ \
+    /* is used); PCG_mixed returns MGX_ERR_INVALID.  host_a == NULL frees the arrays: the hierarchy is  */ \
+    /* what it was without one.  use_graph: level 0's d_a is part of the record, so setting or clearing */ \
+    /* re-captures (allocating or freeing the arrays drops the captured graphs) and new values in the    */ \
+    /* same arrays are read by a replay.  Blocking.                                                      */ \
+    int mgMultiGrid3D_##R##_set_coefficient(mgMultiGrid3D_##R* mg, const real* host_a);                  \
+    /* the coefficient of level gridID as a host array in the reference layout                           */ \
+    int mgMultiGrid3D_##R##_download_coefficient(mgMultiGrid3D_##R* mg, int gridID, real* host);         \
     int mgMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6],     \
                                    mgMultiGrid3D_##R** out);                                             \
     int mgMultiGrid3D_##R##_create_layout(mgx_ctx* ctx, const int finestGridSizeXYZ[3],                  \

@@ -549,7 +549,38 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* shift_rhs: f = (-(s*u)) - qscale*q on the interior, f = -(s*u) when q is NULL: the right-hand     */ \
     /*   side of a backward Euler step.  The boundary and pad entries of f are not written.             */ \
     int mgx3dxs_shift_rhs_##SFX(mgx_ctx* ctx, const real* u, const real* q, real qscale, real s,        \
-                                real* f, const int n[3]);
+                                real* f, const int n[3]);                                               \
+    /* ---- the variable-coefficient operator div(a grad u) - s u = f, a > 0 at the grid nodes, s >= 0, */ \
+    /* x-split layout (csrc/mgx_coef3d.hip).  An addition: heterogeneous diffusion.  a is an array of   */ \
+    /* the level's layout that holds ALL points (interior points next to a face read it on the          */ \
+    /* boundary) and is never written.  Arithmetic, in `real`, left to right, nothing contracted        */ \
+    /* (O/E = x-1/x+1, N/S = y-1/y+1, D/U = z-1/z+1, c the centre, aO .. aU, aC the coefficient there,  */ \
+    /* qx = (real)0.5 / (h[0]*h[0]), likewise qy, qz):                                                  */ \
+    /*   AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC             */ \
+    /*   tx = qx*(AW*(O - c) + AE*(E - c)), ty = qy*(AN*(N - c) + AS*(S - c)),                          */ \
+    /*   tz = qz*(AD*(D - c) + AU*(U - c))                                                              */ \
+    /*   residual  r = (((f - tx) - ty) - tz) + s*c on the interior, 0 on the boundary                  */ \
+    /*   operator  q = A p = -(residual of p with f = 0)                                                */ \
+    /*   smoother  v = num / den, den = ((qx*(AW + AE) + qy*(AN + AS)) + qz*(AD + AU)) + s,             */ \
+    /*             num = ((qx*(AW*O + AE*E) + qy*(AN*N + AS*S)) + qz*(AD*D + AU*U)) - f                 */ \
+    /* Every entry returns MGX_ERR_INVALID for NULL arguments or an s that is not finite and >= 0,      */ \
+    /* MGX_ERR_SIZE for sizes that are not odd and >= 3; pad entries are neither written nor read as    */ \
+    /* data.  The values of a are not checked here (mgMultiGrid3D_<r>_set_coefficient does).            */ \
+    /* relax_coef / relax_coef_from_zero: the contracts of relax_shift / relax_shift_from_zero (with    */ \
+    /*   rim_is_zero the first red pass reads f and a only); mgx_ctx_last_relax_kernel names            */ \
+    /*   relax_coef3d_xs_kernel.  residual_coef: residual_shift's contract (r and / or the sum of       */ \
+    /*   squares).  apply_coef_dot: laplace_dot_shift's contract (q = A p on the interior, <p, q>).     */ \
+    int mgx3dxs_relax_coef_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3],   \
+                                 const real h[3], real s, int ncycles);                                 \
+    int mgx3dxs_relax_coef_from_zero_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,         \
+                                           const int n[3], const real h[3], real s, int ncycles,        \
+                                           int rim_is_zero);                                            \
+    int mgx3dxs_residual_coef_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, \
+                                    const int n[3], const real h[3], real s, double* dev_work,          \
+                                    double* dev_sumsq);                                                 \
+    int mgx3dxs_apply_coef_dot_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q,               \
+                                     const int n[3], const real h[3], real s, double* dev_work,         \
+                                     double* dev_sum);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)

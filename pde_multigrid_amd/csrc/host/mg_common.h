@@ -3,6 +3,7 @@
 #define MG_COMMON_H
 #include <math.h>
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

@@ -55,6 +55,7 @@ static int MG_CAT(grid3_new_, R)(mgx_ctx* ctx, int layout, const int sizeXYZ[3],
 static void MG_CAT(grid3_free_, R)(mgx_ctx* ctx, GRID* g) {
     if (!g) return;
     mgx_free(ctx, g->d_v); mgx_free(ctx, g->d_f); mgx_free(ctx, g->d_r); mgx_free(ctx, g->d_e);
+    mgx_free(ctx, g->d_a);
     free(g->h_v); free(g->h_f);
     free(g);
 }
@@ -238,6 +239,92 @@ int FN(set_shift)(MGRID* mg, REAL shift) {
 }
 
 size_t FN(sizeof)(void) { return sizeof(MGRID); }
+size_t MG_CAT3(mgGrid3D_, R, _sizeof)(void) { return sizeof(GRID); }
+
+/* ---------------------------------------------------------------- the variable-coefficient operator div(a grad u) - shift u = f */
+/* "this hierarchy has a coefficient": level 0 holds one (set_coefficient allocates every level or none) */
+static int MG_CAT(has_coef3_, R)(const MGRID* mg) { return mg->grids3D && mg->grids3D[0] && mg->grids3D[0]->d_a != NULL; }
+
+/* what a coefficient needs of the hierarchy (the members are public: checked where the coefficient is used, too) */
+static int MG_CAT(coef_ok3_, R)(const MGRID* mg, const char* what) {
+    MG_REQUIRE(isfinite((double)mg->shift) && mg->shift >= 0, MGX_ERR_INVALID, "%s: the shift %g is not finite and >= 0", what, (double)mg->shift);
+    MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "%s: a hierarchy with a coefficient needs the x-split layout (layout = 1)", what);
+    MG_REQUIRE(mg->smoother == 0, MGX_ERR_INVALID, "%s: a hierarchy with a coefficient needs the red-black smoother (smoother = 0)", what);
+    MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID,
+               "%s: a hierarchy with a coefficient needs residual_mode = MGX_RESIDUAL_CORRECT", what);
+    for (int i = 0; i < mg->maxGrids; i++)
+        MG_REQUIRE(mg->grids3D[i]->d_a, MGX_ERR_INVALID, "%s: level %d has no coefficient array (set it through _set_coefficient)", what, i);
+    return MGX_OK;
+}
+
+/* The captured graphs hold the d_a pointers of every level, their records only level 0's: whenever the arrays are allocated or
+ * freed the graphs are dropped, so that no replay can meet arrays other than those of its capture. */
+static void MG_CAT(coef_drop_graphs3_, R)(MGRID* mg) {
+    for (int i = 0; i < MG_MAX_LEVELS; i++) {
+        if (mg->graph_exec[i]) mgx_graph_destroy(mg->ctx, mg->graph_exec[i]);
+        mg->graph_exec[i] = NULL;
+    }
+    if (mg->pcg_graph_exec) mgx_graph_destroy(mg->ctx, mg->pcg_graph_exec);
+    mg->pcg_graph_exec = NULL;
+}
+
+static void MG_CAT(coef_free3_, R)(MGRID* mg) {
+    MG_CAT(coef_drop_graphs3_, R)(mg);
+    for (int i = 0; i < mg->maxGrids; i++) {
+        mgx_free(mg->ctx, mg->grids3D[i]->d_a);
+        mg->grids3D[i]->d_a = NULL;
+    }
+}
+
+static int MG_CAT(put3_, R)(MGRID* mg, GRID* g, REAL* dev, const REAL* host);
+static int MG_CAT(get3_, R)(MGRID* mg, GRID* g, const REAL* dev, REAL* host);
+
+int FN(set_coefficient)(MGRID* mg, const REAL* host_a) {
+    MG_REQUIRE(mg && mg->grids3D && mg->maxGrids >= 1, MGX_ERR_INVALID, "set_coefficient: NULL");
+    if (!host_a) { /* back to the constant-coefficient operators */
+        MG_TRY(mgx_ctx_sync(mg->ctx));
+        MG_CAT(coef_free3_, R)(mg);
+        return MGX_OK;
+    }
+    MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "set_coefficient: a hierarchy with a coefficient needs the x-split layout (layout = 1)");
+    MG_REQUIRE(mg->smoother == 0, MGX_ERR_INVALID, "set_coefficient: a hierarchy with a coefficient needs the red-black smoother (smoother = 0)");
+    MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID,
+               "set_coefficient: a hierarchy with a coefficient needs residual_mode = MGX_RESIDUAL_CORRECT");
+    const size_t vol = MG_CAT(vol3_, R)(mg->grids3D[0]);
+    for (size_t i = 0; i < vol; i++)
+        MG_REQUIRE(isfinite((double)host_a[i]) && host_a[i] > 0, MGX_ERR_INVALID, "set_coefficient: a[%zu] = %g is not finite and > 0", i,
+                   (double)host_a[i]);
+    const int had = MG_CAT(has_coef3_, R)(mg);
+    int st = MGX_OK;
+    if (!had) { /* (nothing of a captured cycle is in flight any more) */
+        MG_TRY(mgx_ctx_sync(mg->ctx));
+        MG_CAT(coef_drop_graphs3_, R)(mg);
+    }
+    for (int i = 0; !st && i < mg->maxGrids; i++) { /* first use: one array per level, pads zero */
+        GRID* g = mg->grids3D[i];
+        if (g->d_a) continue;
+        const size_t bytes = MG_CAT(dvol3_, R)(mg->layout, g) * sizeof(REAL);
+        st = mgx_malloc(mg->ctx, bytes, (void**)&g->d_a);
+        if (!st) st = mgx_memset_zero(mg->ctx, g->d_a, bytes);
+    }
+    if (!st) st = MG_CAT(put3_, R)(mg, mg->grids3D[0], mg->grids3D[0]->d_a, host_a);
+    for (int i = 0; !st && i + 1 < mg->maxGrids; i++) { /* a_{l+1} = Restrict(a_l) by the step's mask */
+        GRID *fine = mg->grids3D[i], *coarse = mg->grids3D[i + 1];
+        if (mg->coarsen[i] != 7) st = MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, fine->d_a, fine->sizeXYZ, coarse->d_a, coarse->sizeXYZ);
+        else st = MG_CAT(mgx3dxs_restrict_, R)(mg->ctx, fine->d_a, fine->sizeXYZ, coarse->d_a, coarse->sizeXYZ);
+    }
+    if (!st) st = mgx_ctx_sync(mg->ctx);
+    if (st && !had) MG_CAT(coef_free3_, R)(mg); /* nothing half-built stays behind */
+    return st;
+}
+
+int FN(download_coefficient)(MGRID* mg, int gridID, REAL* host) {
+    MG_REQUIRE(mg && gridID >= 0 && gridID < mg->maxGrids, MGX_ERR_INVALID, "download_coefficient: bad gridID %d", gridID);
+    MG_REQUIRE(host, MGX_ERR_INVALID, "download_coefficient: NULL");
+    GRID* g = mg->grids3D[gridID];
+    MG_REQUIRE(g->d_a, MGX_ERR_INVALID, "download_coefficient: the hierarchy has no coefficient");
+    return MG_CAT(get3_, R)(mg, g, g->d_a, host);
+}
 
 int FN(Restrict)(MGRID* mg, const REAL* fine, const int fsizeXYZ[3], REAL* coarse, const int csizeXYZ[3]) {
     MG_REQUIRE(mg, MGX_ERR_INVALID, "Restrict: NULL");
@@ -262,6 +349,11 @@ int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
     int lvl = -1;
     for (int i = 0; i < mg->maxGrids; i++)
         if (mg->grids3D[i] == curGrid) lvl = i;
+    if (MG_CAT(has_coef3_, R)(mg)) { /* one launch per colour pass; d_e is not used */
+        MG_TRY(MG_CAT(coef_ok3_, R)(mg, "Relax"));
+        MG_REQUIRE(curGrid->d_a, MGX_ERR_INVALID, "Relax: the grid has no coefficient array");
+        return MG_CAT(mgx3dxs_relax_coef_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift, ncycles);
+    }
     if (mg->shift != 0) { /* one launch per colour pass; d_e is not used */
         MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "Relax"));
         return MG_CAT(mgx3dxs_relax_shift_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles);
@@ -296,7 +388,11 @@ int FN(setToValue)(MGRID* mg, REAL* grid, const int sizeXYZ[3], REAL value, int 
 int FN(CalculateResidual)(MGRID* mg, GRID* fine, REAL** residual) {
     MG_REQUIRE(mg && fine && residual, MGX_ERR_INVALID, "CalculateResidual: NULL");
     const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
-    if (mg->shift != 0) {
+    if (MG_CAT(has_coef3_, R)(mg)) {
+        MG_TRY(MG_CAT(coef_ok3_, R)(mg, "CalculateResidual"));
+        MG_REQUIRE(fine->d_a, MGX_ERR_INVALID, "CalculateResidual: the grid has no coefficient array");
+        MG_TRY(MG_CAT(mgx3dxs_residual_coef_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->d_r, fine->sizeXYZ, h, mg->shift, NULL, NULL));
+    } else if (mg->shift != 0) {
         MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "CalculateResidual"));
         MG_TRY(MG_CAT(mgx3dxs_residual_shift_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_r, fine->sizeXYZ, h, mg->shift, NULL, NULL));
     } else {
@@ -326,6 +422,8 @@ static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int 
     s.omega_bits = mg_real_bits(&mg->omega, sizeof(REAL));
     s.extra = extra; /* what else the caller's body depends on */
     s.matrixA_bits[0] = mg_real_bits(&mg->shift, sizeof(REAL)); /* a 3D record has no matrix: the shift's bits (0 without one) */
+    s.matrixA_bits[1] = (unsigned long long)(uintptr_t)mg->grids3D[0]->d_a; /* level 0's coefficient array (0 without one): setting or */
+                                                                            /* clearing it captures again, new values in it are read  */
     MG_TRY(mgx_ctx_generation(mg->ctx, &s.generation));
     for (int k = 0; k < 3; k++)
         for (int i = gridID; i < mg->numGrids; i++) s.flags.a[k][i] = flags[k][i];
@@ -412,9 +510,45 @@ static int MG_CAT(vcycle_shift_step3_, R)(MGRID* mg, int gridID, int v1, int v2,
     return FN(Relax)(mg, fine, v2); /* :645 */
 }
 
+/* One level of the cycle of the variable-coefficient operator, on full and on semi-coarsened steps alike: vcycle_shift_step3_
+ * with the mgx3dxs_*_coef smoother, and the residual stored into d_r and restricted by the existing transfers (no fused
+ * residual+restrict).  One launch per colour pass: the one-launch tail and the fused routes are not taken.  The rim flags as in
+ * vcycle_shift_step3_ (Restrict writes the coarse f whole: its boundary is the injected boundary of r, 0); d_e is never used. */
+static int MG_CAT(vcycle_coef_step3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
+    MG_TRY(MG_CAT(coef_ok3_, R)(mg, "VCycle"));
+    GRID* fine = mg->grids3D[gridID];
+    const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
+    if (v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
+        if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
+        MG_TRY(MG_CAT(mgx3dxs_relax_coef_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->sizeXYZ, h, mg->shift, v1,
+                                                        mg->v_rim_zero[gridID]));
+        mg->v_rim_zero[gridID] = 1;
+    } else {
+        if (v_zero) MG_TRY(FN(setToValue)(mg, fine->d_v, fine->sizeXYZ, (REAL)0, 1)); /* :634 */
+        MG_TRY(FN(Relax)(mg, fine, v1));                                              /* :626 */
+    }
+    if (gridID != mg->numGrids - 1) {
+        GRID* coarse = mg->grids3D[gridID + 1];
+        MG_TRY(MG_CAT(mgx3dxs_residual_coef_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->d_r, fine->sizeXYZ, h, mg->shift, NULL,
+                                                 NULL)); /* :629 */
+        if (mg->coarsen[gridID] != 7)
+            MG_TRY(MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ));
+        else
+            MG_TRY(MG_CAT(mgx3dxs_restrict_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ)); /* :632 */
+        mg->f_rim_zero[gridID + 1] = 1;
+        MG_TRY(MG_CAT(vcycle_body3_, R)(mg, gridID + 1, v1, v2, 1)); /* :634-635 */
+        if (mg->coarsen[gridID] != 7)
+            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ));
+        else
+            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */
+    }
+    return FN(Relax)(mg, fine, v2); /* :645 */
+}
+
 /* VCycle from level gridID down.  v_zero: the level's v counts as all zeros (the coarse error of :634) but has not been
  * zeroed in memory yet -- the one-workgroup tail kernel never reads it, the other levels zero it first. */
 static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
+    if (MG_CAT(has_coef3_, R)(mg)) return MG_CAT(vcycle_coef_step3_, R)(mg, gridID, v1, v2, v_zero);
     if (mg->shift != 0) return MG_CAT(vcycle_shift_step3_, R)(mg, gridID, v1, v2, v_zero);
     GRID* fine = mg->grids3D[gridID];
     const int nlev = mg->numGrids - gridID;
@@ -651,7 +785,9 @@ static int MG_CAT(pcg_precond3_, R)(MGRID* mg, int v1, int v2) {
 static int MG_CAT(pcg_true_sumsq3_, R)(MGRID* mg, const REAL* x, const REAL* b, double* ss) {
     GRID* g = mg->grids3D[0];
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
-    if (mg->shift != 0)
+    if (g->d_a)
+        MG_TRY(MG_CAT(mgx3dxs_residual_coef_, R)(mg->ctx, x, b, g->d_a, NULL, g->sizeXYZ, h, mg->shift, mg->pcg_work, mg->pcg_state + MGX_CG_RR));
+    else if (mg->shift != 0)
         MG_TRY(MG_CAT(mgx3dxs_residual_shift_, R)(mg->ctx, x, b, NULL, g->sizeXYZ, h, mg->shift, mg->pcg_work, mg->pcg_state + MGX_CG_RR));
     else
         MG_TRY(MG_CAT(mgx3dxs_residual_sumsq_slab_, R)(mg->ctx, x, b, g->sizeX, g->sizeY, h, MGX_RESIDUAL_CORRECT, 1, g->sizeZ - 1,
@@ -723,10 +859,12 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
     int pending = 0; /* x still lacks alpha p of the last iteration */
     /* r = b - A x (0 on the boundary), ||r0|| */
     const REAL shift = mg->shift; /* != 0: the shifted residual (with its sum) and operator */
-    if (shift != 0) st = MG_CAT(mgx3dxs_residual_shift_, R)(ctx, x, b, r, n, h, shift, w, s + MGX_CG_RR);
+    const REAL* ca = g->d_a;      /* != NULL: the variable-coefficient residual (with its sum) and operator, with any shift */
+    if (ca) st = MG_CAT(mgx3dxs_residual_coef_, R)(ctx, x, b, ca, r, n, h, shift, w, s + MGX_CG_RR);
+    else if (shift != 0) st = MG_CAT(mgx3dxs_residual_shift_, R)(ctx, x, b, r, n, h, shift, w, s + MGX_CG_RR);
     else st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
     mg->f_rim_zero[0] = 0;
-    if (!st && shift == 0) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
+    if (!st && !ca && shift == 0) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
     if (!st) st = mgx_memcpy_d2h(ctx, &rr0, s + MGX_CG_RR, sizeof(double));
     if (!st && rr0 == 0.0) *converged = 1;
     int restart = 1; /* z = M r, p = z, rz = <r, z> */
@@ -739,7 +877,8 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
             restart = 0;
         }
         /* q = A p, alpha = <r, z> / <p, q>; r -= alpha q */
-        if (!st && shift != 0) st = MG_CAT(mgx3dxs_laplace_dot_shift_, R)(ctx, p, q, n, h, shift, w, s + MGX_CG_PQ);
+        if (!st && ca) st = MG_CAT(mgx3dxs_apply_coef_dot_, R)(ctx, p, ca, q, n, h, shift, w, s + MGX_CG_PQ);
+        else if (!st && shift != 0) st = MG_CAT(mgx3dxs_laplace_dot_shift_, R)(ctx, p, q, n, h, shift, w, s + MGX_CG_PQ);
         else if (!st) st = MG_CAT(mgx3dxs_laplace_dot_, R)(ctx, p, q, n, h, w, s + MGX_CG_PQ);
         if (!st) st = mgx_cg_scalars(ctx, s, 0);
         if (!st) st = MG_CAT(mgx3dxs_cg_update_, R)(ctx, NULL, p, r, q, n, s + MGX_CG_ALPHA, w, s + MGX_CG_RR);
@@ -753,9 +892,10 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
         if (rel < tol) { /* the recursive residual may have drifted from b - A x: check the true one */
             st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL);
             pending = 0;
-            if (!st && shift != 0) st = MG_CAT(mgx3dxs_residual_shift_, R)(ctx, x, b, r, n, h, shift, w, s + MGX_CG_RR);
+            if (!st && ca) st = MG_CAT(mgx3dxs_residual_coef_, R)(ctx, x, b, ca, r, n, h, shift, w, s + MGX_CG_RR);
+            else if (!st && shift != 0) st = MG_CAT(mgx3dxs_residual_shift_, R)(ctx, x, b, r, n, h, shift, w, s + MGX_CG_RR);
             else if (!st) st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
-            if (!st && shift == 0) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
+            if (!st && !ca && shift == 0) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
             if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double));
             if (!st && sqrt(rr / rr0) < tol) *converged = 1;
             restart = 1; /* otherwise go on from the true residual */
@@ -799,6 +939,7 @@ int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* i
     MG_REQUIRE(tol > 0 && maxit >= 1 && v1 >= 0 && v2 >= 0 && v1 + v2 >= 1, MGX_ERR_INVALID,
                "PCG: bad arguments (tol %g, maxit %d, v1 %d, v2 %d)", tol, maxit, v1, v2);
     MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "PCG"));
+    if (MG_CAT(has_coef3_, R)(mg)) MG_TRY(MG_CAT(coef_ok3_, R)(mg, "PCG"));
     *iters = 0;
     *rel_res = 0.0;
     *converged = 0;

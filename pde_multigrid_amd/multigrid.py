@@ -504,6 +504,42 @@ class _Ops3D(_Ops):
         f = np.zeros(_shape(n), dtype) if f is None else f
         return self._run(ctx, [u, q, f], lambda a, b, c: fn(ctx._h, a, b, ct(qscale), ct(s), c, _ip(n)), 2, _shape(n), dtype)
 
+    # ---- the variable-coefficient operator div(a grad u) - s u = f (x-split only, mgx3dxs_*_coef); a holds all points
+    def relax_coef(self, ctx, v, f, a, n, rng, s, ncycles, dtype=None):
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_coef", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [v, f, a], lambda x, b, c: fn(ctx._h, x, b, c, _ip(n), h, ct(s), C.c_int(ncycles)), 0, _shape(n), dtype)
+
+    def relax_coef_from_zero(self, ctx, v, f, a, n, rng, s, ncycles, rim_is_zero, dtype=None):
+        """v := 0, then ncycles sweeps; with rim_is_zero the given v must have zero boundary entries (its interior is ignored)"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_coef_from_zero", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [v, f, a], lambda x, b, c: fn(ctx._h, x, b, c, _ip(n), h, ct(s), C.c_int(ncycles), C.c_int(int(rim_is_zero))), 0,
+                         _shape(n), dtype)
+
+    def residual_coef(self, ctx, v, f, a, n, rng, s, store=True, want_sum=True, dtype=None):
+        """(r, sum of squares): r None with store=False, the sum None with want_sum=False"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("residual_coef", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        arrays = [xs_pack(np.ascontiguousarray(x, dtype)) for x in (v, f, a)] + [xs_pack(np.zeros(_shape(n), dtype)) if store else None]
+        (_, _, _, ro), sums = self._krylov(ctx, n, arrays, [],
+                                           lambda w, s0, x, b, c, d: fn(ctx._h, x, b, c, d, _ip(n), h, ct(s), w if want_sum else None,
+                                                                        s0 if want_sum else None), dtype, 1)
+        return (xs_unpack(ro, n[0]) if store else None), (float(sums[0]) if want_sum else None)
+
+    def apply_coef_dot(self, ctx, p, a, n, rng, s, q=None, dtype=None):
+        """q = A p with A = div(a grad .) - s, and <p, q>: returns (q, pq); q: the array written into (default zeros)"""
+        dtype = dtype or p.dtype
+        fn, ct = self._fn("apply_coef_dot", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        pp, aa = xs_pack(np.ascontiguousarray(p, dtype)), xs_pack(np.ascontiguousarray(a, dtype))
+        qq = np.zeros_like(pp) if q is None else xs_pack(np.ascontiguousarray(q, dtype))
+        (_, _, qo), sums = self._krylov(ctx, n, [pp, aa, qq], [], lambda w, s0, x, c, b: fn(ctx._h, x, c, b, _ip(n), h, ct(s), w, s0), dtype, 1)
+        return xs_unpack(qo, n[0]), float(sums[0])
+
     # ---- vector kernels of the preconditioned CG solve (x-split only; every array in the reference layout on the host)
     # every work array is uploaded with WORK_GUARD sentinel doubles behind the elements the library asks for, and the
     # sentinels are looked at after the call: a kernel that writes into the next WORK_GUARD doubles behind its work array
@@ -763,7 +799,7 @@ def _grid3_struct(ct):
         _fields_ = [("h_v", C.c_void_p), ("h_f", C.c_void_p), ("d_v", C.c_void_p), ("d_f", C.c_void_p),
                     ("d_r", C.c_void_p), ("d_e", C.c_void_p), ("sizeX", C.c_int), ("sizeY", C.c_int), ("sizeZ", C.c_int),
                     ("sizeXYZ", C.c_int * 3), ("h_x", ct), ("h_y", ct), ("h_z", ct), ("x_a", ct), ("x_b", ct),
-                    ("y_a", ct), ("y_b", ct), ("z_a", ct), ("z_b", ct)]
+                    ("y_a", ct), ("y_b", ct), ("z_a", ct), ("z_b", ct), ("d_a", C.c_void_p)]
 
     class MultiGrid3D(C.Structure):
         _fields_ = [("grids3D", C.POINTER(C.POINTER(Grid3D))), ("numGrids", C.c_int), ("maxGrids", C.c_int),
@@ -863,10 +899,11 @@ class MultiGrid3D(_MGBase):
     _prefix = "mgMultiGrid3D"
 
     def __init__(self, ctx, finestGridSizeXYZ, rng, dtype=np.float64, nlevels=0, residual_mode=REF_COMPAT, fuse=True,
-                 layout="xsplit", coarsening="full", shift=0.0):
+                 layout="xsplit", coarsening="full", shift=0.0, coefficient=None):
         """coarsening="semi": every level halves only the axes with the smallest spacing (semi_plan, mg_multigrid.h) -- the
         hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count.
-        shift = s >= 0: the hierarchy of (Laplacian - s) u = f (the `shift` property)."""
+        shift = s >= 0: the hierarchy of (Laplacian - s) u = f (the `shift` property).
+        coefficient = a > 0 at every point of the finest grid: the hierarchy of div(a grad u) - s u = f (set_coefficient)."""
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self._sfx, self._ct = _ct(dtype)
@@ -893,6 +930,34 @@ class MultiGrid3D(_MGBase):
             except Exception:
                 self.close()
                 raise
+        if coefficient is not None:
+            try:
+                self.set_coefficient(coefficient)
+            except Exception:
+                self.close()
+                raise
+
+    def set_coefficient(self, a):
+        """a: the coefficient of div(a grad u) - shift u = f at ALL points of level 0 (reference layout, finite and > 0), restricted
+        down the levels by the hierarchy's own transfers; every call then works with that operator (needs layout="xsplit", the
+        red-black smoother and residual_mode=CORRECT; PCG(precond="f32") is not available).  None: back to the constant-coefficient
+        operators.  New values replace the old ones in the same device arrays."""
+        if a is None:
+            self._call("set_coefficient", None)
+            return
+        a = np.ascontiguousarray(a, self.dtype)
+        if a.shape != _shape(self.size(0)):
+            raise ValueError("the coefficient has shape %r, level 0 has %r" % (a.shape, _shape(self.size(0))))
+        self._call("set_coefficient", a.ctypes.data_as(C.c_void_p))
+
+    @property
+    def has_coefficient(self):
+        return bool(self.grid(0).d_a)
+
+    def download_coefficient(self, gridID=0):
+        out = np.empty(_shape(self.size(gridID)), self.dtype)
+        self._call("download_coefficient", C.c_int(gridID), out.ctypes.data_as(C.c_void_p))
+        return out
 
     @property
     def shift(self):
@@ -1337,11 +1402,12 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
 
 
 def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full",
-                shift=0.0):
+                shift=0.0, coefficient=None):
     """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
     precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG).
     coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call.
-    shift = s > 0: the solve of (Laplacian - s) u = rhs (MultiGrid3D(shift=s)), on a hierarchy built here likewise."""
+    shift = s > 0: the solve of (Laplacian - s) u = rhs (MultiGrid3D(shift=s)), on a hierarchy built here likewise.
+    coefficient = a > 0 at every point: the solve of div(a grad u) - shift u = rhs (MultiGrid3D(coefficient=a)), likewise."""
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
     if precond not in ("f64", "f32"):
@@ -1350,9 +1416,9 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
         raise ValueError("precond='f32' needs an fp64 grid")
     if coarsening not in ("full", "semi"):
         raise ValueError("coarsening must be 'full' or 'semi', not %r" % (coarsening,))
-    if coarsening == "semi" or shift != 0:
+    if coarsening == "semi" or shift != 0 or coefficient is not None:
         mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening=coarsening,
-                         shift=shift)
+                         shift=shift, coefficient=coefficient)
         try:
             mg.upload_v(0, grid)
             if rhs is not None:
