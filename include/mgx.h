@@ -125,6 +125,9 @@ int mgx_ctx_device(const mgx_ctx* ctx, int* device);
  * "relax3d.block3_up" 1 (default) / 0: on those levels (and where the correcting red pass runs), a post-smoothing call with a
  * partner array (mgx3dxs_interpolate_correct_relax_pp, two sweeps or more) stores the red of that pass into the partner and runs
  * the next three colour passes (B, R, B) as one launch that writes both colours back into v (mgx3dxs_block3_up_takes) -- or as three.
+ * "relax3d.block3_corr" 1 (default) / 0: on those levels mgx3dxs_interpolate_correct_relax_block3 (two sweeps or more) runs the
+ * correcting red pass and the next two passes (R', B, R) as one in-place launch that stores red only, then plain passes from B on
+ * (mgx3dxs_block3_corr_takes); the cycle of the 3D hierarchy calls it where it takes the level.
  * "gpu.exclusive" 1 (default) / 0: 0 = the GPU is shared with other contexts or processes, so the kernels whose workgroups
  * wait for each other (resident Relax, one-launch sweep of 513-point rows) are never launched; "sync.spin_limit" polls (~1 us
  * each, default 2^21) before such a wait gives up (see mgx_ctx_check); "test.handoff_fault" != 0 is a TEST HOOK that makes
@@ -150,6 +153,12 @@ const char* mgx_ctx_last_block3_kernel(const mgx_ctx* ctx);
  * store_both == 0; store_both needs separate arrays.  Bit-identical to the three passes. */
 int mgx3dxs_relax_block3_f64(mgx_ctx* ctx, const double* vin, double* vout, const double* f, const int n[3], const double h[3],
                              int first_colour, int store_both);
+/* the way up's first three colour passes R', B, R in one in-place launch: R' reads every black interior value as
+ * v + Interpolate(coarse_v) (cn[d] = (n[d] - 1) / 2 + 1), B and R follow; only the red interior points of v are written (the black
+ * ones stay as they were, uncorrected: a black pass has to follow), and no red interior entry of v is read.  Bit-identical to
+ * Interpolate + ApplyCorrection + the three passes at the red points.  Reports "relax3d_xs_block3_kernel<double,0,false,16,corr>". */
+int mgx3dxs_relax_block3_corr_f64(mgx_ctx* ctx, double* v, const double* f, const int n[3], const double h[3], const double* coarse_v,
+                                  const int cn[3]);
 /* TEST HOOK, process-wide: on != 0 -> every kernel launch of the library is preceded by a launch that fills the LDS of every
  * CU with signalling-NaN patterns (a kernel that reads an LDS word before writing it then fails its parity test for certain
  * instead of depending on the previous launch's leftovers).  Costs ~15 us per launch; results are unchanged by contract. */
@@ -422,6 +431,15 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* `ncycles` sweeps runs its passes B, R, B in one launch ("relax3d.block3_up"); such a call brings   */ \
     /* w's boundary up to date (w's interior is scratch, as in relax_pp)                                  */ \
     int mgx3dxs_block3_up_takes_##SFX(const mgx_ctx* ctx, const int n[3], int ncycles);                 \
+    /* interpolate_correct_relax_block3: interpolate_correct_relax whose passes R', B, R run as ONE       */ \
+    /* in-place launch (mgx3dxs_relax_block3_corr_f64) followed by plain passes from B on, where           */ \
+    /* block3_corr_takes says 1: fp64, `ncycles` >= 2, a level that corr_fused_takes and the three-pass    */ \
+    /* launch's size rule accept, "relax3d.block3_corr" on.  Elsewhere it is interpolate_correct_relax.    */ \
+    int mgx3dxs_block3_corr_takes_##SFX(const mgx_ctx* ctx, const int n[3], int ncycles);               \
+    int mgx3dxs_interpolate_correct_relax_block3_##SFX(mgx_ctx* ctx, real* v, const real* f,            \
+                                                       const int n[3], const real h[3],                 \
+                                                       const real* coarse_v, const int cn[3],           \
+                                                       int ncycles);                                    \
     int mgx3dxs_correct_pset_slab_##SFX(mgx_ctx* ctx, real* v, const int n[3], int fzoff,               \
                                         const real* coarse_v, const int cn[3], int czoff, int zmin,     \
                                         int zmax);                                                      \

@@ -619,6 +619,12 @@ static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v
             /* a red-black sweep follows (:645): its red pass rewrites every red interior point from black neighbours
              * alone, so only the black points need the correction, and only for that one pass: the correction and the
              * post-smoothing are one call (on large levels the corrected values are never stored) */
+            if (MG_CAT(mgx3dxs_block3_corr_takes_, R)(mg->ctx, fine->sizeXYZ, v2)) {
+                /* R', B, R as one in-place launch, then plain passes: neither v's faces nor d_e are touched */
+                MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_relax_block3_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, coarse->d_v,
+                                                                            coarse->sizeXYZ, v2)); /* :638-645 */
+                return MGX_OK;
+            }
             MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_relax_pp_, R)(mg->ctx, fine->d_v, fine->d_e, fine->d_f, fine->sizeXYZ, h, coarse->d_v,
                                                                     coarse->sizeXYZ, v2, mg->e_rim_valid[gridID])); /* :638-645 */
             if (MG_CAT(mgx3dxs_relax_pp_takes_, R)(mg->ctx, fine->sizeXYZ, v2) && !MG_CAT(mgx3dxs_corr_fused_takes_, R)(mg->ctx, fine->sizeXYZ, fine->sizeZ - 2))

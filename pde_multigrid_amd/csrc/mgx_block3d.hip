@@ -29,6 +29,18 @@
 // one iteration earlier), of the stage-1 X and of the stage-2 Y, and reads those of the previous iteration -- ONE barrier per
 // iteration, double-buffered.  Loads requested at the top of an iteration are waited for behind its barrier; the stores of the
 // previous iteration's results go out at the top too.
+//
+// CORR (way up, in place, COL = 0, red stored only): the launch stands for R', B, R -- the first red pass reads black THROUGH
+// the coarse-grid correction, as relax3d_xs_pipe_kernel<.., VAR = 2> does.  Every black value that arrives gets
+// e = Interpolate(coarse)(x, y, z) added if it is an interior point of the grid, once, before it is published to sY; stages 2
+// and 3 do not change.  The black values in memory stay uncorrected, which the plain black pass after the launch does not
+// see: it rewrites every black interior point from red and f.  A wave's rows y (odd) and y + 1 lie on the coarse rows
+// cr = y >> 1 and cr + 1, its lane's pair on coarse column p; column p + 1 is the next lane's (lane 63's odd entries, the only
+// ones that have no next lane, are never read).  So the wave keeps those two rows of coarse planes K and K + 1 in registers
+// (K = (t + 2) >> 1 for the plane t + 2 that arrives in iteration t), four values per lane, and asks for the rows of plane
+// K + 2 every other iteration with the iteration's LAST two loads, which its wait leaves outstanding: they have until the end
+// of the next iteration.  (`coarse` is deliberately not __restrict__: with it the compiler sinks those loads past the barrier
+// into the next iteration, in front of that iteration's own requests.)
 #include <type_traits>
 
 #include "mgx_internal.hpp"
@@ -36,12 +48,14 @@
 
 namespace mgx {
 
-template <class real, int COL, bool STORE_BOTH, int TW>
+template <class real, int COL, bool STORE_BOTH, int TW, bool CORR = false>
 __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs, one workgroup per CU
     relax3d_xs_block3_kernel(const real* vin, real* vout, const real* __restrict__ f, int sx, int sy, int sz, real hx2, real hy2,
-                             real hz2, int zrun, int gx, int gy, int xcd_mode) {
+                             real hz2, int zrun, int gx, int gy, int xcd_mode, const real* coarse = nullptr, int cx = 0,
+                             int cy = 0) {
     constexpr int ROWS = 2 * TW, OUTR = ROWS - 6;  // rows of a tile, of which the middle OUTR are stored
     static_assert(OUTR % 2 == 0, "the colour parity of a wave's rows must not depend on the tile");
+    static_assert(!CORR || (COL == 0 && !STORE_BOTH), "the correcting variant is R', B, R with red stored");
     __shared__ real sY[2][TW][2][64];  // [iteration & 1][wave][first / last row][lane]: loaded Y of plane t + 1
     __shared__ real sX[2][TW][2][64];  // stage-1 X of plane t
     __shared__ real sZ[2][TW][2][64];  // stage-2 Y of plane t - 1
@@ -75,16 +89,36 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
     const int wU = w > 0 ? w - 1 : 0, wD = w < TW - 1 ? w + 1 : TW - 1;
     auto zc = [&](int z) { return min(max(z, 0), sz - 1); };
     auto plane = [&](const real* a, int z) { return plane_rsrc<real>(a + (ptrdiff_t)zc(z) * (ptrdiff_t)g.PL, PL, 1); };
+    // CORR: the coarse rows cr, cr + 1 under the wave's rows (row 0 is odd: y = 2 cr + 1), the lane's coarse column p, coarse plane k
+    // (all clamped into the array: what a clamped request brings is only ever added to values that are no interior points)
+    const Geo<XSplit, real> gc(CORR ? cx : 3, CORR ? cy : 3);
+    const int cz = (sz + 1) >> 1;
+    int croff[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) croff[i] = CORR ? min(max(by * (OUTR / 2) - 2 + w + i, 0), cy - 1) * gc.P : 0;
+    const unsigned coff = (unsigned)XSplit::pos(p, gc.H) * (unsigned)sizeof(real);
+    auto cplane = [&](int k) {
+        return plane_rsrc<real>(coarse + (ptrdiff_t)min(max(k, 0), cz - 1) * (ptrdiff_t)gc.PL, (int)gc.PL, 1);
+    };
+    // e of the lane's black entry of row o (x parity ox, z parity oz) from the rows of coarse planes z >> 1 (k0) and (z >> 1) + 1 (k1)
+    auto interp = [&](int ox, int oz, int o, const real (&k0)[2], const real (&k1)[2]) __attribute__((always_inline)) {
+        return interpolate3d_point<real>(ox, 1 - o, oz, [&](int dx, int dy, int dz) __attribute__((always_inline)) {
+            const real c = o + dy ? (dz ? k1[1] : k0[1]) : (dz ? k1[0] : k0[0]);  // row 1 is even: dy = 0
+            return dx ? wave_from_next_lane<real>(c) : c;
+        });
+    };
 
     // per row: loaded Y of planes t-1, t, t+1, t+2 (in flight); f (or v on a face of the grid) of X at planes t, t-1, t-2, t+1 (in
     // flight, v of a y- / z-face); v of the even X entry at plane t+1 (in flight, x-face lanes: replaces f once it has arrived); f of Y at planes t-1, t (in flight); stage-1 X at t, t-1,
     // t-2; stage-2 Y at t-1, t-2, t-3; stage-3 X of plane t-2, stored in the next iteration
     real a_m[2], a_c[2], a_p[2], a_n[2], fx_c[2], fx_1[2], fx_2[2], fx_n[2], xv_n[2], fy_c[2], fy_n[2];
     real b_c[2], b_m[2], b_mm[2], d_c[2], d_m[2], d_mm[2], x3[2];
+    // CORR: rows cr, cr + 1 of coarse planes K, K + 1, K + 2 (in flight); the correction of a_n
+    real c_0[2], c_1[2], c_n[2], e_n[2];
 #pragma unroll
     for (int o = 0; o < 2; o++)
         a_m[o] = a_c[o] = a_p[o] = a_n[o] = fx_c[o] = fx_1[o] = fx_2[o] = fx_n[o] = xv_n[o] = fy_c[o] = fy_n[o] = b_c[o] =
-            b_m[o] = b_mm[o] = d_c[o] = d_m[o] = d_mm[o] = x3[o] = 0;
+            b_m[o] = b_mm[o] = d_c[o] = d_m[o] = d_mm[o] = x3[o] = c_0[o] = c_1[o] = c_n[o] = e_n[o] = 0;
 
     const int t0 = z0 - 2, tlast = z1 + 1;
     // ---- set-up: Y of planes t0 - 1 .. t0 + 1, f / v of X at t0; the rows of Y at t0 published as if by iteration t0 - 1
@@ -105,6 +139,37 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
 #pragma unroll
         for (int o = 0; o < 2; o++)
             if (wxface && ((COL + 1 + o + t0) & 1) == 0 && xface0) fx_c[o] = xv_n[o];
+        if constexpr (CORR) {
+#pragma unroll
+            for (int d = -1; d <= 1; d++) {
+                const int z = t0 + d;
+                const auto k0q = cplane(z >> 1), k1q = cplane((z >> 1) + 1);
+                real k0[2], k1[2];
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    k0[i] = buf_load<real>(k0q, coff, croff[i]);
+                    k1[i] = buf_load<real>(k1q, coff, croff[i]);
+                }
+                const bool zin = z >= 1 && z <= sz - 2;
+#pragma unroll
+                for (int o = 0; o < 2; o++) {
+                    const int hb = (COL + o + z) & 1;  // the black half of row o at plane z
+                    const real e = interp(hb, z & 1, o, k0, k1);
+                    real& a = d < 0 ? a_m[o] : d == 0 ? a_c[o] : a_p[o];
+                    if (zin && yin[o] && xin(hb)) a = a + e;
+                }
+            }
+            // iteration t corrects plane t + 2 from coarse planes K = (t + 2) >> 1 and K + 1; an odd one ends by taking in K + 2
+            const int K = (t0 + 2) >> 1;
+            const auto q0c = cplane(K), q1c = cplane(K + 1), qnc = cplane(K + 2);
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+                c_0[i] = buf_load<real>(q0c, coff, croff[i]);
+                c_1[i] = buf_load<real>(q1c, coff, croff[i]);
+                c_n[i] = buf_load<real>(qnc, coff, croff[i]);
+            }
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+        }
         const int b = (t0 - 1) & 1;
         sY[b][w][0][lane] = a_c[0];
         sY[b][w][1][lane] = a_c[1];
@@ -146,6 +211,13 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
             if ((hx ^ 1) == 0 && wxface) xv_n[o] = buf_load<real>(rXv, off(0), roff[o]);
             fy_n[o] = buf_load<real>(rFy, off(hx ^ 1), roff[o]);
         }
+        if constexpr (CORR && PAR == 0) {  // coarse plane K + 2 = t / 2 + 3: the last requests, still on their way at the iteration's end
+            const auto qnc = cplane((t >> 1) + 3);
+            __builtin_amdgcn_sched_barrier(0);  // (the scheduler would move them up in front of the others)
+#pragma unroll
+            for (int i = 0; i < 2; i++) c_n[i] = buf_load<real>(qnc, coff, croff[i]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         __builtin_amdgcn_s_setprio(0);
         // ---- stage 1: X at plane t (half hx) from the loaded Y
         const bool zin1 = t >= 1 && t <= sz - 2, zin2 = t - 1 >= 1 && t - 1 <= sz - 2;
@@ -182,6 +254,11 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
                             : relax(std::integral_constant<int, 1>{}, o, d_m, nb, sb, d_mm[o], d_c[o], fx_2[o]);
             }
         }
+        // ---- CORR: the correction of the Y of plane t + 2, formed while that Y is on its way
+        if constexpr (CORR) {
+#pragma unroll
+            for (int o = 0; o < 2; o++) e_n[o] = interp((COL + o + PAR) & 1, PAR, o, c_0, c_1);
+        }
         // ---- publish: Y of plane t + 1, stage-1 X of plane t, stage-2 Y of plane t - 1 (first and last row)
 #pragma unroll
         for (int o = 0; o < 2; o++) {
@@ -190,10 +267,14 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
             sZ[PAR][w][o][lane] = d_c[o];
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this iteration's requests have had the whole iteration
+        if constexpr (CORR && PAR == 0) __builtin_amdgcn_s_waitcnt(0x0F72);  // vmcnt(2): all but the two coarse requests
+        else __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this iteration's requests have had the whole iteration
+        const bool zin3 = t + 2 >= 1 && t + 2 <= sz - 2;
 #pragma unroll
         for (int o = 0; o < 2; o++) {
-            a_m[o] = a_c[o]; a_c[o] = a_p[o]; a_p[o] = a_n[o];
+            a_m[o] = a_c[o]; a_c[o] = a_p[o];
+            a_p[o] = CORR && zin3 && yin[o] && xin((COL + o + PAR) & 1) ? a_n[o] + e_n[o] : a_n[o];
+            if constexpr (CORR && PAR == 1) { c_0[o] = c_1[o]; c_1[o] = c_n[o]; }
             fx_2[o] = fx_1[o]; fx_1[o] = fx_c[o];
             fx_c[o] = ((COL + 1 + o + PAR) & 1) == 1 && wxface && xface0 ? xv_n[o] : fx_n[o];  // x-face lanes: v of the even X entry
             fy_c[o] = fy_n[o];
@@ -223,7 +304,8 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
 
 // Does the three-pass launch take the level?  The levels relax_rr3d_xs_kernel takes by its own rule (fp64 from 385-point rows
 // on), not those forced into it by rr3d.black = 2; one plane addressed through a 32-bit buffer descriptor.  part: bit 0 the way
-// down, bit 1 the way up (switched by relax3d.block3 / relax3d.block3_up).
+// down, bit 1 the way up's B, R, B after R', bit 2 the way up's R', B, R (switched by relax3d.block3 / relax3d.block3_up /
+// relax3d.block3_corr).
 bool relax_block3_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int part) {
     if (!(ctx->block3 & part) || elem != 8) return false;
     if ((unsigned long long)Geo<XSplit, double>(n[0], n[1]).PL * 8ull >= (1ull << 31)) return false;
@@ -232,10 +314,11 @@ bool relax_block3_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int par
 
 // colour passes first_colour, 1 - first_colour, first_colour over the interior of an (n[0], n[1], n[2]) level in one launch:
 // reads the other colour and the faces of the grid from vin, f; writes first_colour's interior points (store_both: both
-// colours') into vout.  Any size the smoother accepts.
+// colours') into vout.  Any size the smoother accepts.  coarse != nullptr (first_colour 0, red stored only, vin == vout): the
+// first pass reads black through the correction from `coarse` (cn[0] x cn[1] x cn[2]).
 template <class real>
 void relax3d_xs_block3_launch(mgx_ctx* ctx, const real* vin, real* vout, const real* f, const int n[3], real hx2, real hy2, real hz2,
-                              int first_colour, bool store_both) {
+                              int first_colour, bool store_both, const real* coarse, const int* cn) {
     constexpr int TW = 16;
     const int gx = ceil_div((n[0] - 1) / 2, 60), gy = ceil_div(n[1] - 2, 2 * TW - 6);
     const int tiles = gx * gy, planes = n[2] - 2;
@@ -246,17 +329,20 @@ void relax3d_xs_block3_launch(mgx_ctx* ctx, const real* vin, real* vout, const r
 #define MGX_B3(C, S)                                                                                                          \
     MGX_LAUNCH((relax3d_xs_block3_kernel<real, C, S, TW>), grid, blk, 0, ctx->compute, vin, vout, f, n[0], n[1], n[2], hx2, hy2, \
                hz2, zrun, gx, gy, 1)
-    if (first_colour == 0) {
+    if (coarse) {
+        MGX_LAUNCH((relax3d_xs_block3_kernel<real, 0, false, TW, true>), grid, blk, 0, ctx->compute, vin, vout, f, n[0], n[1], n[2], hx2,
+                   hy2, hz2, zrun, gx, gy, 1, coarse, cn[0], cn[1]);
+    } else if (first_colour == 0) {
         if (store_both) MGX_B3(0, true); else MGX_B3(0, false);
     } else {
         if (store_both) MGX_B3(1, true); else MGX_B3(1, false);
     }
 #undef MGX_B3
-    snprintf(ctx->last_block3_kernel, sizeof ctx->last_block3_kernel, "relax3d_xs_block3_kernel<%s,%d,%s,%d>",
-             sizeof(real) == 8 ? "double" : "float", first_colour, store_both ? "true" : "false", TW);
+    snprintf(ctx->last_block3_kernel, sizeof ctx->last_block3_kernel, "relax3d_xs_block3_kernel<%s,%d,%s,%d%s>",
+             sizeof(real) == 8 ? "double" : "float", first_colour, store_both ? "true" : "false", TW, coarse ? ",corr" : "");
 }
 template void relax3d_xs_block3_launch<double>(mgx_ctx*, const double*, double*, const double*, const int[3], double, double, double, int,
-                                               bool);
+                                               bool, const double*, const int*);
 
 }  // namespace mgx
 
@@ -271,7 +357,23 @@ extern "C" int mgx3dxs_relax_block3_f64(mgx_ctx* ctx, const double* vin, double*
     MGX_REQUIRE(plane_bytes < (1ull << 31), MGX_ERR_SIZE,
                 "relax_block3: a plane of %d x %d is too large", n[0], n[1]);
     MGX_REQUIRE(!store_both || vin != vout, MGX_ERR_INVALID, "relax_block3: store_both needs vout != vin");
-    mgx::relax3d_xs_block3_launch<double>(ctx, vin, vout, f, n, h[0] * h[0], h[1] * h[1], h[2] * h[2], first_colour, store_both != 0);
+    mgx::relax3d_xs_block3_launch<double>(ctx, vin, vout, f, n, h[0] * h[0], h[1] * h[1], h[2] * h[2], first_colour, store_both != 0, nullptr, nullptr);
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
+// the correcting launch alone, in place: red = R(B(R'(v, coarse_v))) on the interior; nothing else of v is written
+extern "C" int mgx3dxs_relax_block3_corr_f64(mgx_ctx* ctx, double* v, const double* f, const int n[3], const double h[3], const double* coarse_v,
+                                             const int cn[3]) {
+    MGX_REQUIRE(ctx && v && f && n && h && coarse_v && cn, MGX_ERR_INVALID, "relax_block3_corr: NULL argument");
+    MGX_USE(ctx);
+    MGX_REQUIRE(mgx::valid_size(n[0]) && mgx::valid_size(n[1]) && mgx::valid_size(n[2]), MGX_ERR_SIZE,
+                "relax_block3_corr: sizes %d x %d x %d are not odd and >= 3", n[0], n[1], n[2]);
+    for (int d = 0; d < 3; d++)
+        MGX_REQUIRE(cn[d] == (n[d] - 1) / 2 + 1, MGX_ERR_SIZE, "relax_block3_corr: coarse size[%d] = %d != (%d-1)/2+1", d, cn[d], n[d]);
+    const unsigned long long plane_bytes = (unsigned long long)mgx::Geo<mgx::XSplit, double>(n[0], n[1]).PL * 8ull;
+    MGX_REQUIRE(plane_bytes < (1ull << 31), MGX_ERR_SIZE, "relax_block3_corr: a plane of %d x %d is too large", n[0], n[1]);
+    mgx::relax3d_xs_block3_launch<double>(ctx, v, v, f, n, h[0] * h[0], h[1] * h[1], h[2] * h[2], 0, false, coarse_v, cn);
     MGX_LAUNCH_CHECK();
     return MGX_OK;
 }

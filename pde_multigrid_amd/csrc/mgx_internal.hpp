@@ -84,8 +84,9 @@ struct mgx_ctx {
     char last_corr_kernel[96] = "";   // the correcting red pass of the most recent interpolate_correct_relax ("" = none: small level or corr_fuse = 0)
     char last_rr_kernel[96] = "";     // the fused black pass + residual + restrict kernel of the most recent call ("" = not fused)
     char last_relax_kernel[96] = "";  // name of the smoother kernel of the most recent colour pass (bench.py: roofline.kernel)
-    int block3 = 3;                   // bit 0 ("relax3d.block3") = the way down's last three passes before the fused black pass in one launch,
-                                      // bit 1 ("relax3d.block3_up") = the way up's three passes after the correcting red pass in one launch
+    int block3 = 7;                   // bit 0 ("relax3d.block3") = the way down's last three passes before the fused black pass in one launch,
+                                      // bit 1 ("relax3d.block3_up") = the way up's three passes after the correcting red pass in one launch,
+                                      // bit 2 ("relax3d.block3_corr") = the way up's R', B, R in one in-place launch (no partner array)
     char last_block3_kernel[96] = ""; // the three-pass kernel of the most recent smooth_residual_restrict / relax_block3 /
                                       // interpolate_correct_relax call ("" = none)
 };

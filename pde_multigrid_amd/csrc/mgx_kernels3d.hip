@@ -3039,9 +3039,10 @@ bool relax_rr3d_xs_takes(const mgx_ctx* ctx, const int n[3], const int cn[3], si
 bool relax_block3_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int part);  // mgx_block3d.hip
 template <class real>
 void relax3d_xs_block3_launch(mgx_ctx* ctx, const real* vin, real* vout, const real* f, const int n[3], real hx2, real hy2, real hz2,
-                              int first_colour, bool store_both);
+                              int first_colour, bool store_both, const real* coarse = nullptr, const int* cn = nullptr);
 template <>
-void relax3d_xs_block3_launch<float>(mgx_ctx*, const float*, float*, const float*, const int[3], float, float, float, int, bool) {}  // fp64 only: never taken
+void relax3d_xs_block3_launch<float>(mgx_ctx*, const float*, float*, const float*, const int[3], float, float, float, int, bool, const float*,
+                                     const int*) {}  // fp64 only: never taken
 
 // The fused launch alone on a z-slab (or the whole grid): black pass of the GLOBAL fine planes [2 pzbeg - 1, 2 pzend - 1] +
 // residual + restrict into the GLOBAL coarse planes [pzbeg, pzend).  n / cn global sizes, v / f start at global plane fzoff,
@@ -3330,12 +3331,44 @@ static bool block3_up_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int
     return ncycles >= 2 && corr_fused_takes(ctx, n[0], n[1], n[2], n[2] - 2) && relax_block3_takes(ctx, n, elem, 2);
 }
 
+// Does the way up run R', B, R as ONE in-place launch that reads black through the correction and stores red only
+// (relax3d_xs_block3_kernel, CORR), followed by plain passes from B on?  The levels of block3_up_takes, under a switch of its own
+// ("relax3d.block3_corr").
+static bool block3_corr_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int ncycles) {
+    return ncycles >= 2 && corr_fused_takes(ctx, n[0], n[1], n[2], n[2] - 2) && relax_block3_takes(ctx, n, elem, 4);
+}
+
+// v += Interpolate(coarse_v), then `ncycles` sweeps, with the passes R', B, R in one launch where block3_corr_takes says so: no
+// partner array, no face copy, nothing of v but its red interior points written by that launch.  Elsewhere as
+// interpolate_correct_relax3d_xs without a partner.
+template <class real>
+int interpolate_correct_relax3d_xs(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], const real* coarse_v,
+                                   const int cn[3], int ncycles, real* w = nullptr, int w_rim_valid = 0);
+template <class real>
+int interpolate_correct_relax_block3_xs(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], const real* coarse_v,
+                                        const int cn[3], int ncycles) {
+    MGX_REQUIRE(ctx && v && f && h && coarse_v, MGX_ERR_INVALID, "interpolate_correct_relax_block3: NULL argument");
+    MGX_USE(ctx);
+    int st = check_n3(n, "interpolate_correct_relax_block3");
+    if (st) return st;
+    st = check_coarse3(n, cn, "interpolate_correct_relax_block3");
+    if (st) return st;
+    MGX_REQUIRE(ncycles >= 1, MGX_ERR_INVALID, "interpolate_correct_relax_block3: ncycles = %d < 1", ncycles);
+    if (!block3_corr_takes(ctx, n, sizeof(real), ncycles)) return interpolate_correct_relax3d_xs<real>(ctx, v, f, n, h, coarse_v, cn, ncycles, nullptr, 0);
+    ctx->last_corr_kernel[0] = 0;
+    const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];  // :498-500
+    relax3d_xs_block3_launch<real>(ctx, v, v, f, n, hx2, hy2, hz2, 0, false, coarse_v, cn);
+    for (int s = 3; s < 2 * ncycles; s++) relax3d_xs_pass<real>(ctx, v, f, n[0], n[1], 1, n[2] - 1, hx2, hy2, hz2, s & 1);
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
 // w != nullptr: a second array of the level's size as ping-pong partner for the sweeps (mgx3dxs_relax_pp); on the levels
 // block3_up_takes, the scratch array between the correcting red pass and the three-pass launch.  w_rim_valid != 0: the caller
 // vouches that w's boundary entries equal v's.
 template <class real>
 int interpolate_correct_relax3d_xs(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], const real* coarse_v,
-                                   const int cn[3], int ncycles, real* w = nullptr, int w_rim_valid = 0) {
+                                   const int cn[3], int ncycles, real* w, int w_rim_valid) {
     MGX_REQUIRE(ctx && v && f && h && coarse_v, MGX_ERR_INVALID, "interpolate_correct_relax3d: NULL argument");
     MGX_USE(ctx);
     int st = check_n3(n, "interpolate_correct_relax3d");
@@ -3672,6 +3705,14 @@ template int relax3d_xs_from_zero<double>(mgx_ctx*, double*, const double*, cons
     int mgx3dxs_block3_up_takes_##SFX(const mgx_ctx* ctx, const int n[3], int ncycles) {                         \
         return ctx && n && mgx::block3_up_takes(ctx, n, sizeof(real), ncycles);                                  \
     }                                                                                                            \
+    int mgx3dxs_block3_corr_takes_##SFX(const mgx_ctx* ctx, const int n[3], int ncycles) {                       \
+        return ctx && n && mgx::block3_corr_takes(ctx, n, sizeof(real), ncycles);                                \
+    }                                                                                                            \
+    int mgx3dxs_interpolate_correct_relax_block3_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3],     \
+                                                       const real h[3], const real* coarse_v, const int cn[3],   \
+                                                       int ncycles) {                                            \
+        return mgx::interpolate_correct_relax_block3_xs<real>(ctx, v, f, n, h, coarse_v, cn, ncycles);           \
+    }                                                                                                            \
     int mgx3dxs_correct_pset_slab_##SFX(mgx_ctx* ctx, real* v, const int n[3], int fzoff, const real* coarse_v,  \
                                         const int cn[3], int czoff, int zmin, int zmax) {                        \
         return mgx::correct_pset3d_slab<real>(ctx, v, n, fzoff, coarse_v, cn, czoff, zmin, zmax);                \
@@ -3863,6 +3904,9 @@ int mgx_ctx_set_param(mgx_ctx* ctx, const char* name, int value) {
     } else if (!strcmp(name, "relax3d.block3_up")) {
         MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.block3_up = %d not in {0, 1}", value);
         ctx->block3 = (ctx->block3 & ~2) | (value << 1);  // bit 1: the way up runs its passes B, R, B after R' in one launch
+    } else if (!strcmp(name, "relax3d.block3_corr")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.block3_corr = %d not in {0, 1}", value);
+        ctx->block3 = (ctx->block3 & ~4) | (value << 2);  // bit 2: the way up runs R', B, R as one in-place launch that stores red only
     } else if (!strcmp(name, "relax3d.zchunk")) {
         MGX_REQUIRE(value >= 0, MGX_ERR_INVALID, "relax3d.zchunk must be >= 0 (0 = automatic)");
         ctx->relax_zchunk = value;

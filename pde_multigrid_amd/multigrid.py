@@ -330,6 +330,11 @@ class _Ops3D(_Ops):
         s, _ = _ct(dtype)
         return bool(getattr(lib, "mgx3dxs_block3_up_takes_" + s)(ctx._h, _ip(n), C.c_int(ncycles)))
 
+    def block3_corr_takes(self, ctx, n, ncycles, dtype=np.float64):
+        """does interpolate_correct_relax_block3 run the passes R', B, R as one in-place launch?"""
+        s, _ = _ct(dtype)
+        return bool(getattr(lib, "mgx3dxs_block3_corr_takes_" + s)(ctx._h, _ip(n), C.c_int(ncycles)))
+
     def residual(self, ctx, v, f, n, rng, mode=REF_COMPAT, dtype=None):
         dtype = dtype or v.dtype
         fn, ct = self._fn("residual", dtype)
@@ -424,6 +429,23 @@ class _Ops3D(_Ops):
             return self._run(ctx, arrs, call, 0, _shape(n), np.float64)
         call = lambda a, b, c: lib.mgx3dxs_relax_block3_f64(ctx._h, a, c, b, _ip(n), h, C.c_int(first_colour), C.c_int(int(store_both)))
         return self._run(ctx, arrs, call, 2, _shape(n), np.float64)
+
+    def relax_block3_corr(self, ctx, v, f, n, rng, coarse):
+        """x-split fp64 only: the passes R', B, R of the way up in one in-place launch (mgx3dxs_relax_block3_corr_f64): the first red
+        pass reads black through the correction from `coarse`; only the red interior points of v are written"""
+        h = _rp(grid_spacing(n, rng, np.float64), C.c_double)
+        cn = coarse_size(n)
+        return self._run(ctx, [v, f, coarse], lambda a, b, c: lib.mgx3dxs_relax_block3_corr_f64(ctx._h, a, b, _ip(n), h, c, _ip(cn)), 0,
+                         _shape(n), np.float64)
+
+    def interpolate_correct_relax_block3(self, ctx, v, f, n, rng, coarse, ncycles, dtype=None):
+        """x-split only: interpolate_correct_relax with R', B, R in one launch where block3_corr_takes says so"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("interpolate_correct_relax_block3", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        cn = coarse_size(n)
+        return self._run(ctx, [v, f, coarse], lambda a, b, c: fn(ctx._h, a, b, _ip(n), h, c, _ip(cn), C.c_int(ncycles)), 0, _shape(n),
+                         dtype)
 
     def interpolate_correct_relax(self, ctx, v, f, n, rng, coarse, ncycles, dtype=None):
         """x-split only: v += Interpolate(coarse) on the interior, then ncycles >= 1 red-black sweeps, in one call"""

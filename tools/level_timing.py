@@ -63,8 +63,15 @@ print("  the way up in one call: interpolate + correct + Relax(2)   %.4f ms" % t
     lambda: P.check(icr(ctx._h, C.c_void_p(g0.d_v), C.c_void_p(g0.d_f), n0, h, C.c_void_p(g1.d_v), n1, C.c_int(2)))))
 icp = getattr(P.lib, "mgx3dxs_interpolate_correct_relax_pp_" + sfx)
 P.check(icp(ctx._h, C.c_void_p(g0.d_v), C.c_void_p(g0.d_e), C.c_void_p(g0.d_f), n0, h, C.c_void_p(g1.d_v), n1, C.c_int(2), C.c_int(0)))
-print("  the way up as the cycle calls it (d_e as partner)          %.4f ms  [%s]" % (
+print("  the way up with d_e as partner (R', then B, R, B)          %.4f ms  [%s]" % (
     timed(lambda: P.check(icp(ctx._h, C.c_void_p(g0.d_v), C.c_void_p(g0.d_e), C.c_void_p(g0.d_f), n0, h, C.c_void_p(g1.d_v), n1,
                               C.c_int(2), C.c_int(1)))), ctx.last_block3_kernel() or "separate launches"))
+if getattr(P.lib, "mgx3dxs_block3_corr_takes_" + sfx)(ctx._h, n0, C.c_int(2)):  # R', B, R in place, then B
+    icb = getattr(P.lib, "mgx3dxs_interpolate_correct_relax_block3_" + sfx)
+    up = lambda: P.check(icb(ctx._h, C.c_void_p(g0.d_v), C.c_void_p(g0.d_f), n0, h, C.c_void_p(g1.d_v), n1, C.c_int(2)))
+else:
+    up = lambda: P.check(icp(ctx._h, C.c_void_p(g0.d_v), C.c_void_p(g0.d_e), C.c_void_p(g0.d_f), n0, h, C.c_void_p(g1.d_v), n1, C.c_int(2),
+                             C.c_int(1)))
+print("  the way up as the cycle calls it                           %.4f ms  [%s]" % (timed(up), ctx.last_block3_kernel() or "separate launches"))
 print("  interpolate+correct (black)     %.4f ms" % timed(lambda: P.check(ic(ctx._h, C.c_void_p(g0.d_v), n0, C.c_void_p(g1.d_v), n1, C.c_int(1)))))
 print("  zero fill of the coarse v       %.4f ms" % timed(lambda: mg.setToValue_v(1, 0.0, True)))
