@@ -585,9 +585,10 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* MGX_ERR_SIZE for sizes that are not odd and >= 3; pad entries are neither written nor read as    */ \
     /* data.  The values of a are not checked here (mgMultiGrid3D_<r>_set_coefficient does).            */ \
     /* relax_coef / relax_coef_from_zero: the contracts of relax_shift / relax_shift_from_zero (with    */ \
-    /*   rim_is_zero the first red pass reads f and a only); mgx_ctx_last_relax_kernel names            */ \
-    /*   relax_coef3d_xs_kernel.  residual_coef: residual_shift's contract (r and / or the sum of       */ \
-    /*   squares).  apply_coef_dot: laplace_dot_shift's contract (q = A p on the interior, <p, q>).     */ \
+    /*   rim_is_zero the first red pass reads f and a only); mgx_ctx_last_relax_kernel reports the      */ \
+    /*   name relax_coef3d_xs_kernel (the colour pass both operators share, instantiated for this       */ \
+    /*   one).  residual_coef: residual_shift's contract (r and / or the sum of squares).               */ \
+    /*   apply_coef_dot: laplace_dot_shift's contract (q = A p on the interior, <p, q>).                */ \
     int mgx3dxs_relax_coef_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3],   \
                                  const real h[3], real s, int ncycles);                                 \
     int mgx3dxs_relax_coef_from_zero_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,         \

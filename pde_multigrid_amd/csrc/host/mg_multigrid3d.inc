@@ -257,6 +257,36 @@ static int MG_CAT(coef_ok3_, R)(const MGRID* mg, const char* what) {
     return MGX_OK;
 }
 
+/* The operators other than the plain Laplacian: the variable-coefficient one where the hierarchy has a coefficient (with any
+ * shift), else the shifted one where shift != 0.  What the hierarchy's operator needs of the hierarchy and of the grid g it is
+ * applied to (nothing for the plain one). */
+static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) {
+    if (!MG_CAT(has_coef3_, R)(mg)) return MG_CAT(shift_ok3_, R)(mg, mg->shift, what);
+    MG_TRY(MG_CAT(coef_ok3_, R)(mg, what));
+    MG_REQUIRE(g->d_a, MGX_ERR_INVALID, "%s: the grid has no coefficient array", what);
+    return MGX_OK;
+}
+
+/* r = f - A v on grid g by the hierarchy's operator, 0 on the boundary (r == NULL: not stored), and its sum of squares into
+ * *dev_sumsq (NULL: none; dev_work: the partials).  The plain operator takes mg->residual_mode and sums in a launch of its own. */
+static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, const REAL* f, REAL* r, double* dev_work, double* dev_sumsq) {
+    const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    if (MG_CAT(has_coef3_, R)(mg))
+        return MG_CAT(mgx3dxs_residual_coef_, R)(mg->ctx, v, f, g->d_a, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq);
+    if (mg->shift != 0) return MG_CAT(mgx3dxs_residual_shift_, R)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq);
+    MG_TRY(MGXL(mg, residual)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->residual_mode));
+    return dev_sumsq ? MG_CAT(mgx3dxs_dot2_, R)(mg->ctx, r, r, NULL, g->sizeXYZ, dev_work, dev_sumsq) : MGX_OK;
+}
+
+/* q = A p on grid g by the hierarchy's operator (x-split, CORRECT mode), *dev_sum = <p, q> */
+static int MG_CAT(op_apply_dot3_, R)(MGRID* mg, const GRID* g, const REAL* p, REAL* q, double* dev_work, double* dev_sum) {
+    const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    if (MG_CAT(has_coef3_, R)(mg))
+        return MG_CAT(mgx3dxs_apply_coef_dot_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum);
+    if (mg->shift != 0) return MG_CAT(mgx3dxs_laplace_dot_shift_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum);
+    return MG_CAT(mgx3dxs_laplace_dot_, R)(mg->ctx, p, q, g->sizeXYZ, h, dev_work, dev_sum);
+}
+
 /* The captured graphs hold the d_a pointers of every level, their records only level 0's: whenever the arrays are allocated or
  * freed the graphs are dropped, so that no replay can meet arrays other than those of its capture. */
 static void MG_CAT(coef_drop_graphs3_, R)(MGRID* mg) {
@@ -349,15 +379,11 @@ int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
     int lvl = -1;
     for (int i = 0; i < mg->maxGrids; i++)
         if (mg->grids3D[i] == curGrid) lvl = i;
-    if (MG_CAT(has_coef3_, R)(mg)) { /* one launch per colour pass; d_e is not used */
-        MG_TRY(MG_CAT(coef_ok3_, R)(mg, "Relax"));
-        MG_REQUIRE(curGrid->d_a, MGX_ERR_INVALID, "Relax: the grid has no coefficient array");
+    MG_TRY(MG_CAT(op_ok3_, R)(mg, curGrid, "Relax"));
+    /* the coefficient and the shifted operator: one launch per colour pass; d_e is not used */
+    if (MG_CAT(has_coef3_, R)(mg))
         return MG_CAT(mgx3dxs_relax_coef_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift, ncycles);
-    }
-    if (mg->shift != 0) { /* one launch per colour pass; d_e is not used */
-        MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "Relax"));
-        return MG_CAT(mgx3dxs_relax_shift_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles);
-    }
+    if (mg->shift != 0) return MG_CAT(mgx3dxs_relax_shift_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles);
     if (mg->smoother == 1) { /* weighted Jacobi: the error scratch doubles as the ping-pong array */
         if (lvl >= 0) mg->e_rim_valid[lvl] = 0;
         return MGXL(mg, jacobi)(mg->ctx, curGrid->d_v, curGrid->d_e, curGrid->d_f, curGrid->sizeXYZ, h, mg->omega, ncycles);
@@ -387,17 +413,8 @@ int FN(setToValue)(MGRID* mg, REAL* grid, const int sizeXYZ[3], REAL value, int 
  * never freed, N3/MultiGrid3D.cpp:695) */
 int FN(CalculateResidual)(MGRID* mg, GRID* fine, REAL** residual) {
     MG_REQUIRE(mg && fine && residual, MGX_ERR_INVALID, "CalculateResidual: NULL");
-    const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
-    if (MG_CAT(has_coef3_, R)(mg)) {
-        MG_TRY(MG_CAT(coef_ok3_, R)(mg, "CalculateResidual"));
-        MG_REQUIRE(fine->d_a, MGX_ERR_INVALID, "CalculateResidual: the grid has no coefficient array");
-        MG_TRY(MG_CAT(mgx3dxs_residual_coef_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->d_r, fine->sizeXYZ, h, mg->shift, NULL, NULL));
-    } else if (mg->shift != 0) {
-        MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "CalculateResidual"));
-        MG_TRY(MG_CAT(mgx3dxs_residual_shift_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_r, fine->sizeXYZ, h, mg->shift, NULL, NULL));
-    } else {
-        MG_TRY(MGXL(mg, residual)(mg->ctx, fine->d_v, fine->d_f, fine->d_r, fine->sizeXYZ, h, mg->residual_mode));
-    }
+    MG_TRY(MG_CAT(op_ok3_, R)(mg, fine, "CalculateResidual"));
+    MG_TRY(MG_CAT(op_residual3_, R)(mg, fine, fine->d_v, fine->d_f, fine->d_r, NULL, NULL));
     *residual = fine->d_r;
     return MGX_OK;
 }
@@ -480,17 +497,24 @@ static int MG_CAT(vcycle_semi_step3_, R)(MGRID* mg, int gridID, int v1, int v2, 
     return FN(Relax)(mg, fine, v2); /* :645 */
 }
 
-/* One level of the cycle of the shifted operator (shift != 0), on full and on semi-coarsened steps alike: vcycle_semi_step3_ with
- * the mgx3dxs_*_shift smoother and residual+restrict around the unshifted transfers (the shift only changes the operator, not how
- * grids are transferred).  One launch per colour pass: the one-launch tail and the fused routes are not taken.  The rim flags as
- * in vcycle_semi_step3_; d_e is never used. */
-static int MG_CAT(vcycle_shift_step3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
-    MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "VCycle"));
+/* One level of the cycle of the shifted (shift != 0) or the variable-coefficient operator, on full and on semi-coarsened steps
+ * alike: vcycle_semi_step3_ with the operator's smoother and residual around the plain transfers (the operator does not change
+ * how grids are transferred).  The operator decides the settings check, the from-zero smoother and how the coarse f is formed:
+ * the shifted one by the fused residual+restrict, the coefficient one by its residual stored into d_r and restricted by the
+ * existing transfers (Restrict writes the coarse f whole: its boundary is the injected boundary of r, 0).  One launch per colour
+ * pass: the one-launch tail and the fused routes are not taken.  The rim flags as in vcycle_semi_step3_; d_e is never used. */
+static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
     GRID* fine = mg->grids3D[gridID];
+    MG_TRY(MG_CAT(op_ok3_, R)(mg, fine, "VCycle"));
+    const int coef = MG_CAT(has_coef3_, R)(mg);
     const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
     if (v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
         if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
-        MG_TRY(MG_CAT(mgx3dxs_relax_shift_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, mg->shift, v1, mg->v_rim_zero[gridID]));
+        if (coef)
+            MG_TRY(MG_CAT(mgx3dxs_relax_coef_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->sizeXYZ, h, mg->shift, v1,
+                                                            mg->v_rim_zero[gridID]));
+        else
+            MG_TRY(MG_CAT(mgx3dxs_relax_shift_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, mg->shift, v1, mg->v_rim_zero[gridID]));
         mg->v_rim_zero[gridID] = 1;
     } else {
         if (v_zero) MG_TRY(FN(setToValue)(mg, fine->d_v, fine->sizeXYZ, (REAL)0, 1)); /* :634 */
@@ -498,49 +522,19 @@ static int MG_CAT(vcycle_shift_step3_, R)(MGRID* mg, int gridID, int v1, int v2,
     }
     if (gridID != mg->numGrids - 1) {
         GRID* coarse = mg->grids3D[gridID + 1];
-        MG_TRY(MG_CAT(mgx3dxs_residual_restrict_shift_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, mg->shift, coarse->d_f,
-                                                           coarse->sizeXYZ, mg->f_rim_zero[gridID + 1])); /* :629-632 */
+        const int semi = mg->coarsen[gridID] != 7;
+        if (coef) {
+            MG_TRY(MG_CAT(op_residual3_, R)(mg, fine, fine->d_v, fine->d_f, fine->d_r, NULL, NULL)); /* :629 */
+            if (semi) MG_TRY(MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ));
+            else MG_TRY(MG_CAT(mgx3dxs_restrict_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ)); /* :632 */
+        } else {
+            MG_TRY(MG_CAT(mgx3dxs_residual_restrict_shift_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, mg->shift, coarse->d_f,
+                                                               coarse->sizeXYZ, mg->f_rim_zero[gridID + 1])); /* :629-632 */
+        }
         mg->f_rim_zero[gridID + 1] = 1;
         MG_TRY(MG_CAT(vcycle_body3_, R)(mg, gridID + 1, v1, v2, 1)); /* :634-635 */
-        if (mg->coarsen[gridID] != 7)
-            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ));
-        else
-            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */
-    }
-    return FN(Relax)(mg, fine, v2); /* :645 */
-}
-
-/* One level of the cycle of the variable-coefficient operator, on full and on semi-coarsened steps alike: vcycle_shift_step3_
- * with the mgx3dxs_*_coef smoother, and the residual stored into d_r and restricted by the existing transfers (no fused
- * residual+restrict).  One launch per colour pass: the one-launch tail and the fused routes are not taken.  The rim flags as in
- * vcycle_shift_step3_ (Restrict writes the coarse f whole: its boundary is the injected boundary of r, 0); d_e is never used. */
-static int MG_CAT(vcycle_coef_step3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
-    MG_TRY(MG_CAT(coef_ok3_, R)(mg, "VCycle"));
-    GRID* fine = mg->grids3D[gridID];
-    const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
-    if (v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
-        if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
-        MG_TRY(MG_CAT(mgx3dxs_relax_coef_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->sizeXYZ, h, mg->shift, v1,
-                                                        mg->v_rim_zero[gridID]));
-        mg->v_rim_zero[gridID] = 1;
-    } else {
-        if (v_zero) MG_TRY(FN(setToValue)(mg, fine->d_v, fine->sizeXYZ, (REAL)0, 1)); /* :634 */
-        MG_TRY(FN(Relax)(mg, fine, v1));                                              /* :626 */
-    }
-    if (gridID != mg->numGrids - 1) {
-        GRID* coarse = mg->grids3D[gridID + 1];
-        MG_TRY(MG_CAT(mgx3dxs_residual_coef_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->d_r, fine->sizeXYZ, h, mg->shift, NULL,
-                                                 NULL)); /* :629 */
-        if (mg->coarsen[gridID] != 7)
-            MG_TRY(MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ));
-        else
-            MG_TRY(MG_CAT(mgx3dxs_restrict_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ)); /* :632 */
-        mg->f_rim_zero[gridID + 1] = 1;
-        MG_TRY(MG_CAT(vcycle_body3_, R)(mg, gridID + 1, v1, v2, 1)); /* :634-635 */
-        if (mg->coarsen[gridID] != 7)
-            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ));
-        else
-            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */
+        if (semi) MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ));
+        else MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */
     }
     return FN(Relax)(mg, fine, v2); /* :645 */
 }
@@ -548,8 +542,7 @@ static int MG_CAT(vcycle_coef_step3_, R)(MGRID* mg, int gridID, int v1, int v2, 
 /* VCycle from level gridID down.  v_zero: the level's v counts as all zeros (the coarse error of :634) but has not been
  * zeroed in memory yet -- the one-workgroup tail kernel never reads it, the other levels zero it first. */
 static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
-    if (MG_CAT(has_coef3_, R)(mg)) return MG_CAT(vcycle_coef_step3_, R)(mg, gridID, v1, v2, v_zero);
-    if (mg->shift != 0) return MG_CAT(vcycle_shift_step3_, R)(mg, gridID, v1, v2, v_zero);
+    if (MG_CAT(has_coef3_, R)(mg) || mg->shift != 0) return MG_CAT(vcycle_op_step3_, R)(mg, gridID, v1, v2, v_zero);
     GRID* fine = mg->grids3D[gridID];
     const int nlev = mg->numGrids - gridID;
     if (mg->fuse && mg->smoother == 0 && nlev <= 6 && !MG_CAT(semi_below3_, R)(mg, gridID)) { /* levels of at most 17^3: the rest of the cycle in ONE launch */
@@ -853,7 +846,6 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
     mgx_ctx* ctx = mg->ctx;
     GRID* g = mg->grids3D[0];
     const int* n = g->sizeXYZ;
-    const REAL h[3] = {g->h_x, g->h_y, g->h_z};
     const size_t bytes = MG_CAT(dvol3_, R)(mg->layout, g) * sizeof(REAL);
     REAL *x = mg->pcg_x, *b = mg->pcg_b, *p = mg->pcg_p, *q = mg->pcg_q, *r = g->d_f, *z = g->d_v;
     double *s = mg->pcg_state, *w = mg->pcg_work;
@@ -864,13 +856,8 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
     double rr0 = 0.0, rr = 0.0;
     int pending = 0; /* x still lacks alpha p of the last iteration */
     /* r = b - A x (0 on the boundary), ||r0|| */
-    const REAL shift = mg->shift; /* != 0: the shifted residual (with its sum) and operator */
-    const REAL* ca = g->d_a;      /* != NULL: the variable-coefficient residual (with its sum) and operator, with any shift */
-    if (ca) st = MG_CAT(mgx3dxs_residual_coef_, R)(ctx, x, b, ca, r, n, h, shift, w, s + MGX_CG_RR);
-    else if (shift != 0) st = MG_CAT(mgx3dxs_residual_shift_, R)(ctx, x, b, r, n, h, shift, w, s + MGX_CG_RR);
-    else st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
+    st = MG_CAT(op_residual3_, R)(mg, g, x, b, r, w, s + MGX_CG_RR);
     mg->f_rim_zero[0] = 0;
-    if (!st && !ca && shift == 0) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
     if (!st) st = mgx_memcpy_d2h(ctx, &rr0, s + MGX_CG_RR, sizeof(double));
     if (!st && rr0 == 0.0) *converged = 1;
     int restart = 1; /* z = M r, p = z, rz = <r, z> */
@@ -883,9 +870,7 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
             restart = 0;
         }
         /* q = A p, alpha = <r, z> / <p, q>; r -= alpha q */
-        if (!st && ca) st = MG_CAT(mgx3dxs_apply_coef_dot_, R)(ctx, p, ca, q, n, h, shift, w, s + MGX_CG_PQ);
-        else if (!st && shift != 0) st = MG_CAT(mgx3dxs_laplace_dot_shift_, R)(ctx, p, q, n, h, shift, w, s + MGX_CG_PQ);
-        else if (!st) st = MG_CAT(mgx3dxs_laplace_dot_, R)(ctx, p, q, n, h, w, s + MGX_CG_PQ);
+        if (!st) st = MG_CAT(op_apply_dot3_, R)(mg, g, p, q, w, s + MGX_CG_PQ);
         if (!st) st = mgx_cg_scalars(ctx, s, 0);
         if (!st) st = MG_CAT(mgx3dxs_cg_update_, R)(ctx, NULL, p, r, q, n, s + MGX_CG_ALPHA, w, s + MGX_CG_RR);
         if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double)); /* the one host read of the iteration */
@@ -898,10 +883,7 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
         if (rel < tol) { /* the recursive residual may have drifted from b - A x: check the true one */
             st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL);
             pending = 0;
-            if (!st && ca) st = MG_CAT(mgx3dxs_residual_coef_, R)(ctx, x, b, ca, r, n, h, shift, w, s + MGX_CG_RR);
-            else if (!st && shift != 0) st = MG_CAT(mgx3dxs_residual_shift_, R)(ctx, x, b, r, n, h, shift, w, s + MGX_CG_RR);
-            else if (!st) st = MG_CAT(mgx3dxs_residual_, R)(ctx, x, b, r, n, h, MGX_RESIDUAL_CORRECT);
-            if (!st && !ca && shift == 0) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, r, r, NULL, n, w, s + MGX_CG_RR);
+            if (!st) st = MG_CAT(op_residual3_, R)(mg, g, x, b, r, w, s + MGX_CG_RR);
             if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double));
             if (!st && sqrt(rr / rr0) < tol) *converged = 1;
             restart = 1; /* otherwise go on from the true residual */

@@ -71,7 +71,7 @@ template <class real>  // mgx_relax_rr3d.hip
 __attribute__((visibility("hidden"))) bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int mode,
                                                                 real* coarse_f, const int cn[3], int fzoff, int czoff, int pzbeg, int pzend);
 
-// dev_sum[s] = the sum of work[s * count .. (s + 1) * count) for s < nsums, in a fixed order (mgx_krylov3d.hip; also used by mgx_shift3d.hip)
+// dev_sum[s] = the sum of work[s * count .. (s + 1) * count) for s < nsums, in a fixed order (mgx_krylov3d.hip; also used by mgx_stencil3d.hpp)
 __attribute__((visibility("hidden"))) int krylov_final(mgx_ctx* ctx, const double* work, size_t count, int nsums, double* dev_sum);
 
 // two consecutive elements of `real` as one vector value

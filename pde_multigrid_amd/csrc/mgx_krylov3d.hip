@@ -2,13 +2,10 @@
 // An addition: the reference has no Krylov solver.
 //
 // All four kernels stream interior points only (boundary and pad entries are neither read as data nor written) and walk the
-// arrays the same way: one wavefront per x-row (y, z), its lanes over the row's storage positions j in [0, P) (the even-x
-// half, then the odd-x half from H on), so every access of a wave is one contiguous run of a half-row.  Each lane handles
-// KJ positions per step, loads first, so that KJ loads per array are in flight.  Reductions are accumulated in double in a
-// fixed order: per lane in loop order, wavefront-wide shuffles, the block's four waves in a fixed order into one partial per
-// block, then cg_final_kernel adds the partials in a fixed order -- the same bits on every run.
+// arrays the same way, the row walk of mgx_stencil3d.hpp, with its fixed-order sums -- the same bits on every run.
 //
-//   laplace_dot3d_xs_kernel   q = A p (A = the CORRECT-mode Laplacian, q = -residual(p, f = 0)), partials of <p, q>
+//   residual_op3d_xs_kernel<real, PlainOp, MODE, true> (mgx_stencil3d.hpp)
+//                             q = A p (A = the CORRECT-mode Laplacian, q = -residual(p, f = 0)), partials of <p, q>
 //   cg_update3d_xs_kernel     [x += alpha p;] r -= alpha q, partials of <r, r>
 //   dot2_3d_xs_kernel         partials of <a, b> and <a, c>
 //   cg_direction3d_xs_kernel  [x += alpha p;] p = z + beta p   (or p = z)
@@ -17,67 +14,30 @@
 //
 // Below them the kernels of the mixed-precision solve (mgMultiGrid3D_f64_PCG_mixed), which read or write the fp32 twin's arrays.
 #include "mgx_internal.hpp"
-#include "mgx_kernels3d.hpp"
+#include "mgx_stencil3d.hpp"
 
 namespace mgx {
 
-constexpr int KJ = 4;          // positions per lane and step
-constexpr int KROWS = 4;       // rows (waves) per block
-constexpr int KSTEP = 64 * KJ; // positions of a row per wave and step
-
-// x of storage position j of an x-split row (pads give x >= sx)
-__device__ __forceinline__ int xs_x(int j, int H) { return j < H ? 2 * j : 2 * (j - H) + 1; }
-
-// the wave's sum into part[wave]; the block then combines its four waves in a fixed order
-__device__ __forceinline__ void wave_sum(double acc, double* part) {
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if (threadIdx.x == 0) part[threadIdx.y] = acc;
-}
-
-template <class real, int MODE>
-__global__ void __launch_bounds__(256) laplace_dot3d_xs_kernel(const real* __restrict__ p, real* __restrict__ q, int sx, int sy,
-                                                               real hx2, real hy2, real hz2, double* __restrict__ partial) {
-    const Geo<XSplit, real> g(sx, sy);
-    const int y = 1 + blockIdx.x * KROWS + threadIdx.y, z = 1 + blockIdx.y;
-    const int H = g.H, P = g.P;
-    const size_t PL = g.PL;
-    double acc = 0.0;
-    if (y < sy - 1) {
-        const size_t row = g.row(y, z);
-        for (int j0 = 0; j0 < P; j0 += KSTEP) {
-            real O[KJ], E[KJ], N[KJ], S[KJ], D[KJ], U[KJ], c[KJ];
-            bool in[KJ];
-#pragma unroll
-            for (int k = 0; k < KJ; k++) {
-                const int j = j0 + k * 64 + threadIdx.x, x = xs_x(j, H);
-                in[k] = j < P && x >= 1 && x <= sx - 2;
-                if (in[k]) {
-                    const size_t i = row + j;
-                    O[k] = p[row + XSplit::pos(x - 1, H)];
-                    E[k] = p[row + XSplit::pos(x + 1, H)];
-                    N[k] = p[i - P];
-                    S[k] = p[i + P];
-                    D[k] = p[i - PL];
-                    U[k] = p[i + PL];
-                    c[k] = p[i];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < KJ; k++)
-                if (in[k]) {
-                    // -residual3d(p, f = 0): the residual's own expression, negated (negation is exact)
-                    const real t = -residual3d_point<real, MODE>(O[k], E[k], N[k], S[k], D[k], U[k], c[k], (real)0, hx2, hy2, hz2);
-                    q[row + j0 + k * 64 + threadIdx.x] = t;
-                    acc += (double)c[k] * (double)t;
-                }
-        }
+// the CORRECT-mode Laplacian, for q = A p alone: the residual's own expression and nothing added (a shift of 0 would change the
+// sign of a zero residual)
+template <class real>
+struct PlainOp {
+    static constexpr bool HAS_A = false, HAS_S = false;
+    real qx, qy, qz;  // as mgx3dxs_residual forms them: residual_scale's, MODE 1, or 3 with exact reciprocals
+    int mode;
+    PlainOp(const mgx_ctx* ctx, const real h[3], real) {
+        const ResidualScale<real> sc = residual_scale<real>(ctx, h, MGX_RESIDUAL_CORRECT);
+        qx = sc.qx, qy = sc.qy, qz = sc.qz, mode = sc.mode;
     }
-    __shared__ double part[1][KROWS];
-    wave_sum(acc, part[0]);
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0)
-        partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
-}
+    template <class F>
+    static void with_mode(int mode, F&& f) {
+        with_value<1, 3>(mode, f);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>&) const {
+        return residual3d_point<real, MODE>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, qx, qy, qz);
+    }
+};
 
 template <class real, bool X>
 __global__ void __launch_bounds__(256) cg_update3d_xs_kernel(real* __restrict__ x, const real* __restrict__ p, real* __restrict__ r,
@@ -118,11 +78,8 @@ __global__ void __launch_bounds__(256) cg_update3d_xs_kernel(real* __restrict__ 
                 }
         }
     }
-    __shared__ double part[1][KROWS];
-    wave_sum(acc, part[0]);
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0)
-        partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
+    __shared__ double part[KROWS];
+    block_sum(acc, part, partial);
 }
 
 // partials of <a, b> at partial[block] and, with TWO, of <a, c> at partial[nblocks + block]
@@ -314,11 +271,8 @@ __global__ void __launch_bounds__(256) cg_update_demote3d_xs_kernel(double* __re
                 }
         }
     }
-    __shared__ double part[1][KROWS];
-    wave_sum(acc, part[0]);
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0)
-        partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
+    __shared__ double part[KROWS];
+    block_sum(acc, part, partial);
 }
 
 // partials of <z, b> at partial[block] and, with TWO, of <z, c> at partial[nblocks + block]
@@ -541,18 +495,8 @@ __global__ void __launch_bounds__(64 * TYW)
 }
 
 // ------------------------------------------------------------------ host side
-static int krylov_check(const int n[3], const char* what) {
-    MGX_REQUIRE(n, MGX_ERR_INVALID, "%s: NULL size", what);
-    for (int d = 0; d < 3; d++)
-        MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "%s: size[%d] = %d is not odd and >= 3", what, d, n[d]);
-    MGX_REQUIRE(n[2] - 2 <= 65535, MGX_ERR_SIZE, "%s: %d planes are too many", what, n[2]);
-    return MGX_OK;
-}
-static dim3 krylov_grid(const int n[3]) { return dim3((unsigned)ceil_div(n[1] - 2, KROWS), (unsigned)(n[2] - 2)); }
-static dim3 krylov_block() { return dim3(64, KROWS, 1); }
-
 size_t krylov_work_elems(const int n[3]) {
-    if (krylov_check(n, "krylov_work_elems")) return 0;
+    if (rows_check(n, "krylov_work_elems")) return 0;
     const dim3 g = krylov_grid(n);
     return 2 * (size_t)g.x * g.y;
 }
@@ -564,26 +508,11 @@ int krylov_final(mgx_ctx* ctx, const double* work, size_t count, int nsums, doub
 }
 
 template <class real>
-int laplace_dot3d(mgx_ctx* ctx, const real* p, real* q, const int n[3], const real h[3], double* dev_work, double* dev_sum) {
-    MGX_REQUIRE(ctx && p && q && h && dev_work && dev_sum, MGX_ERR_INVALID, "laplace_dot: NULL argument");
-    MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "laplace_dot"));
-    const ResidualScale<real> s = residual_scale<real>(ctx, h, MGX_RESIDUAL_CORRECT);  // as mgx3dxs_residual forms them: MODE 1 or 3
-    const dim3 g = krylov_grid(n);
-    with_value<1, 3>(s.mode, [&](auto m) __attribute__((always_inline)) {
-        MGX_LAUNCH((laplace_dot3d_xs_kernel<real, decltype(m)::value>), g, krylov_block(), 0, ctx->compute, p, q, n[0], n[1], s.qx, s.qy,
-                   s.qz, dev_work);
-    });
-    MGX_LAUNCH_CHECK();
-    return krylov_final(ctx, dev_work, (size_t)g.x * g.y, 1, dev_sum);
-}
-
-template <class real>
 int cg_update3d(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3], const double* dev_alpha, double* dev_work,
                 double* dev_sum) {
     MGX_REQUIRE(ctx && r && q && (!x || p) && dev_alpha && dev_work && dev_sum, MGX_ERR_INVALID, "cg_update: NULL argument");
     MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "cg_update"));
+    MGX_TRY_RET(rows_check(n, "cg_update"));
     const dim3 g = krylov_grid(n);
     if (x) MGX_LAUNCH((cg_update3d_xs_kernel<real, true>), g, krylov_block(), 0, ctx->compute, x, p, r, q, n[0], n[1], dev_alpha, dev_work);
     else MGX_LAUNCH((cg_update3d_xs_kernel<real, false>), g, krylov_block(), 0, ctx->compute, x, p, r, q, n[0], n[1], dev_alpha, dev_work);
@@ -595,7 +524,7 @@ template <class real>
 int dot2_3d(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3], double* dev_work, double* dev_sum) {
     MGX_REQUIRE(ctx && a && b && dev_work && dev_sum, MGX_ERR_INVALID, "dot2: NULL argument");
     MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "dot2"));
+    MGX_TRY_RET(rows_check(n, "dot2"));
     const dim3 g = krylov_grid(n);
     if (c) MGX_LAUNCH((dot2_3d_xs_kernel<real, true>), g, krylov_block(), 0, ctx->compute, a, b, c, n[0], n[1], dev_work);
     else MGX_LAUNCH((dot2_3d_xs_kernel<real, false>), g, krylov_block(), 0, ctx->compute, a, b, c, n[0], n[1], dev_work);
@@ -608,7 +537,7 @@ int cg_direction3d(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3]
     MGX_REQUIRE(ctx && p && (!x || dev_alpha), MGX_ERR_INVALID, "cg_direction: NULL argument");
     MGX_REQUIRE(x || z, MGX_ERR_INVALID, "cg_direction: nothing to do (x and z are NULL)");
     MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "cg_direction"));
+    MGX_TRY_RET(rows_check(n, "cg_direction"));
     const dim3 g = krylov_grid(n);
 #define MGX_DIR(X, P_, B)                                                                                                     \
     MGX_LAUNCH((cg_direction3d_xs_kernel<real, X, P_, B>), g, krylov_block(), 0, ctx->compute, x, p, z, n[0], n[1], dev_alpha, \
@@ -656,7 +585,7 @@ static CrdPlan crd_plan(const mgx_ctx* ctx, const int n[3], const double h[3], b
 // partials any mixed kernel writes: the Krylov kernels' count or the z-marching pass's at its smallest tiles (2 rows per wave,
 // one plane per run), whichever is larger
 size_t mixed_work_elems(const int n[3]) {
-    if (krylov_check(n, "mixed_work_elems")) return 0;
+    if (rows_check(n, "mixed_work_elems")) return 0;
     const size_t crd = (size_t)ceil_div(std::max((n[0] + 1) / 2 - 1, 1), 63) * ceil_div(n[1] - 2, 2 * CRD_TYW) * (size_t)(n[2] - 2);
     return std::max(krylov_work_elems(n), crd);
 }
@@ -664,7 +593,7 @@ size_t mixed_work_elems(const int n[3]) {
 int demote3d(mgx_ctx* ctx, const double* r, float* r32, double s, const int n[3]) {
     MGX_REQUIRE(ctx && r && r32, MGX_ERR_INVALID, "demote: NULL argument");
     MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "demote"));
+    MGX_TRY_RET(rows_check(n, "demote"));
     MGX_LAUNCH(demote3d_xs_kernel, krylov_grid(n), krylov_block(), 0, ctx->compute, r, r32, n[0], n[1], s);
     MGX_LAUNCH_CHECK();
     return MGX_OK;
@@ -674,7 +603,7 @@ int cg_update_demote3d(mgx_ctx* ctx, double* x, const double* p, double* r, cons
                        const double* dev_alpha, double* dev_work, double* dev_sum) {
     MGX_REQUIRE(ctx && r && q && r32 && (!x || p) && dev_alpha && dev_work && dev_sum, MGX_ERR_INVALID, "cg_update_demote: NULL argument");
     MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "cg_update_demote"));
+    MGX_TRY_RET(rows_check(n, "cg_update_demote"));
     const dim3 g = krylov_grid(n);
     if (x) MGX_LAUNCH(cg_update_demote3d_xs_kernel<true>, g, krylov_block(), 0, ctx->compute, x, p, r, q, r32, n[0], n[1], s, dev_alpha, dev_work);
     else MGX_LAUNCH(cg_update_demote3d_xs_kernel<false>, g, krylov_block(), 0, ctx->compute, x, p, r, q, r32, n[0], n[1], s, dev_alpha, dev_work);
@@ -686,7 +615,7 @@ int dot2_mixed3d(mgx_ctx* ctx, const float* z32, double inv_s, const double* b, 
                  double* dev_sum) {
     MGX_REQUIRE(ctx && z32 && b && dev_work && dev_sum, MGX_ERR_INVALID, "dot2_mixed: NULL argument");
     MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "dot2_mixed"));
+    MGX_TRY_RET(rows_check(n, "dot2_mixed"));
     const dim3 g = krylov_grid(n);
     if (c) MGX_LAUNCH(dot2_mixed3d_xs_kernel<true>, g, krylov_block(), 0, ctx->compute, z32, inv_s, b, c, n[0], n[1], dev_work);
     else MGX_LAUNCH(dot2_mixed3d_xs_kernel<false>, g, krylov_block(), 0, ctx->compute, z32, inv_s, b, c, n[0], n[1], dev_work);
@@ -698,7 +627,7 @@ int cg_direction_mixed3d(mgx_ctx* ctx, double* x, double* p, const float* z32, d
                          const double* dev_beta) {
     MGX_REQUIRE(ctx && p && z32 && (!x || dev_alpha), MGX_ERR_INVALID, "cg_direction_mixed: NULL argument");
     MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "cg_direction_mixed"));
+    MGX_TRY_RET(rows_check(n, "cg_direction_mixed"));
     const dim3 g = krylov_grid(n);
 #define MGX_DIR(X, B) \
     MGX_LAUNCH((cg_direction_mixed3d_xs_kernel<X, B>), g, krylov_block(), 0, ctx->compute, x, p, z32, inv_s, n[0], n[1], dev_alpha, dev_beta)
@@ -716,7 +645,7 @@ int correct_residual_demote3d(mgx_ctx* ctx, const double* x, double* xo, const d
     MGX_REQUIRE(ctx && x && b && r32 && h && dev_work && dev_sum, MGX_ERR_INVALID, "correct_residual_demote: NULL argument");
     MGX_REQUIRE(!z32 || (xo && xo != x), MGX_ERR_INVALID, "correct_residual_demote: the correction needs an output array xo != x");
     MGX_USE(ctx);
-    MGX_TRY_RET(krylov_check(n, "correct_residual_demote"));
+    MGX_TRY_RET(rows_check(n, "correct_residual_demote"));
     const CrdPlan p = crd_plan(ctx, n, h, z32 != nullptr);
     bool corr = z32 != nullptr;
     if (p.launches == 2) {  // the two-launch form: a streaming correction, then the pass without it
@@ -743,7 +672,7 @@ int correct_residual_demote3d(mgx_ctx* ctx, const double* x, double* xo, const d
 // what correct_residual_demote3d launches: the plan it launches from
 int correct_residual_demote_plan3d(const mgx_ctx* ctx, const int n[3], const double h[3], int with_correction, int* out) {
     MGX_REQUIRE(ctx && h && out, MGX_ERR_INVALID, "correct_residual_demote_plan: NULL argument");
-    MGX_TRY_RET(krylov_check(n, "correct_residual_demote_plan"));
+    MGX_TRY_RET(rows_check(n, "correct_residual_demote_plan"));
     const CrdPlan p = crd_plan(ctx, n, h, with_correction != 0);
     out[MGX_CRD_ROWS] = p.TR;
     out[MGX_CRD_ZCHUNK] = p.zchunk;
@@ -772,7 +701,7 @@ int mgx_cg_scalars(mgx_ctx* ctx, double* dev_state, int step) {
     size_t mgx3dxs_krylov_work_elems_##SFX(const int n[3]) { return mgx::krylov_work_elems(n); }                                \
     int mgx3dxs_laplace_dot_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3], const real h[3], double* dev_work,       \
                                   double* dev_sum) {                                                                          \
-        return mgx::laplace_dot3d<real>(ctx, p, q, n, h, dev_work, dev_sum);                                                  \
+        return mgx::apply_op_dot3d<mgx::PlainOp<real>, real>(ctx, p, nullptr, q, n, h, (real)0, dev_work, dev_sum, "laplace_dot");\
     }                                                                                                                         \
     int mgx3dxs_cg_update_##SFX(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3],                  \
                                 const double* dev_alpha, double* dev_work, double* dev_sum) {                                 \

@@ -182,6 +182,38 @@ def test_apply_coef_dot(ctx, n3, rg, s, dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("n3", [(21, 13, 29), (131, 7, 9), (513, 33, 9)])
+def test_relax_rows_knob_lowers_the_coefficient_pass_only(ctx, n3, dtype):
+    """"relax3d.rows" below 4 lowers the rows per lane of the coefficient's colour pass (same bits) and is not read by the shifted
+    one.  The pass then halves its rows while four waves of them exceed the level's interior rows, as with the default: 11
+    interior rows take at most 2 rows per lane, 5 take 1, and only the 31 of the last shape take every value as set."""
+    s, rng = 0.75, RG
+    v, f, a = _rand(n3, dtype, 1), _rand(n3, dtype, 2), _coef(n3, dtype)
+    coef, ct = _fn("relax_coef", dtype)
+    shift, _ = _fn("relax_shift", dtype)
+    want, want_shift = CO.relax(n3, rng, v, f, a, s, 1, dtype), SH.relax(n3, rng, v, f, s, 1, dtype)
+    ups, outs = run_poisoned(ctx, [v, f], lambda x, b: shift(ctx._h, x, b, _ip(n3), _h(n3, rng, dtype), ct(s), C.c_int(1)), dtype)
+    default_shift = ctx.last_relax_kernel()
+    assert default_shift.startswith("relax_shift3d_xs_kernel") and bits_equal(xs_unpack(outs[0], n3[0]), want_shift)
+    try:
+        for knob in (1, 2):
+            ctx.set_param("relax3d.rows", knob)
+            rows = knob
+            while rows > 1 and 4 * rows > n3[1] - 2:
+                rows //= 2
+            ups, outs = run_poisoned(ctx, [v, f, a], lambda x, b, c: coef(ctx._h, x, b, c, _ip(n3), _h(n3, rng, dtype), ct(s), C.c_int(1)), dtype)
+            name = ctx.last_relax_kernel()
+            assert name.startswith("relax_coef3d_xs_kernel") and int(name.rstrip(">").split(",")[2]) == rows, (knob, rows, name)
+            assert bits_equal(xs_unpack(outs[0], n3[0]), want), knob
+            assert pads_unchanged(ups[0], outs[0], n3[0]) and bits_equal(outs[1], ups[1]) and bits_equal(outs[2], ups[2])
+            ups, outs = run_poisoned(ctx, [v, f], lambda x, b: shift(ctx._h, x, b, _ip(n3), _h(n3, rng, dtype), ct(s), C.c_int(1)), dtype)
+            assert ctx.last_relax_kernel() == default_shift, (knob, ctx.last_relax_kernel(), default_shift)
+            assert bits_equal(xs_unpack(outs[0], n3[0]), want_shift), knob
+    finally:
+        ctx.set_param("relax3d.rows", 4)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_kernels_reject_bad_shifts_and_sizes(ctx, dtype):
     n3 = (17, 9, 9)
     a = _coef(n3, dtype)

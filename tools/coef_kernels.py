@@ -3,9 +3,11 @@
 a = 1 + 0.5 sin(2 pi x) cos(pi y) + 0.25 z.
 
 --mode kernels (for rocprofv3, counters off): on the same --n^3 arrays, in one process, alternating, --reps times each after
---warmup rounds: one sweep of mgx3dxs_relax_coef (two launches of relax_coef3d_xs_kernel) with four and with two rows per lane
-("relax3d.rows") against one sweep of mgx3dxs_relax_shift (two launches of relax_shift3d_xs_kernel), then mgx3dxs_residual_coef
-(r and the sum) and mgx3dxs_apply_coef_dot.
+--warmup rounds: one sweep of mgx3dxs_relax_coef (two launches of the colour pass) with four and with two rows per lane
+("relax3d.rows") against one sweep of mgx3dxs_relax_shift (two launches of the colour pass), then mgx3dxs_residual_coef
+(r and the sum) and mgx3dxs_apply_coef_dot.  The kernels are the shared templates of csrc/mgx_stencil3d.hpp; the profiler lists
+them as relax_op3d_xs_kernel<double, mgx::CoefOp<double>, 4, R> and <double, mgx::ShiftOp<double>, 4, 4>, and
+residual_op3d_xs_kernel<double, mgx::CoefOp<double>, 1, false> (residual_coef) and <..., 1, true> (apply_coef_dot).
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/coef_kernels.py --mode kernels
 

@@ -2,8 +2,9 @@
 """Workloads behind DESIGN.md 13 (the shifted operator), fp64 on the unit cube.
 
 --mode kernels (for rocprofv3, counters off): on the same --n^3 arrays, in one process, alternating, --reps times each after
---warmup rounds: one sweep of mgx3dxs_relax_shift (two launches of relax_shift3d_xs_kernel) against one sweep of the plain
-mgx3dxs_relax (two colour passes of whichever kernel the level takes), and mgx3dxs_residual_restrict_shift against
+--warmup rounds: one sweep of mgx3dxs_relax_shift (two launches of the colour pass of csrc/mgx_stencil3d.hpp, which the
+profiler lists as relax_op3d_xs_kernel<double, mgx::ShiftOp<double>, 4, 4>) against one sweep of the plain mgx3dxs_relax (two
+colour passes of whichever kernel the level takes), and mgx3dxs_residual_restrict_shift against
 mgx3dxs_residual_restrict_keep_rim.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/shift_kernels.py --mode kernels
