@@ -140,7 +140,13 @@ typedef struct mgGraphFlags {
         double* pcg_state;                                                                               \
         double* pcg_work;                                                                                \
         void* pcg_graph_exec;                                                                            \
-        long long pcg_graph_key; /* unused: kept so that the members after it keep their offsets */     \
+        /* the mask of the homogeneous Neumann faces (an addition; bit 0 x-low, 1 x-high, 2 y-low,       */ \
+        /* 3 y-high, 4 z-low, 5 z-high; default 0 = Dirichlet data on all six faces, and every call then */ \
+        /* does what it did without it).  Set it through _set_boundary.  The two ints take the eight     */ \
+        /* bytes of the unused pcg_graph_key that stood here: the struct keeps its size, every member    */ \
+        /* its offset, and `shift` stays the last one.                                                   */ \
+        int bc;                                                                                          \
+        int bc_reserved; /* unused, 0 */                                                                 \
         /* internal: the record each graph was captured under and the rim flags its capture left behind  */ \
         /* (graph_key[] above is unused likewise)                                                        */ \
         mgGraphRec graph_rec[MG_MAX_LEVELS];                                                             \
@@ -165,6 +171,25 @@ typedef struct mgGraphFlags {
         /* Appended last: every older member keeps its offset.                                           */ \
         real shift;                                                                                      \
     } mgMultiGrid3D_##R;                                                                                 \
+    /* Homogeneous Neumann faces (an addition; mgx3dxs_*_bc of mgx.h).  neumann[k] != 0   */ \
+    /* makes face k (x-low, x-high, y-low, y-high, z-low, z-high) a wall with du/dn = 0 on EVERY level:  */ \
+    /* its points, but for those on a Dirichlet face too, become unknowns, and d_v there is no longer    */ \
+    /* data but part of the solution.  Relax, CalculateResidual (ResidualNorm, download_residual),       */ \
+    /* Restrict, Interpolate, VCycle, FullMultiGridVCycle, PCG(krylov = 0) and BackwardEuler(krylov = 0) */ \
+    /* then run the _bc kernels with the hierarchy's coefficient and shift (the plain Laplacian as the   */ \
+    /* shifted kernels with s = 0): per level relax, the residual stored into d_r, restrict_bc into the  */ \
+    /* coarse d_f, the coarser levels from a zero fill of all points, interpolate_correct_bc, relax --   */ \
+    /* no from-zero shortcut, none of the fused routes.  ResidualNorm and PCG's stopping rule sum over   */ \
+    /* all unknowns, unweighted.  That needs layout = 1, smoother = 0, residual_mode =                   */ \
+    /* MGX_RESIDUAL_CORRECT and a hierarchy that is not semi-coarsened (else MGX_ERR_INVALID, here and   */ \
+    /* where the mask is used); all six faces with shift == 0 is singular and MGX_ERR_INVALID where the  */ \
+    /* operator is used; PCG(krylov != 0) and PCG_mixed return MGX_ERR_INVALID.  A prescribed flux g     */ \
+    /* (du/dn = g, outward) is not an argument: subtract 2 g a / h from f at the face.  All zeros: the   */ \
+    /* hierarchy is what it was without a mask.  A change of the mask drops the captured graphs and      */ \
+    /* zeroes, on the levels below the finest, the entries of d_v the old mask made unknowns.  Blocking. */ \
+    /* The mask is the member `bc` (bit k = neumann[k]).                                                 */ \
+    int mgMultiGrid3D_##R##_set_boundary(mgMultiGrid3D_##R* mg, const int neumann[6]);                   \
+    int mgMultiGrid3D_##R##_get_boundary(const mgMultiGrid3D_##R* mg, int neumann[6]);                   \
     /* shift must be finite and >= 0, and a non-zero one needs the settings named at the member          */ \
     int mgMultiGrid3D_##R##_set_shift(mgMultiGrid3D_##R* mg, real shift);                                \
     size_t mgMultiGrid3D_##R##_sizeof(void); /* sizeof(mgMultiGrid3D_<r>): for mirrors of the struct */  \

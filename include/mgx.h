@@ -599,7 +599,49 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
                                     double* dev_sumsq);                                                 \
     int mgx3dxs_apply_coef_dot_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q,               \
                                      const int n[3], const real h[3], real s, double* dev_work,         \
-                                     double* dev_sum);
+                                     double* dev_sum);                                                  \
+    /* ---- homogeneous Neumann faces for the two operators above, x-split layout (csrc/mgx_rim3d.hip,  */ \
+    /* DESIGN.md 15).  An addition.  bc is a mask of six bits -- bit 0 x-low, 1 x-high, 2 y-low,        */ \
+    /* 3 y-high, 4 z-low, 5 z-high -- and a set bit makes that face homogeneous Neumann, du/dn = 0      */ \
+    /* (a mirrored too).  A point is an UNKNOWN when it is interior, or lies on one or more Neumann     */ \
+    /* faces and on no Dirichlet face (Dirichlet wins on shared edges and corners; Dirichlet entries    */ \
+    /* of v are data and are never written).  At an unknown on a face every operator is the interior's  */ \
+    /* point expression on a star whose out-of-range entry is replaced by the opposite one (x-low:      */ \
+    /* O := E, for v and for a; edges and corners: on each axis).  A prescribed flux g enters through   */ \
+    /* f, f -= 2 g a / h at the face for the outward derivative du/dn = g; no entry takes g.            */ \
+    /* Each entry is the entry without _bc, argument for argument, plus the mask; with bc = 0 it does   */ \
+    /* exactly what that entry does, bit for bit.  Otherwise the interior kernels run unchanged and     */ \
+    /* each is followed by one launch over the face unknowns of all six faces (a colour pass: the       */ \
+    /* interior launch, then the face launch of that colour).  MGX_ERR_INVALID for NULL arguments, a    */ \
+    /* bc outside 0 .. 63 or a bad shift, MGX_ERR_SIZE for bad sizes; pads are neither written nor read */ \
+    /* as data; f and a are never written.                                                              */ \
+    /* residual_*_bc: r is stored at every unknown and is 0 at the Dirichlet points; *dev_sumsq = the   */ \
+    /*   unweighted sum over ALL unknowns, in double, in a fixed order (the same bits on every run);    */ \
+    /*   dev_work: mgx3dxs_krylov_work_elems doubles as before.                                         */ \
+    /* restrict_bc: a coarse unknown on a face is the full weighting of the 27 reflected fine values;   */ \
+    /*   coarse Dirichlet points keep injection.  interpolate(_correct)_bc: the interpolation formula   */ \
+    /*   at the fine face unknowns too; it reads coarse points of the same face only.                   */ \
+    /* shift_rhs_bc: shift_rhs on the face unknowns too.                                                */ \
+    /* set_rim_bc: v := value on the face unknowns, nothing else (bc = 0: nothing at all).              */ \
+    int mgx3dxs_relax_shift_bc_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3],              \
+                                     const real h[3], real s, int ncycles, int bc);                     \
+    int mgx3dxs_relax_coef_bc_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,                \
+                                    const int n[3], const real h[3], real s, int ncycles, int bc);      \
+    int mgx3dxs_residual_shift_bc_##SFX(mgx_ctx* ctx, const real* v, const real* f, real* r,            \
+                                        const int n[3], const real h[3], real s, double* dev_work,      \
+                                        double* dev_sumsq, int bc);                                     \
+    int mgx3dxs_residual_coef_bc_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a,       \
+                                       real* r, const int n[3], const real h[3], real s,                \
+                                       double* dev_work, double* dev_sumsq, int bc);                    \
+    int mgx3dxs_restrict_bc_##SFX(mgx_ctx* ctx, const real* fine, const int fn[3], real* coarse,        \
+                                  const int cn[3], int bc);                                             \
+    int mgx3dxs_interpolate_bc_##SFX(mgx_ctx* ctx, real* fine, const int fn[3], const real* coarse,     \
+                                     const int cn[3], int bc);                                          \
+    int mgx3dxs_interpolate_correct_bc_##SFX(mgx_ctx* ctx, real* v, const int n[3],                     \
+                                             const real* coarse_v, const int cn[3], int bc);            \
+    int mgx3dxs_shift_rhs_bc_##SFX(mgx_ctx* ctx, const real* u, const real* q, real qscale, real s,     \
+                                   real* f, const int n[3], int bc);                                    \
+    int mgx3dxs_set_rim_bc_##SFX(mgx_ctx* ctx, real* v, const int n[3], real value, int bc);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)

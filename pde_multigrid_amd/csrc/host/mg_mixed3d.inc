@@ -213,6 +213,7 @@ int mgMultiGrid3D_f64_PCG_mixed(mgMultiGrid3D_f64* mg, int v1, int v2, double to
     MG_REQUIRE(mg->shift == 0, MGX_ERR_INVALID, "PCG_mixed: a shifted hierarchy (shift = %g) is not supported", mg->shift);
     MG_REQUIRE(!(mg->grids3D && mg->grids3D[0] && mg->grids3D[0]->d_a), MGX_ERR_INVALID,
                "PCG_mixed: a hierarchy with a coefficient is not supported");
+    MG_REQUIRE(mg->bc == 0, MGX_ERR_INVALID, "PCG_mixed: a hierarchy with Neumann faces (mask %d) is not supported", mg->bc);
     MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "PCG_mixed: needs the x-split layout (layout = 1)");
     MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "PCG_mixed: needs residual_mode = MGX_RESIDUAL_CORRECT");
     MG_REQUIRE(tol > 0 && maxit >= 1 && v1 >= 0 && v2 >= 0 && v1 + v2 >= 1, MGX_ERR_INVALID,

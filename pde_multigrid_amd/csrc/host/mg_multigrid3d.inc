@@ -257,10 +257,33 @@ static int MG_CAT(coef_ok3_, R)(const MGRID* mg, const char* what) {
     return MGX_OK;
 }
 
+/* ---------------------------------------------------------------- homogeneous Neumann faces (the mask mg->bc) */
+/* what the mask bc needs of the hierarchy (the members are public: checked by set_boundary and where the mask is used) */
+static int MG_CAT(bc_ok3_, R)(const MGRID* mg, int bc, const char* what) {
+    if (!bc) return MGX_OK;
+    MG_REQUIRE(bc > 0 && bc <= 63, MGX_ERR_INVALID, "%s: the boundary mask %d is outside 0 .. 63", what, bc);
+    MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "%s: a hierarchy with Neumann faces needs the x-split layout (layout = 1)", what);
+    MG_REQUIRE(mg->smoother == 0, MGX_ERR_INVALID, "%s: a hierarchy with Neumann faces needs the red-black smoother (smoother = 0)", what);
+    MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID,
+               "%s: a hierarchy with Neumann faces needs residual_mode = MGX_RESIDUAL_CORRECT", what);
+    for (int i = 0; i + 1 < mg->maxGrids; i++)
+        MG_REQUIRE(mg->coarsen[i] == 7, MGX_ERR_INVALID, "%s: Neumann faces are not available on a semi-coarsened hierarchy", what);
+    return MGX_OK;
+}
+/* ... and of the operator: a closed box without a shift has no unique solution (checked where the operator is used only: the
+ * shift is a public member and may still change after set_boundary) */
+static int MG_CAT(bc_singular3_, R)(const MGRID* mg, const char* what) {
+    MG_REQUIRE(!(mg->bc == 63 && mg->shift == 0), MGX_ERR_INVALID,
+               "%s: Neumann data on all six faces with shift = 0 is singular (set a shift > 0 or keep a Dirichlet face)", what);
+    return MGX_OK;
+}
+
 /* The operators other than the plain Laplacian: the variable-coefficient one where the hierarchy has a coefficient (with any
  * shift), else the shifted one where shift != 0.  What the hierarchy's operator needs of the hierarchy and of the grid g it is
  * applied to (nothing for the plain one). */
 static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) {
+    MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, what));
+    MG_TRY(MG_CAT(bc_singular3_, R)(mg, what));
     if (!MG_CAT(has_coef3_, R)(mg)) return MG_CAT(shift_ok3_, R)(mg, mg->shift, what);
     MG_TRY(MG_CAT(coef_ok3_, R)(mg, what));
     MG_REQUIRE(g->d_a, MGX_ERR_INVALID, "%s: the grid has no coefficient array", what);
@@ -272,8 +295,9 @@ static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) 
 static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, const REAL* f, REAL* r, double* dev_work, double* dev_sumsq) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
     if (MG_CAT(has_coef3_, R)(mg))
-        return MG_CAT(mgx3dxs_residual_coef_, R)(mg->ctx, v, f, g->d_a, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq);
-    if (mg->shift != 0) return MG_CAT(mgx3dxs_residual_shift_, R)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq);
+        return MG_CAT(mgx3dxs_residual_coef_bc_, R)(mg->ctx, v, f, g->d_a, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc);
+    if (mg->shift != 0 || mg->bc) /* (with a mask the plain Laplacian is the shifted operator with s = 0) */
+        return MG_CAT(mgx3dxs_residual_shift_bc_, R)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc);
     MG_TRY(MGXL(mg, residual)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->residual_mode));
     return dev_sumsq ? MG_CAT(mgx3dxs_dot2_, R)(mg->ctx, r, r, NULL, g->sizeXYZ, dev_work, dev_sumsq) : MGX_OK;
 }
@@ -356,10 +380,40 @@ int FN(download_coefficient)(MGRID* mg, int gridID, REAL* host) {
     return MG_CAT(get3_, R)(mg, g, g->d_a, host);
 }
 
+/* the mask of the Neumann faces (mg_multigrid.h).  The captured graphs are dropped whenever it changes. */
+int FN(set_boundary)(MGRID* mg, const int neumann[6]) {
+    MG_REQUIRE(mg && mg->grids3D && neumann, MGX_ERR_INVALID, "set_boundary: NULL");
+    int bc = 0;
+    for (int k = 0; k < 6; k++)
+        if (neumann[k]) bc |= 1 << k;
+    if (bc == mg->bc) return MGX_OK;
+    MG_TRY(MG_CAT(bc_ok3_, R)(mg, bc, "set_boundary"));
+    MG_TRY(mgx_ctx_sync(mg->ctx)); /* (nothing of a captured cycle is in flight any more) */
+    MG_CAT(coef_drop_graphs3_, R)(mg);
+    /* below the finest level the entries the old mask made unknowns go back to the zeros they were before it */
+    for (int i = 1; mg->bc && i < mg->maxGrids; i++) {
+        GRID* g = mg->grids3D[i];
+        MG_CAT(v_touched3_, R)(mg, g->d_v);
+        MG_TRY(MG_CAT(mgx3dxs_set_rim_bc_, R)(mg->ctx, g->d_v, g->sizeXYZ, (REAL)0, mg->bc));
+    }
+    mg->bc = bc;
+    return mgx_ctx_sync(mg->ctx);
+}
+
+int FN(get_boundary)(const MGRID* mg, int neumann[6]) {
+    MG_REQUIRE(mg && neumann, MGX_ERR_INVALID, "get_boundary: NULL");
+    for (int k = 0; k < 6; k++) neumann[k] = (mg->bc >> k) & 1;
+    return MGX_OK;
+}
+
 int FN(Restrict)(MGRID* mg, const REAL* fine, const int fsizeXYZ[3], REAL* coarse, const int csizeXYZ[3]) {
     MG_REQUIRE(mg, MGX_ERR_INVALID, "Restrict: NULL");
     MG_CAT(f_touched3_, R)(mg, coarse); /* boundary = injection of the fine boundary (:113-119) */
     MG_CAT(v_touched3_, R)(mg, coarse);
+    if (mg->bc) { /* the coarse unknowns on Neumann faces are restricted too */
+        MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "Restrict"));
+        return MG_CAT(mgx3dxs_restrict_bc_, R)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ, mg->bc);
+    }
     if (mg->layout && fsizeXYZ && csizeXYZ && (fsizeXYZ[0] == csizeXYZ[0] || fsizeXYZ[1] == csizeXYZ[1] || fsizeXYZ[2] == csizeXYZ[2]))
         return MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ); /* a semi-coarsened step */
     return MGXL(mg, restrict)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ);
@@ -367,6 +421,11 @@ int FN(Restrict)(MGRID* mg, const REAL* fine, const int fsizeXYZ[3], REAL* coars
 
 int FN(Interpolate)(MGRID* mg, REAL* fine, const int fsizeXYZ[3], const REAL* coarse, const int csizeXYZ[3]) {
     MG_REQUIRE(mg, MGX_ERR_INVALID, "Interpolate: NULL");
+    if (mg->bc) { /* ... and the fine unknowns on Neumann faces */
+        MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "Interpolate"));
+        MG_CAT(v_touched3_, R)(mg, fine);
+        return MG_CAT(mgx3dxs_interpolate_bc_, R)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ, mg->bc);
+    }
     /* interior points only (:202-206): no boundary entry changes */
     if (mg->layout && fsizeXYZ && csizeXYZ && (fsizeXYZ[0] == csizeXYZ[0] || fsizeXYZ[1] == csizeXYZ[1] || fsizeXYZ[2] == csizeXYZ[2]))
         return MG_CAT(mgx3dxs_interpolate_axes_, R)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ); /* a semi-coarsened step */
@@ -381,9 +440,12 @@ int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
         if (mg->grids3D[i] == curGrid) lvl = i;
     MG_TRY(MG_CAT(op_ok3_, R)(mg, curGrid, "Relax"));
     /* the coefficient and the shifted operator: one launch per colour pass; d_e is not used */
+    if (mg->bc) MG_CAT(v_touched3_, R)(mg, curGrid->d_v); /* with a mask each colour pass is followed by its launch over the face unknowns */
     if (MG_CAT(has_coef3_, R)(mg))
-        return MG_CAT(mgx3dxs_relax_coef_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift, ncycles);
-    if (mg->shift != 0) return MG_CAT(mgx3dxs_relax_shift_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles);
+        return MG_CAT(mgx3dxs_relax_coef_bc_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift, ncycles,
+                                                 mg->bc);
+    if (mg->shift != 0 || mg->bc)
+        return MG_CAT(mgx3dxs_relax_shift_bc_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc);
     if (mg->smoother == 1) { /* weighted Jacobi: the error scratch doubles as the ping-pong array */
         if (lvl >= 0) mg->e_rim_valid[lvl] = 0;
         return MGXL(mg, jacobi)(mg->ctx, curGrid->d_v, curGrid->d_e, curGrid->d_f, curGrid->sizeXYZ, h, mg->omega, ncycles);
@@ -441,6 +503,7 @@ static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int 
     s.matrixA_bits[0] = mg_real_bits(&mg->shift, sizeof(REAL)); /* a 3D record has no matrix: the shift's bits (0 without one) */
     s.matrixA_bits[1] = (unsigned long long)(uintptr_t)mg->grids3D[0]->d_a; /* level 0's coefficient array (0 without one): setting or */
                                                                             /* clearing it captures again, new values in it are read  */
+    s.matrixA_bits[2] = (unsigned long long)mg->bc; /* the mask of the Neumann faces (0 without one) */
     MG_TRY(mgx_ctx_generation(mg->ctx, &s.generation));
     for (int k = 0; k < 3; k++)
         for (int i = gridID; i < mg->numGrids; i++) s.flags.a[k][i] = flags[k][i];
@@ -508,7 +571,8 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
     MG_TRY(MG_CAT(op_ok3_, R)(mg, fine, "VCycle"));
     const int coef = MG_CAT(has_coef3_, R)(mg);
     const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
-    if (v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
+    const int bc = mg->bc; /* Neumann faces: no from-zero shortcut (v := 0 on all points, then Relax), the stored-residual route */
+    if (!bc && v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
         if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
         if (coef)
             MG_TRY(MG_CAT(mgx3dxs_relax_coef_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->sizeXYZ, h, mg->shift, v1,
@@ -523,7 +587,10 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
     if (gridID != mg->numGrids - 1) {
         GRID* coarse = mg->grids3D[gridID + 1];
         const int semi = mg->coarsen[gridID] != 7;
-        if (coef) {
+        if (bc) {
+            MG_TRY(MG_CAT(op_residual3_, R)(mg, fine, fine->d_v, fine->d_f, fine->d_r, NULL, NULL)); /* :629 */
+            MG_TRY(MG_CAT(mgx3dxs_restrict_bc_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ, bc)); /* :632 */
+        } else if (coef) {
             MG_TRY(MG_CAT(op_residual3_, R)(mg, fine, fine->d_v, fine->d_f, fine->d_r, NULL, NULL)); /* :629 */
             if (semi) MG_TRY(MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ));
             else MG_TRY(MG_CAT(mgx3dxs_restrict_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ)); /* :632 */
@@ -531,9 +598,12 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
             MG_TRY(MG_CAT(mgx3dxs_residual_restrict_shift_, R)(mg->ctx, fine->d_v, fine->d_f, fine->sizeXYZ, h, mg->shift, coarse->d_f,
                                                                coarse->sizeXYZ, mg->f_rim_zero[gridID + 1])); /* :629-632 */
         }
-        mg->f_rim_zero[gridID + 1] = 1;
+        mg->f_rim_zero[gridID + 1] = !bc; /* (the coarse unknowns on Neumann faces hold restricted residuals) */
         MG_TRY(MG_CAT(vcycle_body3_, R)(mg, gridID + 1, v1, v2, 1)); /* :634-635 */
-        if (semi) MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ));
+        if (bc) {
+            MG_CAT(v_touched3_, R)(mg, fine->d_v);
+            MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_bc_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ, bc));
+        } else if (semi) MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ));
         else MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */
     }
     return FN(Relax)(mg, fine, v2); /* :645 */
@@ -542,7 +612,7 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
 /* VCycle from level gridID down.  v_zero: the level's v counts as all zeros (the coarse error of :634) but has not been
  * zeroed in memory yet -- the one-workgroup tail kernel never reads it, the other levels zero it first. */
 static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
-    if (MG_CAT(has_coef3_, R)(mg) || mg->shift != 0) return MG_CAT(vcycle_op_step3_, R)(mg, gridID, v1, v2, v_zero);
+    if (MG_CAT(has_coef3_, R)(mg) || mg->shift != 0 || mg->bc) return MG_CAT(vcycle_op_step3_, R)(mg, gridID, v1, v2, v_zero);
     GRID* fine = mg->grids3D[gridID];
     const int nlev = mg->numGrids - gridID;
     if (mg->fuse && mg->smoother == 0 && nlev <= 6 && !MG_CAT(semi_below3_, R)(mg, gridID)) { /* levels of at most 17^3: the rest of the cycle in ONE launch */
@@ -660,6 +730,11 @@ int FN(FullMultiGridVCycle)(MGRID* mg, int gridID, int v0, int v1, int v2) {
         MG_TRY(FN(Interpolate)(mg, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :577 */
     } else {
         MG_TRY(FN(setToValue)(mg, fine->d_v, fine->sizeXYZ, (REAL)0, 0)); /* :581 */
+        if (mg->bc) { /* the unknowns on Neumann faces start from zero like the interior; Dirichlet entries stay */
+            MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "FMG"));
+            MG_CAT(v_touched3_, R)(mg, fine->d_v);
+            MG_TRY(MG_CAT(mgx3dxs_set_rim_bc_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, (REAL)0, mg->bc));
+        }
     }
     for (int i = 0; i < v0; i++) MG_TRY(FN(VCycle)(mg, gridID, v1, v2)); /* :583-584 */
     return MGX_OK;
@@ -785,9 +860,11 @@ static int MG_CAT(pcg_true_sumsq3_, R)(MGRID* mg, const REAL* x, const REAL* b, 
     GRID* g = mg->grids3D[0];
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
     if (g->d_a)
-        MG_TRY(MG_CAT(mgx3dxs_residual_coef_, R)(mg->ctx, x, b, g->d_a, NULL, g->sizeXYZ, h, mg->shift, mg->pcg_work, mg->pcg_state + MGX_CG_RR));
-    else if (mg->shift != 0)
-        MG_TRY(MG_CAT(mgx3dxs_residual_shift_, R)(mg->ctx, x, b, NULL, g->sizeXYZ, h, mg->shift, mg->pcg_work, mg->pcg_state + MGX_CG_RR));
+        MG_TRY(MG_CAT(mgx3dxs_residual_coef_bc_, R)(mg->ctx, x, b, g->d_a, NULL, g->sizeXYZ, h, mg->shift, mg->pcg_work,
+                                                    mg->pcg_state + MGX_CG_RR, mg->bc));
+    else if (mg->shift != 0 || mg->bc) /* (with a mask: over all unknowns, unweighted) */
+        MG_TRY(MG_CAT(mgx3dxs_residual_shift_bc_, R)(mg->ctx, x, b, NULL, g->sizeXYZ, h, mg->shift, mg->pcg_work, mg->pcg_state + MGX_CG_RR,
+                                                     mg->bc));
     else
         MG_TRY(MG_CAT(mgx3dxs_residual_sumsq_slab_, R)(mg->ctx, x, b, g->sizeX, g->sizeY, h, MGX_RESIDUAL_CORRECT, 1, g->sizeZ - 1,
                                                        mg->pcg_state + MGX_CG_RR));
@@ -928,6 +1005,10 @@ int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* i
                "PCG: bad arguments (tol %g, maxit %d, v1 %d, v2 %d)", tol, maxit, v1, v2);
     MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "PCG"));
     if (MG_CAT(has_coef3_, R)(mg)) MG_TRY(MG_CAT(coef_ok3_, R)(mg, "PCG"));
+    MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "PCG"));
+    MG_TRY(MG_CAT(bc_singular3_, R)(mg, "PCG"));
+    MG_REQUIRE(!mg->bc || !krylov, MGX_ERR_INVALID,
+               "PCG: krylov != 0 is not available with Neumann faces (the CG vector kernels are interior-only); use krylov = 0");
     *iters = 0;
     *rel_res = 0.0;
     *converged = 0;
@@ -944,6 +1025,9 @@ int FN(BackwardEuler)(MGRID* mg, int nsteps, double dt, double kappa, const REAL
                "BackwardEuler: bad arguments (nsteps %d, dt %g, kappa %g)", nsteps, dt, kappa);
     const REAL s = (REAL)(1.0 / (kappa * dt)), qscale = (REAL)(1.0 / kappa);
     MG_REQUIRE(s > 0, MGX_ERR_INVALID, "BackwardEuler: 1 / (kappa dt) = %g is not a positive number of the hierarchy's precision", (double)s);
+    MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "BackwardEuler"));
+    MG_REQUIRE(!mg->bc || !krylov, MGX_ERR_INVALID,
+               "BackwardEuler: krylov != 0 is not available with Neumann faces (the CG vector kernels are interior-only); use krylov = 0");
     MG_TRY(FN(set_shift)(mg, s)); /* stays set */
     *iters_total = 0;
     *worst_rel_res = 0.0;
@@ -952,8 +1036,9 @@ int FN(BackwardEuler)(MGRID* mg, int nsteps, double dt, double kappa, const REAL
     for (int k = 0; k < nsteps; k++) {
         int it = 0, conv = 0;
         double rel = 0.0;
-        /* interior only: the boundary entries of d_f[0] are read by nobody and stay as they are (f_rim_zero too) */
-        MG_TRY(MG_CAT(mgx3dxs_shift_rhs_, R)(mg->ctx, g->d_v, d_source, qscale, s, g->d_f, g->sizeXYZ));
+        /* the unknowns only: the Dirichlet entries of d_f[0] are read by nobody and stay as they are (f_rim_zero too, without a mask) */
+        if (mg->bc) mg->f_rim_zero[0] = 0;
+        MG_TRY(MG_CAT(mgx3dxs_shift_rhs_bc_, R)(mg->ctx, g->d_v, d_source, qscale, s, g->d_f, g->sizeXYZ, mg->bc));
         MG_TRY(FN(PCG)(mg, v1, v2, tol, maxit, krylov, &it, &rel, &conv, NULL, 0));
         *iters_total += it;
         if (rel > *worst_rel_res || !(rel == rel)) *worst_rel_res = rel;

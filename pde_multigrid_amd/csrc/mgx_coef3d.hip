@@ -14,65 +14,14 @@
 // The conservative 7-point form with arithmetic-mean face coefficients, the 1/2 of each mean folded into q*.  a is read on
 // the boundary too (interior points next to a face read it there) and never written.
 //
-// This file holds the operator's policy, CoefOp; the kernels and their host drivers are the shared ones of mgx_stencil3d.hpp,
+// The operator's policy, CoefOp, is in mgx_ops3d.hpp; the kernels and their host drivers are the shared ones of mgx_stencil3d.hpp,
 // instantiated with the policy:
 //   relax_op3d_xs_kernel<real, CoefOp, TYW, R>     one colour pass ("relax_coef3d_xs_kernel" to last_relax_kernel()), a marched
 //                                                  next to v: per step and row it loads one entry of v, one of f and BOTH entries
 //                                                  of a's pair at plane z+1 (2.5 words per point and pass with the store); no LDS
 //   relax_op_zero3d_xs_kernel<real, CoefOp>        the first red pass on a level that counts as zero: f and a in, red out, v not read
 //   residual_op3d_xs_kernel<real, CoefOp, 1, LAP>  r and / or the partials of <r, r>; with LAP: q = A p and the partials of <p, q>
-#include "mgx_stencil3d.hpp"
-
-namespace mgx {
-
-template <class real>
-__device__ __forceinline__ real relax_coef3d_point(real O, real E, real N, real S, real D, real U, real f, real aO, real aE, real aN, real aS,
-                                                   real aD, real aU, real aC, real qx, real qy, real qz, real s) {
-    const real AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC;
-    const real den = ((qx * (AW + AE) + qy * (AN + AS)) + qz * (AD + AU)) + s;
-    const real num = ((qx * (AW * O + AE * E) + qy * (AN * N + AS * S)) + qz * (AD * D + AU * U)) - f;
-    return num / den;
-}
-
-template <class real>
-__device__ __forceinline__ real residual_coef3d_point(real O, real E, real N, real S, real D, real U, real c, real f, real aO, real aE, real aN,
-                                                      real aS, real aD, real aU, real aC, real qx, real qy, real qz, real s) {
-    const real AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC;
-    const real tx = qx * (AW * (O - c) + AE * (E - c));
-    const real ty = qy * (AN * (N - c) + AS * (S - c));
-    const real tz = qz * (AD * (D - c) + AU * (U - c));
-    return (((f - tx) - ty) - tz) + s * c;
-}
-
-// qx = (real)0.5 / hx2 .. : half the reciprocal squared spacings (the 1/2 of the face means)
-template <class real>
-struct CoefOp {
-    static constexpr bool HAS_A = true, HAS_S = true;
-    static constexpr const char *relax_kernel = "relax_coef3d_xs_kernel", *zero_kernel = "relax_coef_zero3d_xs_kernel";
-    static constexpr int mode = 1;  // (the expressions divide by nothing the host could invert: one MODE)
-    real qx, qy, qz, s;
-    CoefOp(const mgx_ctx*, const real h[3], real s_) : s(s_) {
-        const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
-        qx = (real)0.5 / hx2;
-        qy = (real)0.5 / hy2;
-        qz = (real)0.5 / hz2;
-    }
-    // "relax3d.rows" below 4 lowers the rows per lane (fp64 with four rows: 124 VGPRs, four waves per SIMD; with two: 74, six)
-    static int rows(const mgx_ctx* ctx) { return ctx->relax_rows < 4 ? ctx->relax_rows : 4; }
-    template <class F>
-    static void with_mode(int, F&& f) {
-        f(std::integral_constant<int, 1>());
-    }
-    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>& a) const {
-        return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, s);
-    }
-    template <int MODE>
-    __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a) const {
-        return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, s);
-    }
-};
-
-}  // namespace mgx
+#include "mgx_ops3d.hpp"
 
 #define MGX_COEF3D_API(SFX, real)                                                                                                            \
     extern "C" int mgx3dxs_relax_coef_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s,    \

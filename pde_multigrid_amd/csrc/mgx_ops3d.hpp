@@ -1,0 +1,101 @@
+// mgx_ops3d.hpp -- the operator policies of mgx_stencil3d.hpp that more than one file instantiates: ShiftOp, (Laplacian - s) u = f
+// (its arithmetic is described in mgx_shift3d.hip), and CoefOp, div(a grad u) - s u = f (mgx_coef3d.hip,
+// section 14).  mgx_shift3d.hip and mgx_coef3d.hip build the interior kernels from them, mgx_rim3d.hip the kernels of the
+// Neumann faces (section 15): the point expressions exist once.
+#pragma once
+#include "mgx_stencil3d.hpp"
+
+namespace mgx {
+
+template <class real>
+__device__ __forceinline__ real relax_shift3d_point(real O, real E, real N, real S, real D, real U, real f, real hx2, real hy2, real hz2,
+                                                    real den, double rd) {
+    const real num = O * (hy2 * hz2) + E * (hy2 * hz2) + N * (hx2 * hz2) + S * (hx2 * hz2) + D * (hx2 * hy2) + U * (hx2 * hy2) -
+                     f * hx2 * hy2 * hz2;
+    if constexpr (sizeof(real) == 4) {
+        real q = (real)((double)num * rd);
+        if (__builtin_expect(!(__builtin_fabsf(q) >= 1.17549435e-38f), 0)) q = num / den;
+        return q;
+    } else {
+        return num / den;
+    }
+}
+
+// den and, for fp32's route, rd = 1 / den in double are the same for every point of a level
+template <class real>
+struct ShiftOp {
+    static constexpr bool HAS_A = false, HAS_S = true;
+    static constexpr const char *relax_kernel = "relax_shift3d_xs_kernel", *zero_kernel = "relax_shift_zero3d_xs_kernel";
+    real hx2, hy2, hz2, den;  // the smoother's
+    double rd;
+    real qx, qy, qz, s;  // the residual's: residual_scale's, MODE 1, or 3 with exact reciprocals
+    int mode;
+    ShiftOp(const mgx_ctx* ctx, const real h[3], real s_) : s(s_) {
+        const ResidualScale<real> sc = residual_scale<real>(ctx, h, MGX_RESIDUAL_CORRECT);
+        hx2 = sc.hx2, hy2 = sc.hy2, hz2 = sc.hz2;
+        den = 2 * (hy2 * hz2 + hx2 * hz2 + hx2 * hy2) + s * hx2 * hy2 * hz2;
+        rd = sizeof(real) == 4 ? 1.0 / (double)den : 0.0;
+        qx = sc.qx, qy = sc.qy, qz = sc.qz, mode = sc.mode;
+    }
+    static int rows(const mgx_ctx*) { return 4; }  // ("relax3d.rows" is not read)
+    template <class F>
+    static void with_mode(int mode, F&& f) {
+        with_value<1, 3>(mode, f);
+    }
+    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>&) const {
+        return relax_shift3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, hx2, hy2, hz2, den, rd);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>&) const {
+        return residual3d_point<real, MODE>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, qx, qy, qz) + s * v.C;
+    }
+};
+
+template <class real>
+__device__ __forceinline__ real relax_coef3d_point(real O, real E, real N, real S, real D, real U, real f, real aO, real aE, real aN, real aS,
+                                                   real aD, real aU, real aC, real qx, real qy, real qz, real s) {
+    const real AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC;
+    const real den = ((qx * (AW + AE) + qy * (AN + AS)) + qz * (AD + AU)) + s;
+    const real num = ((qx * (AW * O + AE * E) + qy * (AN * N + AS * S)) + qz * (AD * D + AU * U)) - f;
+    return num / den;
+}
+
+template <class real>
+__device__ __forceinline__ real residual_coef3d_point(real O, real E, real N, real S, real D, real U, real c, real f, real aO, real aE, real aN,
+                                                      real aS, real aD, real aU, real aC, real qx, real qy, real qz, real s) {
+    const real AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC;
+    const real tx = qx * (AW * (O - c) + AE * (E - c));
+    const real ty = qy * (AN * (N - c) + AS * (S - c));
+    const real tz = qz * (AD * (D - c) + AU * (U - c));
+    return (((f - tx) - ty) - tz) + s * c;
+}
+
+// qx = (real)0.5 / hx2 .. : half the reciprocal squared spacings (the 1/2 of the face means)
+template <class real>
+struct CoefOp {
+    static constexpr bool HAS_A = true, HAS_S = true;
+    static constexpr const char *relax_kernel = "relax_coef3d_xs_kernel", *zero_kernel = "relax_coef_zero3d_xs_kernel";
+    static constexpr int mode = 1;  // (the expressions divide by nothing the host could invert: one MODE)
+    real qx, qy, qz, s;
+    CoefOp(const mgx_ctx*, const real h[3], real s_) : s(s_) {
+        const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
+        qx = (real)0.5 / hx2;
+        qy = (real)0.5 / hy2;
+        qz = (real)0.5 / hz2;
+    }
+    // "relax3d.rows" below 4 lowers the rows per lane (fp64 with four rows: 124 VGPRs, four waves per SIMD; with two: 74, six)
+    static int rows(const mgx_ctx* ctx) { return ctx->relax_rows < 4 ? ctx->relax_rows : 4; }
+    template <class F>
+    static void with_mode(int, F&& f) {
+        f(std::integral_constant<int, 1>());
+    }
+    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>& a) const {
+        return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, s);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a) const {
+        return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, s);
+    }
+};
+
+}  // namespace mgx

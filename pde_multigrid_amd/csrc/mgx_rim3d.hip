@@ -1,0 +1,358 @@
+// mgx_rim3d.hip -- homogeneous NEUMANN faces for the shifted and the variable-coefficient operator, x-split layout.  DESIGN.md
+// section 15.
+//
+// A mask bc of six bits (bit 0 x-low, 1 x-high, 2 y-low, 3 y-high, 4 z-low, 5 z-high) makes the faces whose bit is set
+// homogeneous Neumann, du/dn = 0.  A grid point is an UNKNOWN when it is interior, or when it lies on one or more Neumann faces
+// and on no Dirichlet face (Dirichlet wins on shared edges and corners; Dirichlet entries of v are data and are never written).
+// At an unknown on a face every operator is the interior's point expression on a star whose out-of-range entry is replaced by the
+// opposite one (on x-low O := E, for v and for a; on an edge or corner on each axis): there is no new point arithmetic here, the
+// kernels call Op::relax / Op::residual<MODE> (mgx_ops3d.hpp), restrict3d_point and interpolate3d_point (mgx_kernels3d.hpp) on
+// reflected indices.
+//
+// The tuned interior kernels run unchanged; every entry below is the existing entry followed by (the colour passes: interleaved
+// with) a RIM launch over the face unknowns, all six faces of a call in one launch.  Points of one colour are independent and the
+// rim launch of a colour reads only points of the other colour, so a colour pass is the interior launch plus the rim launch of that
+// colour, in stream order.  With bc = 0 nothing but the existing entry runs.
+//
+// The rim launch: a 1-D grid whose threads stride over the list of face points -- the two z-faces as whole planes (row pitch P
+// positions per row: the lanes of a wave run along a row's storage positions, pads skipped), the two y-faces as whole rows of the
+// planes 1 .. sz-2, the two x-faces as the points (y, z) of the open square, the lanes along y.  The x-faces are the first and the
+// last entry of a row's even-x half: one line per point whatever the lane order; with the lanes along y the rows above and below
+// are the neighbouring lanes' own lines.  Only the faces whose bit is set are listed, and a listed point that lies on a Dirichlet
+// face as well is skipped.  No scratch; the residual's partial sums go behind the interior launch's in the caller's work array.
+#include "mgx_ops3d.hpp"
+
+namespace mgx {
+
+typedef unsigned long long u64;
+
+// the list of face points of a grid: the faces in the order z-low, z-high, y-low, y-high, x-low, x-high, end[k] = the number of
+// listed points of the faces 0 .. k (a face whose bit is clear lists none)
+// -- in 32 bits, so that a thread finds its point with 32-bit divisions: a grid whose list is longer is MGX_ERR_SIZE
+struct Rim {
+    int sx, sy, sz, bc;
+    unsigned end[6];
+};
+
+template <class real>
+static int rim_list(const int n[3], int bc, const char* what, Rim& r) {
+    r.sx = n[0], r.sy = n[1], r.sz = n[2], r.bc = bc;
+    const u64 P = (u64)Geo<XSplit, real>(n[0], n[1]).P;
+    const u64 cnt[6] = {P * (u64)n[1], P * (u64)n[1], P * (u64)(n[2] - 2), P * (u64)(n[2] - 2), (u64)(n[1] - 2) * (u64)(n[2] - 2),
+                        (u64)(n[1] - 2) * (u64)(n[2] - 2)};
+    const int bit[6] = {4, 5, 2, 3, 0, 1};
+    u64 acc = 0;
+    for (int k = 0; k < 6; k++) {
+        if ((bc >> bit[k]) & 1) acc += cnt[k];
+        MGX_REQUIRE(acc < 0xffffffffull, MGX_ERR_SIZE, "%s: %llu face points are too many", what, acc);
+        r.end[k] = (unsigned)acc;
+    }
+    return MGX_OK;
+}
+
+constexpr int RIM_THREADS = 256;
+constexpr int RIM_MAX_BLOCKS = 4096;
+static unsigned rim_blocks(const Rim& r) {
+    const u64 b = ((u64)r.end[5] + RIM_THREADS - 1) / RIM_THREADS;
+    return (unsigned)(b < 1 ? 1 : b > RIM_MAX_BLOCKS ? RIM_MAX_BLOCKS : b);
+}
+
+// i reflected into [0, n) for -1 <= i <= n
+__device__ __forceinline__ int rim_reflect(int i, int n) { return i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i; }
+
+// point t of the list: its coordinates; false for a pad position and for a point that is no unknown
+template <class real>
+__device__ __forceinline__ bool rim_point(const Rim& R, const Geo<XSplit, real>& g, unsigned t, int& x, int& y, int& z) {
+    int k = 0;
+    while (k < 5 && t >= R.end[k]) k++;
+    const unsigned u = t - (k ? R.end[k - 1] : 0);
+    if (k < 4) {  // whole rows: storage position j of row u / P
+        const unsigned row = u / (unsigned)g.P;
+        x = xs_x((int)(u - row * (unsigned)g.P), g.H);
+        if (x >= R.sx) return false;
+        if (k < 2) y = (int)row, z = k == 0 ? 0 : R.sz - 1;
+        else y = k == 2 ? 0 : R.sy - 1, z = 1 + (int)row;
+    } else {
+        const unsigned q = u / (unsigned)(R.sy - 2);
+        x = k == 4 ? 0 : R.sx - 1, y = 1 + (int)(u - q * (unsigned)(R.sy - 2)), z = 1 + (int)q;
+    }
+    const int on = (x == 0) | (x == R.sx - 1) << 1 | (y == 0) << 2 | (y == R.sy - 1) << 3 | (z == 0) << 4 | (z == R.sz - 1) << 5;
+    return (on & ~R.bc) == 0;
+}
+
+// the reflected star of p around (x, y, z) (C: the centre too)
+template <class real, bool C>
+__device__ __forceinline__ Star7<real> rim_star(const real* __restrict__ p, const Geo<XSplit, real>& g, const Rim& R, int x, int y, int z) {
+    const int xm = rim_reflect(x - 1, R.sx), xp = rim_reflect(x + 1, R.sx);
+    const int ym = rim_reflect(y - 1, R.sy), yp = rim_reflect(y + 1, R.sy);
+    const int zm = rim_reflect(z - 1, R.sz), zp = rim_reflect(z + 1, R.sz);
+    const size_t row = g.row(y, z);
+    const int j = g.pos(x);
+    Star7<real> s;
+    s.O = p[row + g.pos(xm)];
+    s.E = p[row + g.pos(xp)];
+    s.N = p[g.row(ym, z) + j];
+    s.S = p[g.row(yp, z) + j];
+    s.D = p[g.row(y, zm) + j];
+    s.U = p[g.row(y, zp) + j];
+    s.C = C ? p[row + j] : (real)0;
+    return s;
+}
+
+#define RIM_FOR_EACH_POINT(R, g, x, y, z)                                                                                  \
+    for (u64 t_ = (u64)blockIdx.x * RIM_THREADS + threadIdx.x; t_ < (R).end[5]; t_ += (u64)gridDim.x * RIM_THREADS)        \
+        if (int x, y, z; rim_point<real>(R, g, (unsigned)t_, x, y, z))
+
+// one colour pass on the face unknowns
+template <class real, class Op>
+__global__ void __launch_bounds__(RIM_THREADS) rim_relax3d_xs_kernel(real* __restrict__ v, const real* __restrict__ f, const real* __restrict__ a,
+                                                                     Rim R, Op op, int colour) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        if (((x + y + z) & 1) != colour) continue;
+        const size_t i = g.row(y, z) + g.pos(x);
+        const Star7<real> vs = rim_star<real, false>(v, g, R, x, y, z);
+        Star7<real> as = {};
+        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
+        v[i] = op.relax(vs, f[i], as);
+    }
+}
+
+// r on the face unknowns (out == NULL: not stored) and the block's partial of its squares (partial == NULL: none): per thread in
+// list order, wavefront-wide shuffles, the four waves in a fixed order -- the same bits on every run
+template <class real, class Op, int MODE>
+__global__ void __launch_bounds__(RIM_THREADS) rim_residual3d_xs_kernel(const real* __restrict__ v, const real* __restrict__ f,
+                                                                        const real* __restrict__ a, real* __restrict__ out, Rim R, Op op,
+                                                                        double* __restrict__ partial) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    double acc = 0.0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const size_t i = g.row(y, z) + g.pos(x);
+        const Star7<real> vs = rim_star<real, true>(v, g, R, x, y, z);
+        Star7<real> as = {};
+        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
+        const real t = op.template residual<MODE>(vs, f[i], as);
+        if (out) out[i] = t;
+        acc += (double)t * (double)t;
+    }
+    if (partial) {  // (uniform over the launch)
+        __shared__ double part[RIM_THREADS / 64];
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) partial[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+    }
+}
+
+// coarse = restrict3d_point on the 27 reflected fine values, at the coarse face unknowns (R lists the COARSE grid)
+template <class real>
+__global__ void __launch_bounds__(RIM_THREADS) rim_restrict3d_xs_kernel(const real* __restrict__ fine, int fsx, int fsy, int fsz,
+                                                                        real* __restrict__ coarse, Rim R) {
+    const Geo<XSplit, real> gc(R.sx, R.sy), gf(fsx, fsy);
+    RIM_FOR_EACH_POINT(R, gc, x, y, z) {
+        auto get = [&](int dx, int dy, int dz) __attribute__((always_inline)) {
+            return fine[gf.row(rim_reflect(2 * y + dy, fsy), rim_reflect(2 * z + dz, fsz)) + gf.pos(rim_reflect(2 * x + dx, fsx))];
+        };
+        coarse[gc.row(y, z) + gc.pos(x)] = restrict3d_point<real>(get);
+    }
+}
+
+// fine (+)= interpolate3d_point at the fine face unknowns (R lists the FINE grid).  A face coordinate is even, so on the axis of
+// its face a point reads the coarse point of the same face only.
+template <class real, bool ADD>
+__global__ void __launch_bounds__(RIM_THREADS) rim_interpolate3d_xs_kernel(real* __restrict__ fine, const real* __restrict__ coarse, int csx,
+                                                                           int csy, Rim R) {
+    const Geo<XSplit, real> gf(R.sx, R.sy), gc(csx, csy);
+    RIM_FOR_EACH_POINT(R, gf, x, y, z) {
+        auto get = [&](int dx, int dy, int dz) __attribute__((always_inline)) {
+            return coarse[gc.row((y >> 1) + dy, (z >> 1) + dz) + gc.pos((x >> 1) + dx)];
+        };
+        const real e = interpolate3d_point<real>(x & 1, y & 1, z & 1, get);
+        const size_t i = gf.row(y, z) + gf.pos(x);
+        fine[i] = ADD ? fine[i] + e : e;
+    }
+}
+
+// f = (-(s*u)) - qscale*q on the face unknowns (q == NULL: f = -(s*u))
+template <class real>
+__global__ void __launch_bounds__(RIM_THREADS) rim_shift_rhs3d_xs_kernel(const real* __restrict__ u, const real* __restrict__ q, real qscale,
+                                                                         real s, real* __restrict__ f, Rim R) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const size_t i = g.row(y, z) + g.pos(x);
+        real t = -(s * u[i]);
+        if (q) t = t - qscale * q[i];
+        f[i] = t;
+    }
+}
+
+// the face unknowns := value
+template <class real>
+__global__ void __launch_bounds__(RIM_THREADS) rim_set3d_xs_kernel(real* __restrict__ v, real value, Rim R) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    RIM_FOR_EACH_POINT(R, g, x, y, z) v[g.row(y, z) + g.pos(x)] = value;
+}
+
+// =========================================================================== host side
+#define RIM_BC_CHECK(bc, what) MGX_REQUIRE((bc) >= 0 && (bc) <= 63, MGX_ERR_INVALID, "%s: bc = %d is outside 0 .. 63", what, bc)
+
+// ncycles red+black sweeps, each colour pass the interior launch and the rim launch of that colour
+template <class Op, class real>
+static int relax_op3d_bc(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int bc,
+                         const char* what) {
+    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && n && h, MGX_ERR_INVALID, "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    if (!bc) return relax_op3d<Op, real>(ctx, v, f, a, n, h, s, ncycles, 0, 0, what);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd, false));
+    MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "%s: ncycles = %d < 0", what, ncycles);
+    MGX_USE(ctx);
+    const Op op(ctx, h, s);
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    for (int p = 0; p < 2 * ncycles; p++) {
+        relax_op3d_pass<Op, real>(ctx, v, f, a, n, op, p & 1);
+        MGX_LAUNCH((rim_relax3d_xs_kernel<real, Op>), dim3(rim_blocks(R)), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, R, op, p & 1);
+    }
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
+// r = the residual on all unknowns, 0 on the Dirichlet points (r == NULL: not stored); *dev_sumsq = the sum of its squares over all
+// unknowns (NULL: none).  The rim launch has at most as many blocks as the interior launch has partials: the work array of
+// mgx3dxs_krylov_work_elems doubles, twice that count, holds both.
+template <class Op, class real>
+static int residual_op3d_bc(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3], const real h[3], real s,
+                            double* dev_work, double* dev_sumsq, int bc, const char* what) {
+    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && n && h && (r || dev_sumsq) && (!dev_sumsq || dev_work), MGX_ERR_INVALID,
+                "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    if (!bc) return residual_op3d<Op, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, what);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd));
+    MGX_USE(ctx);
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    if (r)  // every boundary point first: the Dirichlet points keep the 0
+        MGX_LAUNCH((rim_zero3d_xs_kernel<real>), dim3(ceil_div(n[0], 64), ceil_div(n[1], 4), n[2]), dim3(64, 4, 1), 0, ctx->compute, r, n[0], n[1],
+                   n[2]);
+    const Op op(ctx, h, s);
+    MGX_TRY_RET((residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, op, dev_work, dev_sumsq, false)));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    unsigned nb = rim_blocks(R);
+    if (dev_sumsq && nb > interior) nb = (unsigned)interior;
+    Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
+        MGX_LAUNCH((rim_residual3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, r, R, op,
+                   dev_sumsq ? dev_work + interior : (double*)nullptr);
+    });
+    MGX_LAUNCH_CHECK();
+    return dev_sumsq ? krylov_final(ctx, dev_work, interior + nb, 1, dev_sumsq) : MGX_OK;
+}
+
+// the coarse sizes of a transfer with a mask: a level of its own, odd and >= 3 (the existing entries ask that of the fine sizes only)
+static int rim_coarse_check(const int cn[3], const char* what) {
+    for (int d = 0; d < 3; d++)
+        MGX_REQUIRE(valid_size(cn[d]), MGX_ERR_SIZE, "%s: coarse size[%d] = %d is not odd and >= 3", what, d, cn[d]);
+    return MGX_OK;
+}
+
+template <class real>
+static int rim_set3d(mgx_ctx* ctx, real* v, const int n[3], real value, int bc) {
+    MGX_REQUIRE(ctx && v && n, MGX_ERR_INVALID, "set_rim_bc: NULL argument");
+    RIM_BC_CHECK(bc, "set_rim_bc");
+    MGX_TRY_RET(rows_check(n, "set_rim_bc", nullptr, false));
+    MGX_REQUIRE((double)n[0] * n[1] * n[2] < 2147483647.0 * 4, MGX_ERR_SIZE, "set_rim_bc: grid too large");
+    if (!bc) return MGX_OK;
+    MGX_USE(ctx);
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, "set_rim_bc", R));
+    MGX_LAUNCH((rim_set3d_xs_kernel<real>), dim3(rim_blocks(R)), dim3(RIM_THREADS), 0, ctx->compute, v, value, R);
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
+}  // namespace mgx
+
+// each transfer entry runs the existing entry first: it checks the sizes (the coarse ones are (n - 1) / 2 + 1) before the rim launch,
+// which makes the context's device current itself
+#define MGX_RIM3D_API(SFX, real)                                                                                                             \
+    extern "C" int mgx3dxs_relax_shift_bc_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], real s, int ncycles,   \
+                                                int bc) {                                                                                    \
+        return mgx::relax_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, n, h, s, ncycles, bc, "relax_shift_bc");                     \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_relax_coef_bc_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s,  \
+                                               int ncycles, int bc) {                                                                        \
+        return mgx::relax_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, "relax_coef_bc");                             \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_residual_shift_bc_##SFX(mgx_ctx* ctx, const real* v, const real* f, real* r, const int n[3], const real h[3],      \
+                                                   real s, double* dev_work, double* dev_sumsq, int bc) {                                    \
+        return mgx::residual_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, r, n, h, s, dev_work, dev_sumsq, bc, "residual_shift_bc"); \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_residual_coef_bc_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3],         \
+                                                  const real h[3], real s, double* dev_work, double* dev_sumsq, int bc) {                    \
+        return mgx::residual_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, "residual_coef_bc");        \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_restrict_bc_##SFX(mgx_ctx* ctx, const real* fine, const int fn[3], real* coarse, const int cn[3], int bc) {        \
+        MGX_REQUIRE(ctx && fine && fn && coarse && cn, MGX_ERR_INVALID, "restrict_bc: NULL argument");                                       \
+        RIM_BC_CHECK(bc, "restrict_bc");                                                                                                     \
+        if (bc) MGX_TRY_RET(mgx::rim_coarse_check(cn, "restrict_bc"));                                                                       \
+        MGX_TRY_RET(mgx3dxs_restrict_##SFX(ctx, fine, fn, coarse, cn));                                                                      \
+        if (!bc) return MGX_OK;                                                                                                              \
+        mgx::Rim R;                                                                                                                          \
+        MGX_TRY_RET(mgx::rim_list<real>(cn, bc, "restrict_bc", R));                                                                          \
+        MGX_USE(ctx);                                                                                                                        \
+        MGX_LAUNCH((mgx::rim_restrict3d_xs_kernel<real>), dim3(mgx::rim_blocks(R)), dim3(mgx::RIM_THREADS), 0, ctx->compute, fine, fn[0],    \
+                   fn[1], fn[2], coarse, R);                                                                                                 \
+        MGX_LAUNCH_CHECK();                                                                                                                  \
+        return MGX_OK;                                                                                                                       \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_interpolate_bc_##SFX(mgx_ctx* ctx, real* fine, const int fn[3], const real* coarse, const int cn[3], int bc) {     \
+        MGX_REQUIRE(ctx && fine && fn && coarse && cn, MGX_ERR_INVALID, "interpolate_bc: NULL argument");                                    \
+        RIM_BC_CHECK(bc, "interpolate_bc");                                                                                                  \
+        if (bc) MGX_TRY_RET(mgx::rim_coarse_check(cn, "interpolate_bc"));                                                                    \
+        MGX_TRY_RET(mgx3dxs_interpolate_##SFX(ctx, fine, fn, coarse, cn));                                                                   \
+        if (!bc) return MGX_OK;                                                                                                              \
+        mgx::Rim R;                                                                                                                          \
+        MGX_TRY_RET(mgx::rim_list<real>(fn, bc, "interpolate_bc", R));                                                                       \
+        MGX_USE(ctx);                                                                                                                        \
+        MGX_LAUNCH((mgx::rim_interpolate3d_xs_kernel<real, false>), dim3(mgx::rim_blocks(R)), dim3(mgx::RIM_THREADS), 0, ctx->compute, fine, \
+                   coarse, cn[0], cn[1], R);                                                                                                 \
+        MGX_LAUNCH_CHECK();                                                                                                                  \
+        return MGX_OK;                                                                                                                       \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_interpolate_correct_bc_##SFX(mgx_ctx* ctx, real* v, const int n[3], const real* coarse_v, const int cn[3],         \
+                                                        int bc) {                                                                            \
+        MGX_REQUIRE(ctx && v && n && coarse_v && cn, MGX_ERR_INVALID, "interpolate_correct_bc: NULL argument");                              \
+        RIM_BC_CHECK(bc, "interpolate_correct_bc");                                                                                          \
+        if (bc) MGX_TRY_RET(mgx::rim_coarse_check(cn, "interpolate_correct_bc"));                                                            \
+        MGX_TRY_RET(mgx3dxs_interpolate_correct_##SFX(ctx, v, n, coarse_v, cn));                                                             \
+        if (!bc) return MGX_OK;                                                                                                              \
+        mgx::Rim R;                                                                                                                          \
+        MGX_TRY_RET(mgx::rim_list<real>(n, bc, "interpolate_correct_bc", R));                                                                \
+        MGX_USE(ctx);                                                                                                                        \
+        MGX_LAUNCH((mgx::rim_interpolate3d_xs_kernel<real, true>), dim3(mgx::rim_blocks(R)), dim3(mgx::RIM_THREADS), 0, ctx->compute, v,     \
+                   coarse_v, cn[0], cn[1], R);                                                                                               \
+        MGX_LAUNCH_CHECK();                                                                                                                  \
+        return MGX_OK;                                                                                                                       \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_shift_rhs_bc_##SFX(mgx_ctx* ctx, const real* u, const real* q, real qscale, real s, real* f, const int n[3],       \
+                                              int bc) {                                                                                      \
+        MGX_REQUIRE(ctx && u && f && n, MGX_ERR_INVALID, "shift_rhs_bc: NULL argument");                                                     \
+        RIM_BC_CHECK(bc, "shift_rhs_bc");                                                                                                    \
+        MGX_TRY_RET(mgx3dxs_shift_rhs_##SFX(ctx, u, q, qscale, s, f, n));                                                                    \
+        if (!bc) return MGX_OK;                                                                                                              \
+        mgx::Rim R;                                                                                                                          \
+        MGX_TRY_RET(mgx::rim_list<real>(n, bc, "shift_rhs_bc", R));                                                                          \
+        MGX_USE(ctx);                                                                                                                        \
+        MGX_LAUNCH((mgx::rim_shift_rhs3d_xs_kernel<real>), dim3(mgx::rim_blocks(R)), dim3(mgx::RIM_THREADS), 0, ctx->compute, u, q, qscale,  \
+                   s, f, R);                                                                                                                 \
+        MGX_LAUNCH_CHECK();                                                                                                                  \
+        return MGX_OK;                                                                                                                       \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_set_rim_bc_##SFX(mgx_ctx* ctx, real* v, const int n[3], real value, int bc) {                                     \
+        return mgx::rim_set3d<real>(ctx, v, n, value, bc);                                                                                   \
+    }
+
+MGX_RIM3D_API(f32, float)
+MGX_RIM3D_API(f64, double)

@@ -14,60 +14,16 @@
 // With s = 0 every one of them gives the bits of the unshifted operator (x + 0 = x for the positive den, r + 0*c = r up to
 // the sign of a zero residual).
 //
-// This file holds the operator's policy, ShiftOp, and what only this operator has; the kernels and their host drivers are the
+// The operator's policy, ShiftOp, is in mgx_ops3d.hpp; this file holds what only this operator has; the kernels and their host drivers are the
 // shared ones of mgx_stencil3d.hpp, instantiated with the policy:
 //   relax_op3d_xs_kernel<real, ShiftOp, TYW, R>       one colour pass ("relax_shift3d_xs_kernel" to last_relax_kernel())
 //   relax_op_zero3d_xs_kernel<real, ShiftOp>          the first red pass on a level that counts as zero: f in, red out, v not read
 //   residual_op3d_xs_kernel<real, ShiftOp, MODE, LAP> r and / or the partials of <r, r>; with LAP: q = A p and the partials of <p, q>
 //   shift_rhs3d_xs_kernel                             f = (-(s*u)) - qscale*q, the right-hand side of a backward Euler step
 //   residual_restrict_axes3d_xs_kernel<..., SHIFT = true> (mgx_semi3d.hpp)   Restrict(residual) for the masks 1 .. 7
-#include "mgx_stencil3d.hpp"
+#include "mgx_ops3d.hpp"
 
 namespace mgx {
-
-template <class real>
-__device__ __forceinline__ real relax_shift3d_point(real O, real E, real N, real S, real D, real U, real f, real hx2, real hy2, real hz2,
-                                                    real den, double rd) {
-    const real num = O * (hy2 * hz2) + E * (hy2 * hz2) + N * (hx2 * hz2) + S * (hx2 * hz2) + D * (hx2 * hy2) + U * (hx2 * hy2) -
-                     f * hx2 * hy2 * hz2;
-    if constexpr (sizeof(real) == 4) {
-        real q = (real)((double)num * rd);
-        if (__builtin_expect(!(__builtin_fabsf(q) >= 1.17549435e-38f), 0)) q = num / den;
-        return q;
-    } else {
-        return num / den;
-    }
-}
-
-// den and, for fp32's route, rd = 1 / den in double are the same for every point of a level
-template <class real>
-struct ShiftOp {
-    static constexpr bool HAS_A = false, HAS_S = true;
-    static constexpr const char *relax_kernel = "relax_shift3d_xs_kernel", *zero_kernel = "relax_shift_zero3d_xs_kernel";
-    real hx2, hy2, hz2, den;  // the smoother's
-    double rd;
-    real qx, qy, qz, s;  // the residual's: residual_scale's, MODE 1, or 3 with exact reciprocals
-    int mode;
-    ShiftOp(const mgx_ctx* ctx, const real h[3], real s_) : s(s_) {
-        const ResidualScale<real> sc = residual_scale<real>(ctx, h, MGX_RESIDUAL_CORRECT);
-        hx2 = sc.hx2, hy2 = sc.hy2, hz2 = sc.hz2;
-        den = 2 * (hy2 * hz2 + hx2 * hz2 + hx2 * hy2) + s * hx2 * hy2 * hz2;
-        rd = sizeof(real) == 4 ? 1.0 / (double)den : 0.0;
-        qx = sc.qx, qy = sc.qy, qz = sc.qz, mode = sc.mode;
-    }
-    static int rows(const mgx_ctx*) { return 4; }  // ("relax3d.rows" is not read)
-    template <class F>
-    static void with_mode(int mode, F&& f) {
-        with_value<1, 3>(mode, f);
-    }
-    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>&) const {
-        return relax_shift3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, hx2, hy2, hz2, den, rd);
-    }
-    template <int MODE>
-    __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>&) const {
-        return residual3d_point<real, MODE>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, qx, qy, qz) + s * v.C;
-    }
-};
 
 // f = (-(s*u)) - qscale*q on the interior (q == NULL: f = -(s*u))
 template <class real, bool Q>

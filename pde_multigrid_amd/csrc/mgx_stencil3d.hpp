@@ -2,8 +2,8 @@
 // and the residual / operator kernel built on it, the colour pass of the smoother and its from-zero first pass, and the host
 // drivers that launch them.  Each is written once and takes the operator as a policy `Op`, passed to the kernels by value:
 //   PlainOp  (mgx_krylov3d.hip)  the CORRECT-mode Laplacian                         q = A p only
-//   ShiftOp  (mgx_shift3d.hip)   (Laplacian - s) u = f                             DESIGN.md section 13
-//   CoefOp   (mgx_coef3d.hip)    div(a grad u) - s u = f, a at the grid nodes      DESIGN.md section 14
+//   ShiftOp  (mgx_ops3d.hpp)     (Laplacian - s) u = f                             DESIGN.md section 13
+//   CoefOp   (mgx_ops3d.hpp)     div(a grad u) - s u = f, a at the grid nodes      DESIGN.md section 14
 // A policy holds
 //   Op(ctx, h, s)                          the operator's scalars for a level with spacings h, formed by the host once per call
 //   HAS_A, HAS_S                           does it read a coefficient array / take a shift (checked to be finite and >= 0)
@@ -302,17 +302,18 @@ static int relax_op3d(mgx_ctx* ctx, real* v, const real* f, const real* a, const
     return MGX_OK;
 }
 
-// the launch of residual_op3d_xs_kernel and the final sum (dev_sum == NULL: none)
+// the launch of residual_op3d_xs_kernel and the final sum (dev_sum == NULL: none; finalize = false: the partials are left in
+// dev_work[0, grid.x * grid.y) for a caller that adds partials of its own before the final sum)
 template <class Op, bool LAP, class real>
 static int residual_op3d_launch(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* out, const int n[3], const Op& op,
-                                double* dev_work, double* dev_sum) {
+                                double* dev_work, double* dev_sum, bool finalize = true) {
     const dim3 g = krylov_grid(n);
     Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
         MGX_LAUNCH((residual_op3d_xs_kernel<real, Op, decltype(m)::value, LAP>), g, krylov_block(), 0, ctx->compute, v, f, a, out, n[0], n[1], op,
                    dev_sum ? dev_work : (double*)nullptr);
     });
     MGX_LAUNCH_CHECK();
-    return dev_sum ? krylov_final(ctx, dev_work, (size_t)g.x * g.y, 1, dev_sum) : MGX_OK;
+    return dev_sum && finalize ? krylov_final(ctx, dev_work, (size_t)g.x * g.y, 1, dev_sum) : MGX_OK;
 }
 
 // r = the residual (r == NULL: not stored; its boundary is 0), *dev_sumsq = <r, r> (NULL: not summed)

@@ -562,6 +562,74 @@ class _Ops3D(_Ops):
         (_, _, qo), sums = self._krylov(ctx, n, [pp, aa, qq], [], lambda w, s0, x, c, b: fn(ctx._h, x, c, b, _ip(n), h, ct(s), w, s0), dtype, 1)
         return xs_unpack(qo, n[0]), float(sums[0])
 
+    # ---- homogeneous Neumann faces (x-split only, mgx3dxs_*_bc): the wrappers above with the face mask bc as their last argument
+    def relax_shift_bc(self, ctx, v, f, n, rng, s, ncycles, bc, dtype=None):
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_shift_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [v, f], lambda a, b: fn(ctx._h, a, b, _ip(n), h, ct(s), C.c_int(ncycles), C.c_int(bc)), 0, _shape(n), dtype)
+
+    def relax_coef_bc(self, ctx, v, f, a, n, rng, s, ncycles, bc, dtype=None):
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_coef_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [v, f, a], lambda x, b, c: fn(ctx._h, x, b, c, _ip(n), h, ct(s), C.c_int(ncycles), C.c_int(bc)), 0, _shape(n),
+                         dtype)
+
+    def residual_shift_bc(self, ctx, v, f, n, rng, s, bc, store=True, want_sum=True, dtype=None):
+        """(r, sum of squares over all unknowns): r None with store=False, the sum None with want_sum=False"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("residual_shift_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        arrays = [xs_pack(np.ascontiguousarray(a, dtype)) for a in (v, f)] + [xs_pack(np.zeros(_shape(n), dtype)) if store else None]
+        (_, _, ro), sums = self._krylov(ctx, n, arrays, [],
+                                        lambda w, s0, a, b, c: fn(ctx._h, a, b, c, _ip(n), h, ct(s), w if want_sum else None,
+                                                                  s0 if want_sum else None, C.c_int(bc)), dtype, 1)
+        return (xs_unpack(ro, n[0]) if store else None), (float(sums[0]) if want_sum else None)
+
+    def residual_coef_bc(self, ctx, v, f, a, n, rng, s, bc, store=True, want_sum=True, dtype=None):
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("residual_coef_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        arrays = [xs_pack(np.ascontiguousarray(x, dtype)) for x in (v, f, a)] + [xs_pack(np.zeros(_shape(n), dtype)) if store else None]
+        (_, _, _, ro), sums = self._krylov(ctx, n, arrays, [],
+                                           lambda w, s0, x, b, c, d: fn(ctx._h, x, b, c, d, _ip(n), h, ct(s), w if want_sum else None,
+                                                                        s0 if want_sum else None, C.c_int(bc)), dtype, 1)
+        return (xs_unpack(ro, n[0]) if store else None), (float(sums[0]) if want_sum else None)
+
+    def restrict_bc(self, ctx, fine, n, bc, coarse=None, dtype=None):
+        """coarse: the array the call writes into (every point is written; default zeros)"""
+        dtype = dtype or fine.dtype
+        fn, _ = self._fn("restrict_bc", dtype)
+        cn = coarse_size(n)
+        coarse = np.zeros(_shape(cn), dtype) if coarse is None else coarse
+        return self._run(ctx, [fine, coarse], lambda f, c: fn(ctx._h, f, _ip(n), c, _ip(cn), C.c_int(bc)), 1, _shape(cn), dtype)
+
+    def interpolate_bc(self, ctx, fine, n, coarse, bc, dtype=None):
+        dtype = dtype or fine.dtype
+        fn, _ = self._fn("interpolate_bc", dtype)
+        cn = coarse_size(n)
+        return self._run(ctx, [fine, coarse], lambda f, c: fn(ctx._h, f, _ip(n), c, _ip(cn), C.c_int(bc)), 0, _shape(n), dtype)
+
+    def interpolate_correct_bc(self, ctx, v, n, coarse, bc, dtype=None):
+        dtype = dtype or v.dtype
+        fn, _ = self._fn("interpolate_correct_bc", dtype)
+        cn = coarse_size(n)
+        return self._run(ctx, [v, coarse], lambda a, c: fn(ctx._h, a, _ip(n), c, _ip(cn), C.c_int(bc)), 0, _shape(n), dtype)
+
+    def shift_rhs_bc(self, ctx, u, q, qscale, s, n, bc, f=None, dtype=None):
+        """f = (-(s*u)) - qscale*q on all unknowns (q None: -(s*u)); f: the array written into (default zeros)"""
+        dtype = dtype or u.dtype
+        fn, ct = self._fn("shift_rhs_bc", dtype)
+        f = np.zeros(_shape(n), dtype) if f is None else f
+        return self._run(ctx, [u, q, f], lambda a, b, c: fn(ctx._h, a, b, ct(qscale), ct(s), c, _ip(n), C.c_int(bc)), 2, _shape(n), dtype)
+
+    def set_rim_bc(self, ctx, v, n, value, bc, dtype=None):
+        """v := value at the unknowns on the faces of bc, nothing else"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("set_rim_bc", dtype)
+        return self._run(ctx, [v], lambda a: fn(ctx._h, a, _ip(n), ct(value), C.c_int(bc)), 0, _shape(n), dtype)
+
     # ---- vector kernels of the preconditioned CG solve (x-split only; every array in the reference layout on the host)
     # every work array is uploaded with WORK_GUARD sentinel doubles behind the elements the library asks for, and the
     # sentinels are looked at after the call: a kernel that writes into the next WORK_GUARD doubles behind its work array
@@ -830,7 +898,7 @@ def _grid3_struct(ct):
                     ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 32), ("f_rim_zero", C.c_ubyte * 32),
                     ("v_rim_zero", C.c_ubyte * 32), ("e_rim_valid", C.c_ubyte * 32), ("pcg_x", C.c_void_p),
                     ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
-                    ("pcg_work", C.c_void_p), ("pcg_graph_exec", C.c_void_p), ("pcg_graph_key", C.c_longlong),
+                    ("pcg_work", C.c_void_p), ("pcg_graph_exec", C.c_void_p), ("bc", C.c_int), ("bc_reserved", C.c_int),
                     ("graph_rec", GraphRec * 32), ("graph_post", GraphFlags * 32), ("pcg_graph_rec", GraphRec),
                     ("pcg_graph_post", GraphFlags), ("pcg_mixed", C.c_void_p), ("coarsen", C.c_ubyte * 32), ("shift", ct)]
 
@@ -921,11 +989,12 @@ class MultiGrid3D(_MGBase):
     _prefix = "mgMultiGrid3D"
 
     def __init__(self, ctx, finestGridSizeXYZ, rng, dtype=np.float64, nlevels=0, residual_mode=REF_COMPAT, fuse=True,
-                 layout="xsplit", coarsening="full", shift=0.0, coefficient=None):
+                 layout="xsplit", coarsening="full", shift=0.0, coefficient=None, neumann=None):
         """coarsening="semi": every level halves only the axes with the smallest spacing (semi_plan, mg_multigrid.h) -- the
         hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count.
         shift = s >= 0: the hierarchy of (Laplacian - s) u = f (the `shift` property).
-        coefficient = a > 0 at every point of the finest grid: the hierarchy of div(a grad u) - s u = f (set_coefficient)."""
+        coefficient = a > 0 at every point of the finest grid: the hierarchy of div(a grad u) - s u = f (set_coefficient).
+        neumann = six truthy values (x-low, x-high, y-low, y-high, z-low, z-high): the faces with du/dn = 0 (set_neumann)."""
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self._sfx, self._ct = _ct(dtype)
@@ -958,6 +1027,29 @@ class MultiGrid3D(_MGBase):
             except Exception:
                 self.close()
                 raise
+        if neumann is not None:
+            try:
+                self.set_neumann(neumann)
+            except Exception:
+                self.close()
+                raise
+
+    def set_neumann(self, faces):
+        """faces: six truthy values, one per face in the order x-low, x-high, y-low, y-high, z-low, z-high (None: all False).  A
+        true one makes that face a wall with du/dn = 0 on every level: its points, but for those on a Dirichlet face too, become
+        unknowns, and v there is part of the solution instead of data.  Needs layout="xsplit", the red-black smoother,
+        residual_mode=CORRECT and coarsening="full"; PCG and BackwardEuler then need krylov=False, PCG(precond="f32") is not
+        available, and all six faces need a shift > 0.  A prescribed flux g (du/dn = g, outward) goes into the right-hand side:
+        f -= 2 g a / h at the face.  All False: the hierarchy is what it was without walls."""
+        faces = [0] * 6 if faces is None else [int(bool(x)) for x in faces]
+        if len(faces) != 6:
+            raise ValueError("neumann takes six values (x-low, x-high, y-low, y-high, z-low, z-high), not %d" % len(faces))
+        self._call("set_boundary", _ip(faces))
+
+    @property
+    def neumann(self):
+        """the six faces' flags as set_neumann takes them"""
+        return tuple(bool((self._mg.contents.bc >> k) & 1) for k in range(6))
 
     def set_coefficient(self, a):
         """a: the coefficient of div(a grad u) - shift u = f at ALL points of level 0 (reference layout, finite and > 0), restricted
@@ -1424,12 +1516,13 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
 
 
 def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full",
-                shift=0.0, coefficient=None):
+                shift=0.0, coefficient=None, neumann=None):
     """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
     precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG).
     coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call.
     shift = s > 0: the solve of (Laplacian - s) u = rhs (MultiGrid3D(shift=s)), on a hierarchy built here likewise.
-    coefficient = a > 0 at every point: the solve of div(a grad u) - shift u = rhs (MultiGrid3D(coefficient=a)), likewise."""
+    coefficient = a > 0 at every point: the solve of div(a grad u) - shift u = rhs (MultiGrid3D(coefficient=a)), likewise.
+    neumann = six truthy values: the faces with du/dn = 0 (MultiGrid3D(neumann=...)), likewise; needs krylov=False."""
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
     if precond not in ("f64", "f32"):
@@ -1438,9 +1531,9 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
         raise ValueError("precond='f32' needs an fp64 grid")
     if coarsening not in ("full", "semi"):
         raise ValueError("coarsening must be 'full' or 'semi', not %r" % (coarsening,))
-    if coarsening == "semi" or shift != 0 or coefficient is not None:
+    if coarsening == "semi" or shift != 0 or coefficient is not None or (neumann is not None and any(neumann)):
         mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening=coarsening,
-                         shift=shift, coefficient=coefficient)
+                         shift=shift, coefficient=coefficient, neumann=neumann)
         try:
             mg.upload_v(0, grid)
             if rhs is not None:
