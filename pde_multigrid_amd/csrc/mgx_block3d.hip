@@ -43,8 +43,7 @@
 // into the next iteration, in front of that iteration's own requests.)
 #include <type_traits>
 
-#include "mgx_internal.hpp"
-#include "mgx_kernels3d.hpp"
+#include "mgx_host3d.hpp"
 
 namespace mgx {
 
@@ -343,6 +342,9 @@ void relax3d_xs_block3_launch(mgx_ctx* ctx, const real* vin, real* vout, const r
 }
 template void relax3d_xs_block3_launch<double>(mgx_ctx*, const double*, double*, const double*, const int[3], double, double, double, int,
                                                bool, const double*, const int*);
+template <>
+void relax3d_xs_block3_launch<float>(mgx_ctx*, const float*, float*, const float*, const int[3], float, float, float, int, bool, const float*,
+                                     const int*) {}  // fp64 only: never taken
 
 }  // namespace mgx
 

@@ -1,5 +1,5 @@
-// mgx_core.hip -- context, memory, events, errors behind include/mgx.h.
-#include "mgx_internal.hpp"
+// mgx_core.hip -- context, its parameter table (mgx_ctx_set_param), memory, events, errors behind include/mgx.h.
+#include "mgx_host3d.hpp"
 
 namespace mgx {
 
@@ -335,6 +335,170 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     MGX_USE(ctx);
     MGX_HIP(hipEventSynchronize(stop->ev));
     MGX_HIP(hipEventElapsedTime(ms, start->ev, stop->ev));
+    return MGX_OK;
+}
+
+const char* mgx_ctx_last_relax_kernel(const mgx_ctx* ctx) { return ctx ? ctx->last_relax_kernel : ""; }
+const char* mgx_ctx_last_rr_kernel(const mgx_ctx* ctx) { return ctx ? ctx->last_rr_kernel : ""; }
+const char* mgx_ctx_last_corr_kernel(const mgx_ctx* ctx) { return ctx ? ctx->last_corr_kernel : ""; }
+const char* mgx_ctx_last_block3_kernel(const mgx_ctx* ctx) { return ctx ? ctx->last_block3_kernel : ""; }
+
+int mgx_ctx_set_param(mgx_ctx* ctx, const char* name, int value) {
+    MGX_REQUIRE(ctx && name, MGX_ERR_INVALID, "set_param: NULL argument");
+    MGX_USE(ctx);
+    ctx->generation++;  // also on a rejected value: a spurious re-capture is harmless
+    if (!strcmp(name, "relax3d.ty")) {
+        MGX_REQUIRE(value == 1 || value == 2 || value == 4 || value == 8, MGX_ERR_INVALID, "relax3d.ty (waves per block) must be 1, 2, 4 or 8");
+        ctx->relax_ty = value;
+    } else if (!strcmp(name, "relax3d.small")) {
+        ctx->relax_small = value ? 1 : 0;  // one-workgroup LDS kernel for levels <= 17^3
+    } else if (!strcmp(name, "relax3d.ablate")) {
+#ifdef MGX_DIAGNOSTICS
+        ctx->relax_ablate = value;  // diagnostic builds only: non-zero gives WRONG results (see relax3d_xs_kernel)
+#else
+        return mgx::fail(MGX_ERR_INVALID, "set_param: 'relax3d.ablate' exists only in diagnostic builds (make diag)");
+#endif
+    } else if (!strcmp(name, "relax3d.wave_planes")) {
+        ctx->relax_wave_planes = value;  // < 0 automatic, 0 off (whole-grid passes), > 0 planes per slab
+    } else if (!strcmp(name, "relax3d.rows")) {
+        MGX_REQUIRE(value == 1 || value == 2 || value == 4 || value == 8, MGX_ERR_INVALID, "relax3d.rows must be 1, 2, 4 or 8");
+        ctx->relax_rows = value;
+    } else if (!strcmp(name, "residual_restrict3d.rows")) {
+        MGX_REQUIRE(value == 0 || value == 2 || value == 4, MGX_ERR_INVALID, "residual_restrict3d.rows (fine rows per wave of the pipelined kernel) must be 0 (by level size), 2 or 4");
+        ctx->rr_rows = value;
+    } else if (!strcmp(name, "residual_restrict3d.rcp")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "residual_restrict3d.rcp must be 0 or 1");
+        ctx->rr_rcp = value;
+    } else if (!strcmp(name, "mixed3d.fused")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "mixed3d.fused must be 0 or 1");
+        ctx->mixed_fused = value;
+    } else if (!strcmp(name, "mixed3d.rows")) {
+        MGX_REQUIRE(value == 2 || value == 4 || value == 8, MGX_ERR_INVALID, "mixed3d.rows must be 2, 4 or 8");
+        ctx->mixed_rows = value;
+    } else if (!strcmp(name, "mixed3d.zchunk")) {
+        MGX_REQUIRE(value >= 0, MGX_ERR_INVALID, "mixed3d.zchunk must be >= 0 (0 = automatic)");
+        ctx->mixed_zchunk = value;
+    } else if (!strcmp(name, "residual_restrict3d.xcd")) {
+        MGX_REQUIRE(value >= 0 && value <= 2, MGX_ERR_INVALID, "residual_restrict3d.xcd must be 0, 1 or 2");
+        ctx->rr_xcd = value;
+    } else if (!strcmp(name, "relax3d.xcd")) {
+        MGX_REQUIRE(value >= 0 && value <= 2, MGX_ERR_INVALID, "relax3d.xcd must be 0, 1 or 2");
+        ctx->relax_xcd = value;
+    } else if (!strcmp(name, "relax3d.lds")) {
+        // -1 = automatic (default), 0 = relax3d_xs_kernel, 1000 + 100*WX + 10*WY + R = relax3d_xs_pipe_kernel<WX, WY, R>,
+        // 3282 = the 2 x 8 x 2 shape with non-temporal loads of f; below 1000 (no software pipeline): diagnostic builds
+        bool ok = value == -1 || value == 0 || value == 3282 || (value >= 1000 && value < 2000 && mgx::relax3d_lds_shape_known(value - 1000));
+#ifdef MGX_DIAGNOSTICS
+        ok = ok || (value > 0 && value < 1000 && mgx::relax3d_lds_shape_known(value)) || (value >= 3000 && mgx::relax3d_lds_shape_known(value - 3000));
+#endif
+        MGX_REQUIRE(ok, MGX_ERR_INVALID, "relax3d.lds = %d is not a kernel shape of this build", value);
+        ctx->relax_lds = value;
+    } else if (!strcmp(name, "residual_restrict3d.cr")) {
+        MGX_REQUIRE(value >= 0 && value <= 2, MGX_ERR_INVALID, "residual_restrict3d.cr must be 0 (by level size), 1 or 2");
+        ctx->rr_cr = value;   // coarse rows per lane of the streaming kernel
+    } else if (!strcmp(name, "residual_restrict3d.tyw")) {
+        MGX_REQUIRE(value == 2 || value == 4 || value == 8, MGX_ERR_INVALID, "residual_restrict3d.tyw (waves per block) must be 2, 4 or 8");
+        ctx->rr_tyw = value;
+    } else if (!strcmp(name, "residual_restrict3d.stream")) {
+        MGX_REQUIRE(value >= 0 && value <= 3, MGX_ERR_INVALID, "residual_restrict3d.stream must be 0 ... 3");
+        ctx->rr_stream = value;  // 0 = LDS rolling-window kernel, 1 = streaming shuffle kernel,
+                                                              // 2 = pipelined with halos through LDS (x-split), 3 = 2 on large levels, else 1 (default)
+    } else if (!strcmp(name, "residual_restrict3d.pzchunk")) {
+        MGX_REQUIRE(value >= 0, MGX_ERR_INVALID, "residual_restrict3d.pzchunk must be >= 0 (0 = automatic)");
+        ctx->rr_pzchunk = value;
+    } else if (!strcmp(name, "relax3d.zero_first")) {
+        ctx->relax_zero_first = value ? 1 : 0;  // relax_from_zero: first red pass without reading v (1) or zero fill + generic passes (0)
+    } else if (!strcmp(name, "relax3d.v2")) {
+        ctx->relax_v2 = value ? 1 : 0;  // fp32, wide levels: two x-pairs per lane (relax3d_xs_pipe_v2_kernel) or one
+    } else if (!strcmp(name, "relax3d.corr_fuse")) {
+        ctx->corr_fuse = value ? 1 : 0;  // interpolate_correct_relax: first red pass reads the correction on the fly (1) or in-place correction first (0)
+    } else if (!strcmp(name, "cycle2d.tile")) {
+        MGX_REQUIRE(value == 0 || value == 16 || value == 32 || value == 64, MGX_ERR_INVALID, "cycle2d.tile must be 0 (automatic), 16, 32 or 64");
+        ctx->cyc2_tile = value;
+    } else if (!strcmp(name, "cycle2d.tail_points")) {
+        MGX_REQUIRE(value >= 0 && value <= 5120, MGX_ERR_INVALID, "cycle2d.tail_points must be in [0, 5120]");
+        ctx->cyc2_tail_points = value;
+    } else if (!strcmp(name, "relax3d.fused")) {
+        ctx->sweep_fused = value ? 1 : 0;  // levels of 513-point rows: one launch per red+black sweep (mgx_sweep3d.hip) or one per colour
+    } else if (!strcmp(name, "relax3d.corr_v2")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.corr_v2 = %d not in {0, 1}", value);
+        ctx->corr_v2 = value;
+    } else if (!strcmp(name, "relax3d.zero_sweep")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.zero_sweep = %d not in {0, 1}", value);
+        ctx->relax_zero_sweep = value;
+    } else if (!strcmp(name, "relax3d.resident")) {
+        MGX_REQUIRE(value >= 0 && value <= 2, MGX_ERR_INVALID, "set_param: relax3d.resident = %d not in {0, 1, 2}", value);
+        ctx->relax_resident = value;
+    } else if (!strcmp(name, "sync.spin_limit")) {
+        MGX_REQUIRE(value >= 1, MGX_ERR_INVALID, "set_param: sync.spin_limit = %d < 1", value);
+        ctx->sync_spin_limit = (unsigned)value;  // polls before a wait between workgroups gives up (mgx_sync.hpp)
+    } else if (!strcmp(name, "test.handoff_fault")) {
+        MGX_REQUIRE(value >= 0 && value < (1 << 20), MGX_ERR_INVALID, "set_param: test.handoff_fault = %d out of range", value);
+        ctx->handoff_fault = (unsigned)value;  // TEST HOOK: != 0 makes workgroup 0 of those kernels wait for tags nobody writes
+    } else if (!strcmp(name, "gpu.exclusive")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: gpu.exclusive = %d not in {0, 1}", value);
+        ctx->gpu_exclusive = value;  // 0: the GPU is shared -> no kernel whose workgroups wait for each other is launched
+    } else if (!strcmp(name, "relax3d.corr_low")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.corr_low = %d not in {0, 1}", value);
+        ctx->corr_low = value;  // the correcting red pass in 8-wave workgroups, two to a CU (fp64)
+    } else if (!strcmp(name, "slab.edges_merged")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: slab.edges_merged = %d not in {0, 1}", value);
+        ctx->slab_edges_merged = value;  // the two edge planes of a z-slab in one launch (mgx3dxs_relax_colour_slab2_*) or in two
+    } else if (!strcmp(name, "relax3d.resident_tile")) {
+        MGX_REQUIRE(value == 0 || value == 8, MGX_ERR_INVALID, "set_param: relax3d.resident_tile = %d not in {0, 8}", value);
+        ctx->resident_tile = value;
+    } else if (!strcmp(name, "relax3d.resident_min")) {
+        MGX_REQUIRE(value >= 1, MGX_ERR_INVALID, "set_param: relax3d.resident_min = %d < 1", value);
+        ctx->relax_resident_min = value;
+    } else if (!strcmp(name, "rr3d.black")) {
+        MGX_REQUIRE(value >= 0 && value <= 2, MGX_ERR_INVALID, "set_param: rr3d.black = %d not in {0, 1, 2}", value);
+        ctx->rr_black = value;
+    } else if (!strcmp(name, "rr3d.black_waves")) {
+        MGX_REQUIRE(value == 0 || value == 8 || value == 12 || value == 16, MGX_ERR_INVALID, "set_param: rr3d.black_waves = %d not in {0, 8, 12, 16}", value);
+        ctx->rr_black_waves = value;
+    } else if (!strcmp(name, "rr3d.black_abl")) {
+#ifdef MGX_DIAGNOSTICS
+        ctx->rr_black_abl = value;  // ablation bits of relax_rr3d_xs_kernel: WRONG results
+#else
+        return mgx::fail(MGX_ERR_INVALID, "set_param: 'rr3d.black_abl' exists only in diagnostic builds (make diag)");
+#endif
+    } else if (!strcmp(name, "relax3d.fused_ilv")) {
+        ctx->sweep_ilv = value ? 1 : 0;  // sweep3d_xs_kernel: memory instructions in groups between the rows of the arithmetic (1) or all first (0)
+    } else if (!strcmp(name, "relax3d.fused_mid")) {
+        MGX_REQUIRE(value >= 0 && value <= 2, MGX_ERR_INVALID, "set_param: relax3d.fused_mid = %d not in {0, 1, 2}", value);
+        ctx->sweep_mid = value;  // 2: rows of 129 points too (slower there than two passes; tests).  cache-resident levels (33 ... 129 points per row): one launch per sweep (sweep3d_xs_mid_kernel)
+    } else if (!strcmp(name, "relax3d.fused_dbg")) {
+#ifdef MGX_DIAGNOSTICS
+        ctx->sweep_dbg = value;  // 1 = cycle stamps, + 2 * ablation bits: WRONG results
+#else
+        return mgx::fail(MGX_ERR_INVALID, "set_param: 'relax3d.fused_dbg' exists only in diagnostic builds (make diag)");
+#endif
+    } else if (!strcmp(name, "relax3d.fused_lead")) {
+        MGX_REQUIRE(value == 0 || (value >= 5 && value <= 7), MGX_ERR_INVALID, "relax3d.fused_lead (planes the red stage runs ahead) must be 0 (default), 5, 6 or 7");
+        ctx->sweep_lead = value;
+    } else if (!strcmp(name, "relax3d.unroll")) {
+        // the pipelined smoother's step loop unrolled four times with fixed register roles (same loads, stores, arithmetic; measured:
+        // tools/level_timing.py).  Bit 0: the correcting red pass, bit 1: the plain pass and the from-zero sweep (2 x 8 / 2 x 4 waves of
+        // 2 rows), bit 2: the fp32 two-pair kernels; bits 0 and 1 apply to fp64 only (the fp32 one-pair kernels of the 257^3 level run
+        // short runs in many workgroups and lose 10 % unrolled) unless bit 3 is set too (tests); bit 4: the plain pass requests its
+        // column and f TWO steps ahead (six steps per loop trip; measured 2 % slower, kept for the record).  Default 7.
+        MGX_REQUIRE(value >= 0 && value <= 31, MGX_ERR_INVALID, "set_param: relax3d.unroll = %d not in [0, 31]", value);
+        ctx->pipe_unroll = value;
+    } else if (!strcmp(name, "relax3d.block3")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.block3 = %d not in {0, 1}", value);
+        ctx->block3 = (ctx->block3 & ~1) | value;  // bit 0: the way down runs its last three colour passes in one launch (relax3d_xs_block3_kernel)
+    } else if (!strcmp(name, "relax3d.block3_up")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.block3_up = %d not in {0, 1}", value);
+        ctx->block3 = (ctx->block3 & ~2) | (value << 1);  // bit 1: the way up runs its passes B, R, B after R' in one launch
+    } else if (!strcmp(name, "relax3d.block3_corr")) {
+        MGX_REQUIRE(value == 0 || value == 1, MGX_ERR_INVALID, "set_param: relax3d.block3_corr = %d not in {0, 1}", value);
+        ctx->block3 = (ctx->block3 & ~4) | (value << 2);  // bit 2: the way up runs R', B, R as one in-place launch that stores red only
+    } else if (!strcmp(name, "relax3d.zchunk")) {
+        MGX_REQUIRE(value >= 0, MGX_ERR_INVALID, "relax3d.zchunk must be >= 0 (0 = automatic)");
+        ctx->relax_zchunk = value;
+    } else {
+        return mgx::fail(MGX_ERR_INVALID, "set_param: unknown parameter '%s'", name);
+    }
     return MGX_OK;
 }
 

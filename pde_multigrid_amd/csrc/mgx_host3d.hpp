@@ -1,0 +1,105 @@
+// mgx_host3d.hpp -- the host side the 3D translation units share: launch shapes, argument checks and the declaration of every
+// host function that one 3D unit defines and another one calls.
+//
+// One home per kernel: the library is compiled with -fno-gpu-rdc, so a unit that launches a kernel template gets a copy of
+// that kernel in its own code object.  A launch site in another unit therefore calls the host function declared here, which
+// lives beside the kernel; it never names the kernel template itself.
+#pragma once
+#include "mgx_kernels3d.hpp"
+
+namespace mgx {
+
+// Everything below is shared by the files of the library, not part of its interface: hidden from the symbol table of the
+// shared object.
+#pragma GCC visibility push(hidden)
+
+inline dim3 blk() { return dim3(64, 4, 1); }
+inline dim3 grd(int nx, int ny, int nz) { return dim3(ceil_div(nx, 64), ceil_div(ny, 4), nz); }
+
+inline int check_n3(const int n[3], const char* what) {
+    MGX_REQUIRE(n, MGX_ERR_INVALID, "%s: size array is NULL", what);
+    for (int d = 0; d < 3; d++)
+        MGX_REQUIRE(valid_size(n[d]), MGX_ERR_SIZE, "%s: size[%d] = %d is not odd and >= 3", what, d, n[d]);
+    MGX_REQUIRE((double)n[0] * n[1] * n[2] < 2147483647.0 * 4, MGX_ERR_SIZE, "%s: grid too large", what);
+    return MGX_OK;
+}
+
+inline int check_coarse3(const int fn[3], const int cn[3], const char* what) {
+    MGX_REQUIRE(fn && cn, MGX_ERR_INVALID, "%s: size array is NULL", what);
+    for (int d = 0; d < 3; d++)  // the reference asserts this (N3/MultiGrid3D.cpp:60-62)
+        MGX_REQUIRE(cn[d] == (fn[d] - 1) / 2 + 1, MGX_ERR_SIZE, "%s: coarse size[%d] = %d != (%d-1)/2+1", what, d, cn[d],
+                    fn[d]);
+    return MGX_OK;
+}
+
+// the checks every entry of the residual+restrict family begins with (each entry checks its residual mode itself)
+inline int check_rr_args(mgx_ctx* ctx, bool nonnull, const int n[3], const int cn[3], const char* what) {
+    MGX_REQUIRE(nonnull, MGX_ERR_INVALID, "%s: NULL argument", what);
+    MGX_USE(ctx);
+    MGX_TRY_RET(check_n3(n, what));
+    return check_coarse3(n, cn, what);
+}
+
+// What one unit defines and others call.  The templates are instantiated explicitly, for float and double, in the unit named
+// above them.
+
+// ---- mgx_kernels3d.hip
+bool relax3d_lds_shape_known(int shape);
+// the colour-pass smoother, x-split layout (mgx_sweep3d.hip falls back to it)
+template <class real>
+int relax3d_xs_colour_passes(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int ncycles);
+template <class real>
+int relax3d_xs_from_zero(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int ncycles, int rim_is_zero);
+
+// ---- mgx_rr3d.hip: residual + restrict
+// How a residual+restrict launch runs (rr_plan decides it).  The kernels: the LDS rolling window (residual_restrict3d_kernel),
+// the streaming shuffle kernel (residual_restrict3d_xs_kernel), the pipelined kernel (residual_restrict3d_xs_pipe_kernel), all
+// three in mgx_rr3d.hip, and the fused black pass + residual + restrict (relax_rr3d_xs_kernel, mgx_relax_rr3d.hip).
+enum class RRKernel { Window, Shuffle, Pipe, Black };
+struct RRPlan {
+    RRKernel kernel = RRKernel::Window;
+    int T = 4, CR = 1, OWN = 4;       // waves per workgroup (TYW, T); Shuffle: coarse rows per lane; Pipe: fine rows per wave
+    int gx = 0, gy = 0, pzchunk = 0;  // tiles across x and y, coarse planes per run
+    dim3 grid, block;
+    int xcd = 0;
+};
+bool rr_plan(const mgx_ctx* ctx, bool xsplit, bool black, const int n[3], const int cn[3], int planes, RRPlan& p);
+template <class real, class L>
+int residual_restrict3d(mgx_ctx* ctx, const real* v, const real* f, const int n[3], const real h[3], int mode, real* coarse_f,
+                        const int cn[3], bool rim_is_zero = false);
+
+// ---- mgx_relax_rr3d.hip: the last black pass inside the residual+restrict launch
+bool relax_rr3d_xs_takes(const mgx_ctx* ctx, const int n[3], const int cn[3], size_t elem);
+template <class real>
+bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int mode, real* coarse_f,
+                          const int cn[3], int fzoff, int czoff, int pzbeg, int pzend);
+
+// ---- mgx_block3d.hip: three colour passes in one launch (fp64; the float form is never taken and does nothing)
+bool relax_block3_takes(const mgx_ctx* ctx, const int n[3], size_t elem, int part);
+template <class real>
+void relax3d_xs_block3_launch(mgx_ctx* ctx, const real* vin, real* vout, const real* f, const int n[3], real hx2, real hy2, real hz2,
+                              int first_colour, bool store_both, const real* coarse = nullptr, const int* cn = nullptr);
+template <>
+void relax3d_xs_block3_launch<float>(mgx_ctx*, const float*, float*, const float*, const int[3], float, float, float, int, bool, const float*,
+                                     const int*);
+
+// ---- mgx_sweep3d.hip: one launch per red+black sweep with a ping-pong partner array
+struct SweepSync;                                // mgx_sync.hpp
+int sweep_state(mgx_ctx* ctx, SweepSync* out);  // the context's progress words (allocated on first use)
+template <class real>
+int relax3d_xs_pp(mgx_ctx* ctx, real* v, real* w, const real* f, const int n[3], const real h[3], int ncycles, int w_rim_valid);
+template <class real>
+void copy_rim3d_xs(mgx_ctx* ctx, const real* v, real* w, const int n[3]);
+
+// ---- mgx_resident3d.hip: all colour passes of a Relax call on a cache-resident level in one launch
+bool relax3d_resident_takes(const mgx_ctx* ctx, const int n[3], int ncycles);
+template <class real>
+int relax3d_resident(mgx_ctx* ctx, real* v, const real* f, const int n[3], real hx2, real hy2, real hz2, int ncycles, int zero_start);
+
+// ---- mgx_krylov3d.hip
+// dev_sum[s] = the sum of work[s * count .. (s + 1) * count) for s < nsums, in a fixed order (also used by mgx_stencil3d.hpp)
+int krylov_final(mgx_ctx* ctx, const double* work, size_t count, int nsums, double* dev_sum);
+
+#pragma GCC visibility pop
+
+}  // namespace mgx

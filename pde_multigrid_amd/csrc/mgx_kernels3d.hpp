@@ -1,5 +1,6 @@
 // mgx_kernels3d.hpp -- per-point expressions of the 3D operators (device inline), shared by
-// the kernels of both array layouts (natural and x-split) in mgx_kernels3d.hip.
+// the kernels of both array layouts (natural and x-split) in mgx_kernels3d.hip, mgx_rr3d.hip and the files of the later families
+// (what their host sides share: mgx_host3d.hpp).
 //
 // These are the ONLY places where the arithmetic of the reference is restated on the device;
 // each keeps the reference's association order so that results are bit-identical
@@ -52,27 +53,6 @@ template <class real>
 inline bool planes_fit_descriptor(int sx, int sy) {
     return (unsigned long long)Geo<XSplit, real>(sx, sy).PL * sizeof(real) * 4ull < (1ull << 32);
 }
-
-// How a residual+restrict launch runs (rr_plan in mgx_kernels3d.hip decides it).  The kernels: the LDS rolling window
-// (residual_restrict3d_kernel), the streaming shuffle kernel (residual_restrict3d_xs_kernel), the pipelined kernel
-// (residual_restrict3d_xs_pipe_kernel) and the fused black pass + residual + restrict (relax_rr3d_xs_kernel, mgx_relax_rr3d.hip).
-enum class RRKernel { Window, Shuffle, Pipe, Black };
-struct RRPlan {
-    RRKernel kernel = RRKernel::Window;
-    int T = 4, CR = 1, OWN = 4;       // waves per workgroup (TYW, T); Shuffle: coarse rows per lane; Pipe: fine rows per wave
-    int gx = 0, gy = 0, pzchunk = 0;  // tiles across x and y, coarse planes per run
-    dim3 grid, block;
-    int xcd = 0;
-};
-// (shared by two files of the library, not part of its interface: hidden from the symbol table of the shared object)
-__attribute__((visibility("hidden"))) bool rr_plan(const mgx_ctx* ctx, bool xsplit, bool black, const int n[3], const int cn[3], int planes,
-                                                   RRPlan& p);
-template <class real>  // mgx_relax_rr3d.hip
-__attribute__((visibility("hidden"))) bool relax_rr3d_xs_launch(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int mode,
-                                                                real* coarse_f, const int cn[3], int fzoff, int czoff, int pzbeg, int pzend);
-
-// dev_sum[s] = the sum of work[s * count .. (s + 1) * count) for s < nsums, in a fixed order (mgx_krylov3d.hip; also used by mgx_stencil3d.hpp)
-__attribute__((visibility("hidden"))) int krylov_final(mgx_ctx* ctx, const double* work, size_t count, int nsums, double* dev_sum);
 
 // two consecutive elements of `real` as one vector value
 template <class real>

@@ -501,7 +501,7 @@ size_t krylov_work_elems(const int n[3]) {
     return 2 * (size_t)g.x * g.y;
 }
 
-int krylov_final(mgx_ctx* ctx, const double* work, size_t count, int nsums, double* dev_sum) {  // (declared in mgx_kernels3d.hpp)
+int krylov_final(mgx_ctx* ctx, const double* work, size_t count, int nsums, double* dev_sum) {  // (declared in mgx_host3d.hpp)
     MGX_LAUNCH(cg_final_kernel, dim3(nsums), dim3(1024), 0, ctx->compute, work, count, dev_sum);
     MGX_LAUNCH_CHECK();
     return MGX_OK;

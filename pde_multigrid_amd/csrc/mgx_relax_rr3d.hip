@@ -28,8 +28,7 @@
 // grid, which no pass writes) are loaded by the lanes / rows / planes that hold them.
 #include <type_traits>
 
-#include "mgx_internal.hpp"
-#include "mgx_kernels3d.hpp"
+#include "mgx_host3d.hpp"
 
 namespace mgx {
 

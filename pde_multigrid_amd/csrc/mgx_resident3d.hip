@@ -18,8 +18,7 @@
 //
 // A wave owns 2 rows x 2 planes of the tile (16 waves); lane i the x-pair {2i, 2i+1}.  With 129 points per row the last even
 // entry (x = 128, a boundary value) has no lane: it rides in a register per line.
-#include "mgx_internal.hpp"
-#include "mgx_kernels3d.hpp"
+#include "mgx_host3d.hpp"
 #include "mgx_sync.hpp"
 
 namespace mgx {

@@ -14,6 +14,7 @@
 #pragma once
 #include <cmath>
 
+#include "mgx_host3d.hpp"
 #include "mgx_semi3d.hpp"
 
 namespace mgx {

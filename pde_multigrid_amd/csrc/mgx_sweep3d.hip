@@ -28,8 +28,7 @@
 //
 // z-runs of one tile are independent: a run recomputes the red plane below its first and above its last plane (from vin,
 // never stored), so nothing is exchanged in z.
-#include "mgx_internal.hpp"
-#include "mgx_kernels3d.hpp"
+#include "mgx_host3d.hpp"
 #include "mgx_sync.hpp"
 
 namespace mgx {
@@ -803,9 +802,6 @@ static int sweep3d_launch(mgx_ctx* ctx, int shape, const real* vin, real* vout, 
     }
 }
 
-template <class real>
-int relax3d_xs_colour_passes(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int ncycles);  // mgx_kernels3d.hip
-
 // `ncycles` red-black sweeps of v (N3/MultiGrid3D.cpp:489-567), x-split layout, with a second array w of the same size
 // as ping-pong partner: result in v, w is scratch.  w_rim_valid != 0: the caller vouches that the boundary entries of w
 // already equal those of v (a hierarchy that has run this before and has not touched either boundary since).
@@ -847,9 +843,6 @@ template void copy_rim3d_xs<double>(mgx_ctx*, const double*, double*, const int[
 
 template int relax3d_xs_pp<float>(mgx_ctx*, float*, float*, const float*, const int[3], const float[3], int, int);
 template int relax3d_xs_pp<double>(mgx_ctx*, double*, double*, const double*, const int[3], const double[3], int, int);
-
-template <class real>
-int relax3d_xs_from_zero(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int ncycles, int rim_is_zero);  // mgx_kernels3d.hip
 
 template <class real>
 static bool from_zero_pp_takes(const mgx_ctx* ctx, const int n[3], int ncycles, int rim_is_zero) {

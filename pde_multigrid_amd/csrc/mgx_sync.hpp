@@ -40,11 +40,4 @@ constexpr unsigned SWEEP_SPIN_LIMIT = 1u << 21;  // default of "sync.spin_limit"
 
 constexpr int SWEEP_MAX_WG = 2048;  // progress words per context
 
-int sweep_state(mgx_ctx* ctx, SweepSync* out);  // mgx_sweep3d.hip: the context's words (allocated on first use)
-
-// mgx_resident3d.hip: all colour passes of a Relax call on a cache-resident level in one launch
-bool relax3d_resident_takes(const mgx_ctx* ctx, const int n[3], int ncycles);
-template <class real>
-int relax3d_resident(mgx_ctx* ctx, real* v, const real* f, const int n[3], real hx2, real hy2, real hz2, int ncycles, int zero_start);
-
 }  // namespace mgx
