@@ -80,6 +80,12 @@ typedef struct mgGraphRec {
 typedef struct mgGraphFlags {
     unsigned char a[MG_GRAPH_FLAG_ARRAYS][MG_MAX_LEVELS];
 } mgGraphFlags;
+/* the values of PCG's and BackwardEuler's `krylov`: plain cycling, flexible CG over the interior (any other non-zero value is taken
+ * as this one), flexible CG in the weighted inner product over all unknowns -- the Krylov solver of a hierarchy with Neumann
+ * faces; without a mask it is MG_KRYLOV_CG launch for launch */
+#define MG_KRYLOV_NONE 0
+#define MG_KRYLOV_CG 1
+#define MG_KRYLOV_WEIGHTED 2
 #define MG_NORM_HISTORY 255 /* residual-norm history entries a distributed hierarchy keeps on the device */
 #define MG_DECLARE(R, real)                                                                              \
     /* ------------------------------------------------------------------ 3D ------ */                  \
@@ -115,7 +121,12 @@ typedef struct mgGraphFlags {
                        /* change, or the context's parameters, mgx_ctx_generation).  Default 0.       */ \
         int capturing;                                                                                   \
         void* graph_exec[MG_MAX_LEVELS];                                                                 \
-        long long graph_key[MG_MAX_LEVELS];                                                              \
+        long long graph_key[MG_MAX_LEVELS - 1]; /* unused */                                             \
+        /* internal: PCG's fifth level-0 scratch array, the projected right-hand side f - mean_W(f) of   */ \
+        /* the closed box without a shift (krylov = 2; allocated by the first such call, freed by        */ \
+        /* _destroy).  It takes the last eight bytes of the unused graph_key: every member keeps its     */ \
+        /* offset and the struct its size.                                                               */ \
+        real* pcg_fproj;                                                                                 \
         /* internal: 1 when the boundary entries of level l's d_f are known to be 0 (left so by the     */ \
         /* previous cycle's residual+restrict); cleared by InitF / upload_f / Restrict / setToValue.    */ \
         /* Those entries are never read by any operator; the flag only saves re-zeroing them.           */ \
@@ -146,7 +157,7 @@ typedef struct mgGraphFlags {
         /* bytes of the unused pcg_graph_key that stood here: the struct keeps its size, every member    */ \
         /* its offset, and `shift` stays the last one.                                                   */ \
         int bc;                                                                                          \
-        int bc_reserved; /* unused, 0 */                                                                 \
+        int bc_reserved; /* internal: 1 inside PCG's projected solve (krylov = 2, closed box, shift 0)   */ \
         /* internal: the record each graph was captured under and the rim flags its capture left behind  */ \
         /* (graph_key[] above is unused likewise)                                                        */ \
         mgGraphRec graph_rec[MG_MAX_LEVELS];                                                             \
@@ -183,7 +194,9 @@ typedef struct mgGraphFlags {
     /* all unknowns, unweighted.  That needs layout = 1, smoother = 0, residual_mode =                   */ \
     /* MGX_RESIDUAL_CORRECT and a hierarchy that is not semi-coarsened (else MGX_ERR_INVALID, here and   */ \
     /* where the mask is used); all six faces with shift == 0 is singular and MGX_ERR_INVALID where the  */ \
-    /* operator is used; PCG(krylov != 0) and PCG_mixed return MGX_ERR_INVALID.  A prescribed flux g     */ \
+    /* operator is used -- but PCG(krylov = 2), CG in the weighted inner product over all unknowns,     */ \
+    /* solves it in the projected sense (see PCG); PCG(krylov = 1), BackwardEuler(krylov = 1) and        */ \
+    /* PCG_mixed return MGX_ERR_INVALID with a mask.  A prescribed flux g                                */ \
     /* (du/dn = g, outward) is not an argument: subtract 2 g a / h from f at the face.  All zeros: the   */ \
     /* hierarchy is what it was without a mask.  A change of the mask drops the captured graphs and      */ \
     /* zeroes, on the levels below the finest, the entries of d_v the old mask made unknowns.  Blocking. */ \
@@ -265,6 +278,18 @@ typedef struct mgGraphFlags {
     /* host_hist[k] (k < hist_cap) = relative residual after iteration k + 1 (recursive for CG).  A     */ \
     /* breakdown (<p, q> zero or not finite) returns MGX_OK with *converged = 0.  use_graph captures   */ \
     /* the preconditioning V-cycle.  Blocking: the host reads one double per iteration.                */ \
+    /* krylov = MG_KRYLOV_WEIGHTED (2): flexible CG in the inner product <a, b>_W = sum of W a b over all */ \
+    /* unknowns, W = 1/2 per Neumann face an unknown lies on, in which the operator with a mask is        */ \
+    /* symmetric.  Without a mask every weight is 1: the launches and the bits of          */ \
+    /* krylov = 1.  With a mask it is the Krylov solver (krylov = 1 is then MGX_ERR_INVALID): the         */ \
+    /* mgx3dxs_*_bc vector entries on all unknowns; rr0, the recursive norm, the true-residual check and  */ \
+    /* *rel_res stay unweighted over all unknowns, as with krylov = 0.  All six faces Neumann with        */ \
+    /* shift == 0 (singular: refused everywhere else) is solved in the projected sense: the system is     */ \
+    /* A v = f - mean_W(f), every residual is taken against that right-hand side, the preconditioned      */ \
+    /* residual loses its weighted mean after every V-cycle, so v keeps the weighted mean of the guess;   */ \
+    /* d_f[0] is restored to f bit for bit and _pcg_removed_mean gives mean_W(f) (0 after any other       */ \
+    /* solve).                                                                                            */ \
+    int mgMultiGrid3D_##R##_pcg_removed_mean(mgMultiGrid3D_##R* mg, double* mean);                       \
     int mgMultiGrid3D_##R##_PCG(mgMultiGrid3D_##R* mg, int v1, int v2, double tol, int maxit, int krylov, \
                                 int* iters, double* rel_res, int* converged, double* host_hist,          \
                                 int hist_cap);                                                           \
@@ -276,7 +301,8 @@ typedef struct mgGraphFlags {
     /* guess u.  *iters_total = PCG iterations of all steps, *worst_rel_res = the largest true relative  */ \
     /* residual of a step; it stops at the first step that does not converge, with *converged = 0.       */ \
     /* The shift it sets STAYS SET afterwards (and d_f[0] holds the last step's right-hand side).        */ \
-    /* Needs dt > 0, kappa > 0, nsteps >= 0 and the settings of a shifted hierarchy.                     */ \
+    /* Needs dt > 0, kappa > 0, nsteps >= 0 and the settings of a shifted hierarchy.  krylov is PCG's:   */ \
+    /* with a mask 0 or MG_KRYLOV_WEIGHTED.                                                              */ \
     int mgMultiGrid3D_##R##_BackwardEuler(mgMultiGrid3D_##R* mg, int nsteps, double dt, double kappa,    \
                                           const real* d_source, int v1, int v2, double tol, int maxit,   \
                                           int krylov, int* iters_total, double* worst_rel_res,           \
@@ -296,7 +322,8 @@ typedef struct mgGraphFlags {
                                  int ncycles, int residual_mode);                                        \
     /* solve_pcg: mgMultiGrid3D_<r>_PCG on a hierarchy built for the call (x-split, CORRECT residual);   */ \
     /* grid = initial guess with its Dirichlet boundary on input, solution on output; host arrays in    */ \
-    /* the reference layout; rhs == NULL: the reference's own right-hand side                           */ \
+    /* the reference layout; rhs == NULL: the reference's own right-hand side; krylov as in PCG (the    */ \
+    /* hierarchy has no mask: MG_KRYLOV_WEIGHTED gives the bits of 1)                                   */ \
     int mg3d_solve_pcg_##R(mgx_ctx* ctx, real* grid, const real* rhs, const int sizeXYZ[3],              \
                            const real range[6], int nlevels, int v1, int v2, double tol, int maxit,      \
                            int krylov, int* iters, double* rel_res, int* converged);                     \

@@ -641,7 +641,41 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
                                              const real* coarse_v, const int cn[3], int bc);            \
     int mgx3dxs_shift_rhs_bc_##SFX(mgx_ctx* ctx, const real* u, const real* q, real qscale, real s,     \
                                    real* f, const int n[3], int bc);                                    \
-    int mgx3dxs_set_rim_bc_##SFX(mgx_ctx* ctx, real* v, const int n[3], real value, int bc);
+    int mgx3dxs_set_rim_bc_##SFX(mgx_ctx* ctx, real* v, const int n[3], real value, int bc);            \
+    /* The vector kernels of the solve over ALL unknowns (csrc/mgx_rim3d.hip): flexible CG */ \
+    /* on a hierarchy with a mask works in the inner product <a, b>_W = sum of W a b over the unknowns, */ \
+    /* W = 1/2 per Neumann face an unknown lies on (the trapezoid weights of section 15, in which A is */ \
+    /* symmetric), 1 in the interior.  Each entry is the entry without _bc plus the mask; with bc = 0 it */ \
+    /* calls that entry and nothing else.  Otherwise the interior launch runs unchanged, one launch over */ \
+    /* the face unknowns follows it, its block partials go behind the interior launch's in dev_work and */ \
+    /* one final sum adds both, in a fixed order: the same bits on every run.  Dirichlet entries are  */ \
+    /* never written and pads neither read as data nor written.  MGX_ERR_INVALID for NULL arguments and */ \
+    /* a bc outside 0 .. 63, checked before any argument is used; MGX_ERR_SIZE for bad sizes.         */ \
+    /* krylov_work_elems_bc: the doubles of dev_work these entries need: two sums, each the interior  */ \
+    /*   partials plus the most rim partials of any mask (mgx3dxs_krylov_work_elems keeps its value). */ \
+    /* laplace_dot_shift_bc, apply_coef_dot_bc: q = A p at every unknown (at a face unknown the interior */ \
+    /*   expression on the reflected star), *dev_sum = <p, q>_W.  The plain Laplacian is s = 0.       */ \
+    /* cg_update_bc: [x += a p;] r -= a q at every unknown; *dev_sum = <r, r>, UNWEIGHTED over all    */ \
+    /*   unknowns: the stopping rule's norm, that of residual_*_bc.                                   */ \
+    /* dot2_bc: dev_sum[0] = <a, b>_W and, unless c is NULL, dev_sum[1] = <a, c>_W.                   */ \
+    /* cg_direction_bc: the three forms of cg_direction at every unknown.                             */ \
+    /* project_bc: *dev_mean = sum_W(a) / sum(W) in double, then a -= (real)*dev_mean at every unknown, */ \
+    /*   with no host read in between (bc = 0: the interior and its plain mean).                      */ \
+    size_t mgx3dxs_krylov_work_elems_bc_##SFX(const int n[3]);                                          \
+    int mgx3dxs_laplace_dot_shift_bc_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3],        \
+                                           const real h[3], real s, double* dev_work, double* dev_sum,  \
+                                           int bc);                                                     \
+    int mgx3dxs_apply_coef_dot_bc_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q,            \
+                                        const int n[3], const real h[3], real s, double* dev_work,      \
+                                        double* dev_sum, int bc);                                       \
+    int mgx3dxs_cg_update_bc_##SFX(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q,        \
+                                   const int n[3], const double* dev_alpha, double* dev_work,           \
+                                   double* dev_sum, int bc);                                            \
+    int mgx3dxs_dot2_bc_##SFX(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3],\
+                              double* dev_work, double* dev_sum, int bc);                               \
+    int mgx3dxs_cg_direction_bc_##SFX(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3],    \
+                                      const double* dev_alpha, const double* dev_beta, int bc);         \
+    int mgx3dxs_project_bc_##SFX(mgx_ctx* ctx, real* a, const int n[3], double* dev_work, double* dev_mean, int bc);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)
@@ -688,8 +722,11 @@ int mgx3dxs_cg_direction_mixed_f64(mgx_ctx* ctx, double* x, double* p, const flo
  *   step 0: alpha = RZ / PQ; NaN when PQ is 0 or alpha or PQ is not finite (a breakdown: the following cg_update then
  *           reports a NaN norm);
  *   step 1: beta = -alpha ZQ / RZ (Polak-Ribiere: = <z, r_new - r_old> / <r_old, z_old>), then RZ = ZR;
- *   step 2: RZ = ZR (restart). */
-enum { MGX_CG_RZ = 0, MGX_CG_PQ = 1, MGX_CG_ALPHA = 2, MGX_CG_RR = 3, MGX_CG_ZR = 4, MGX_CG_ZQ = 5, MGX_CG_BETA = 6, MGX_CG_STATE = 8 };
+ *   step 2: RZ = ZR (restart).
+ * FMEAN is no part of the iteration: the weighted mean mgMultiGrid3D_<r>_PCG removed from the right-hand side of a closed box
+ * without a shift (mg_multigrid.h), 0 after every other solve. */
+enum { MGX_CG_RZ = 0, MGX_CG_PQ = 1, MGX_CG_ALPHA = 2, MGX_CG_RR = 3, MGX_CG_ZR = 4, MGX_CG_ZQ = 5, MGX_CG_BETA = 6, MGX_CG_FMEAN = 7,
+       MGX_CG_STATE = 8 };
 int mgx_cg_scalars(mgx_ctx* ctx, double* dev_state, int step);
 
 /* ---- multi-GPU: z-slab halo exchange over RCCL (xGMI) ------------------------------

@@ -222,6 +222,7 @@ int mgMultiGrid3D_f64_PCG_mixed(mgMultiGrid3D_f64* mg, int v1, int v2, double to
     *rel_res = 0.0;
     *converged = 0;
     MG_TRY(pcg_alloc3_f64(mg));
+    MG_TRY(mgx_memset_zero(mg->ctx, mg->pcg_state + MGX_CG_FMEAN, sizeof(double))); /* (no mean is removed here) */
     mgMixed3D* m = NULL;
     MG_TRY(mg_mixed3d_twin(mg, &m));
     if (!krylov) return mg_mixed3d_ir(mg, m, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);

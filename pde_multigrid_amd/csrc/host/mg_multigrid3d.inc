@@ -196,7 +196,7 @@ void FN(destroy)(MGRID* mg) {
         if (mg->graph_exec[i]) mgx_graph_destroy(mg->ctx, mg->graph_exec[i]);
     if (mg->pcg_graph_exec) mgx_graph_destroy(mg->ctx, mg->pcg_graph_exec);
     mgx_free(mg->ctx, mg->pcg_x); mgx_free(mg->ctx, mg->pcg_b); mgx_free(mg->ctx, mg->pcg_p); mgx_free(mg->ctx, mg->pcg_q);
-    mgx_free(mg->ctx, mg->pcg_state); mgx_free(mg->ctx, mg->pcg_work);
+    mgx_free(mg->ctx, mg->pcg_state); mgx_free(mg->ctx, mg->pcg_work); mgx_free(mg->ctx, mg->pcg_fproj);
     mg_mixed3d_free(mg->ctx, mg->pcg_mixed);
     if (mg->grids3D)
         for (int i = 0; i < mg->maxGrids; i++) MG_CAT(grid3_free_, R)(mg->ctx, mg->grids3D[i]);
@@ -271,9 +271,10 @@ static int MG_CAT(bc_ok3_, R)(const MGRID* mg, int bc, const char* what) {
     return MGX_OK;
 }
 /* ... and of the operator: a closed box without a shift has no unique solution (checked where the operator is used only: the
- * shift is a public member and may still change after set_boundary) */
+ * shift is a public member and may still change after set_boundary).  bc_reserved is set while PCG(krylov = 2) solves that
+ * system in the projected sense: its preconditioner's Relax and residual then pass. */
 static int MG_CAT(bc_singular3_, R)(const MGRID* mg, const char* what) {
-    MG_REQUIRE(!(mg->bc == 63 && mg->shift == 0), MGX_ERR_INVALID,
+    MG_REQUIRE(!(mg->bc == 63 && mg->shift == 0) || mg->bc_reserved, MGX_ERR_INVALID,
                "%s: Neumann data on all six faces with shift = 0 is singular (set a shift > 0 or keep a Dirichlet face)", what);
     return MGX_OK;
 }
@@ -302,9 +303,13 @@ static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, con
     return dev_sumsq ? MG_CAT(mgx3dxs_dot2_, R)(mg->ctx, r, r, NULL, g->sizeXYZ, dev_work, dev_sumsq) : MGX_OK;
 }
 
-/* q = A p on grid g by the hierarchy's operator (x-split, CORRECT mode), *dev_sum = <p, q> */
+/* q = A p on grid g by the hierarchy's operator (x-split, CORRECT mode), *dev_sum = <p, q>; with a mask at all unknowns and in the
+ * weighted inner product (the plain Laplacian is then the shifted operator with s = 0) */
 static int MG_CAT(op_apply_dot3_, R)(MGRID* mg, const GRID* g, const REAL* p, REAL* q, double* dev_work, double* dev_sum) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    if (mg->bc && MG_CAT(has_coef3_, R)(mg))
+        return MG_CAT(mgx3dxs_apply_coef_dot_bc_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc);
+    if (mg->bc) return MG_CAT(mgx3dxs_laplace_dot_shift_bc_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc);
     if (MG_CAT(has_coef3_, R)(mg))
         return MG_CAT(mgx3dxs_apply_coef_dot_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum);
     if (mg->shift != 0) return MG_CAT(mgx3dxs_laplace_dot_shift_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum);
@@ -895,14 +900,16 @@ static int MG_CAT(pcg_alloc3_, R)(MGRID* mg) {
     if (mg->pcg_x) return MGX_OK;
     GRID* g = mg->grids3D[0];
     const size_t bytes = MG_CAT(dvol3_, R)(mg->layout, g) * sizeof(REAL);
-    const size_t wbytes = MG_CAT(mgx3dxs_krylov_work_elems_, R)(g->sizeXYZ) * sizeof(double);
+    /* (the entries for all unknowns put the partials of the face unknowns behind those of the interior: the larger count) */
+    const size_t wbytes = MG_CAT(mgx3dxs_krylov_work_elems_bc_, R)(g->sizeXYZ) * sizeof(double);
     int st;
     if ((st = mgx_malloc(mg->ctx, bytes, (void**)&mg->pcg_x)) || (st = mgx_malloc(mg->ctx, bytes, (void**)&mg->pcg_b)) ||
         (st = mgx_malloc(mg->ctx, bytes, (void**)&mg->pcg_p)) || (st = mgx_malloc(mg->ctx, bytes, (void**)&mg->pcg_q)) ||
         (st = mgx_malloc(mg->ctx, MGX_CG_STATE * sizeof(double), (void**)&mg->pcg_state)) ||
         (st = mgx_malloc(mg->ctx, wbytes, (void**)&mg->pcg_work)) ||
         /* p and q: their boundary and pad entries are never written by the kernels; zero them once (q's boundary is read */
-        /* by nobody, p's by the Laplacian as zero Dirichlet data) */
+        /* by nobody, p's by the Laplacian as zero Dirichlet data).  A solve with a mask writes the face unknowns of both and */
+        /* zeroes them again before it returns. */
         (st = mgx_memset_zero(mg->ctx, mg->pcg_p, bytes)) || (st = mgx_memset_zero(mg->ctx, mg->pcg_q, bytes)) ||
         (st = mgx_memset_zero(mg->ctx, mg->pcg_state, MGX_CG_STATE * sizeof(double)))) {
         mgx_free(mg->ctx, mg->pcg_x); mgx_free(mg->ctx, mg->pcg_b); mgx_free(mg->ctx, mg->pcg_p); mgx_free(mg->ctx, mg->pcg_q);
@@ -917,9 +924,14 @@ static int MG_CAT(pcg_alloc3_, R)(MGRID* mg) {
 /* flexible CG (the algorithm of mg_multigrid.h).  r lives in d_f[0] (the preconditioner's right-hand side), z in d_v[0] (its
  * result); x, a copy of b, p and q in the scratch.  The update of x by alpha p is deferred into the next direction pass
  * (x += alpha p; p = z + beta p in one pass over p), so an iteration streams 13 reals per point outside the V-cycle:
- * laplace_dot 2, cg_update 3 (r, q -> r), dot2 3 (z, r, q), cg_direction 5 (x, p, z -> x, p). */
+ * laplace_dot 2, cg_update 3 (r, q -> r), dot2 3 (z, r, q), cg_direction 5 (x, p, z -> x, p).
+ * bc: the mask the vector kernels run with -- the hierarchy's (krylov = 2), where r, z, p, q and x live on all unknowns and the
+ * dots that make alpha and beta are the weighted ones (DESIGN.md 16), while rr0, the recursive norm and the true-residual check
+ * stay unweighted over all unknowns as pcg_plain3_ has them; 0 runs the interior entries and nothing else.
+ * singular (the closed box without a shift): the system solved is A x = f - mean_W(f), the projected right-hand side in
+ * pcg_fproj, every residual against it, and z := z - mean_W(z) after every preconditioner application, outside its graph. */
 static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int maxit, int* iters, double* rel_res, int* converged,
-                                   double* host_hist, int hist_cap) {
+                                   double* host_hist, int hist_cap, int bc, int singular) {
     mgx_ctx* ctx = mg->ctx;
     GRID* g = mg->grids3D[0];
     const int* n = g->sizeXYZ;
@@ -929,27 +941,35 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
     const unsigned char v_rim0 = mg->v_rim_zero[0], f_rim0 = mg->f_rim_zero[0];
     MG_TRY(mgx_memcpy_d2d(ctx, x, g->d_v, bytes)); /* x: the guess with its Dirichlet boundary; pads are zero in both */
     MG_TRY(mgx_memcpy_d2d(ctx, b, g->d_f, bytes));
+    const REAL* rhs = b;
+    if (singular) { /* d_f[0] is restored from b, the caller's f; the removed mean stays in the state vector */
+        if (!mg->pcg_fproj) MG_TRY(mgx_malloc(ctx, bytes, (void**)&mg->pcg_fproj));
+        MG_TRY(mgx_memcpy_d2d(ctx, mg->pcg_fproj, b, bytes));
+        MG_TRY(MG_CAT(mgx3dxs_project_bc_, R)(ctx, mg->pcg_fproj, n, w, s + MGX_CG_FMEAN, bc));
+        rhs = mg->pcg_fproj;
+    }
     int st = MGX_OK;
     double rr0 = 0.0, rr = 0.0;
     int pending = 0; /* x still lacks alpha p of the last iteration */
     /* r = b - A x (0 on the boundary), ||r0|| */
-    st = MG_CAT(op_residual3_, R)(mg, g, x, b, r, w, s + MGX_CG_RR);
+    st = MG_CAT(op_residual3_, R)(mg, g, x, rhs, r, w, s + MGX_CG_RR);
     mg->f_rim_zero[0] = 0;
     if (!st) st = mgx_memcpy_d2h(ctx, &rr0, s + MGX_CG_RR, sizeof(double));
     if (!st && rr0 == 0.0) *converged = 1;
     int restart = 1; /* z = M r, p = z, rz = <r, z> */
     for (int k = 1; !st && !*converged && k <= maxit; k++) {
         if (restart) {
-            st = MG_CAT(pcg_precond3_, R)(mg, v1, v2);
-            if (!st) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, z, r, NULL, n, w, s + MGX_CG_ZR);
+            st = MG_CAT(pcg_precond3_, R)(mg, v1, v2); /* (ZR is dead until dot2 writes it: the projection's mean goes there) */
+            if (!st && singular) st = MG_CAT(mgx3dxs_project_bc_, R)(ctx, z, n, w, s + MGX_CG_ZR, bc);
+            if (!st) st = MG_CAT(mgx3dxs_dot2_bc_, R)(ctx, z, r, NULL, n, w, s + MGX_CG_ZR, bc);
             if (!st) st = mgx_cg_scalars(ctx, s, 2);
-            if (!st) st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, NULL, p, z, n, NULL, NULL);
+            if (!st) st = MG_CAT(mgx3dxs_cg_direction_bc_, R)(ctx, NULL, p, z, n, NULL, NULL, bc);
             restart = 0;
         }
         /* q = A p, alpha = <r, z> / <p, q>; r -= alpha q */
         if (!st) st = MG_CAT(op_apply_dot3_, R)(mg, g, p, q, w, s + MGX_CG_PQ);
         if (!st) st = mgx_cg_scalars(ctx, s, 0);
-        if (!st) st = MG_CAT(mgx3dxs_cg_update_, R)(ctx, NULL, p, r, q, n, s + MGX_CG_ALPHA, w, s + MGX_CG_RR);
+        if (!st) st = MG_CAT(mgx3dxs_cg_update_bc_, R)(ctx, NULL, p, r, q, n, s + MGX_CG_ALPHA, w, s + MGX_CG_RR, bc);
         if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double)); /* the one host read of the iteration */
         if (st) break;
         *iters = k;
@@ -958,9 +978,9 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
         const double rel = sqrt(rr / rr0);
         if (k - 1 < hist_cap) host_hist[k - 1] = rel;
         if (rel < tol) { /* the recursive residual may have drifted from b - A x: check the true one */
-            st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL);
+            st = MG_CAT(mgx3dxs_cg_direction_bc_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL, bc);
             pending = 0;
-            if (!st) st = MG_CAT(op_residual3_, R)(mg, g, x, b, r, w, s + MGX_CG_RR);
+            if (!st) st = MG_CAT(op_residual3_, R)(mg, g, x, rhs, r, w, s + MGX_CG_RR);
             if (!st) st = mgx_memcpy_d2h(ctx, &rr, s + MGX_CG_RR, sizeof(double));
             if (!st && sqrt(rr / rr0) < tol) *converged = 1;
             restart = 1; /* otherwise go on from the true residual */
@@ -968,16 +988,17 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
         }
         /* z = M r; beta = -alpha <z, q> / <r, z>_old; x += alpha p; p = z + beta p */
         st = MG_CAT(pcg_precond3_, R)(mg, v1, v2);
-        if (!st) st = MG_CAT(mgx3dxs_dot2_, R)(ctx, z, r, q, n, w, s + MGX_CG_ZR);
+        if (!st && singular) st = MG_CAT(mgx3dxs_project_bc_, R)(ctx, z, n, w, s + MGX_CG_ZR, bc);
+        if (!st) st = MG_CAT(mgx3dxs_dot2_bc_, R)(ctx, z, r, q, n, w, s + MGX_CG_ZR, bc);
         if (!st) st = mgx_cg_scalars(ctx, s, 1);
-        if (!st) st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, z, n, s + MGX_CG_ALPHA, s + MGX_CG_BETA);
+        if (!st) st = MG_CAT(mgx3dxs_cg_direction_bc_, R)(ctx, x, p, z, n, s + MGX_CG_ALPHA, s + MGX_CG_BETA, bc);
         pending = 0;
     }
-    if (!st && pending) st = MG_CAT(mgx3dxs_cg_direction_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL);
+    if (!st && pending) st = MG_CAT(mgx3dxs_cg_direction_bc_, R)(ctx, x, p, NULL, n, s + MGX_CG_ALPHA, NULL, bc);
     /* the true relative residual of the result */
     if (!st && rr0 > 0.0) {
         double ss = 0.0;
-        st = MG_CAT(pcg_true_sumsq3_, R)(mg, x, b, &ss);
+        st = MG_CAT(pcg_true_sumsq3_, R)(mg, x, rhs, &ss);
         if (!st) *rel_res = sqrt(ss / rr0);
     } else if (!st && rr0 != 0.0) {
         *rel_res = rr0; /* NaN: the initial residual is not finite */
@@ -986,10 +1007,13 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
     /* boundary copy no longer matches d_v's */
     const int st2 = mgx_memcpy_d2d(ctx, g->d_v, x, bytes);
     const int st3 = mgx_memcpy_d2d(ctx, g->d_f, b, bytes);
+    /* the face unknowns of p and q back to the zeros a solve without a mask reads as Dirichlet data */
+    const int st4 = MG_CAT(mgx3dxs_set_rim_bc_, R)(ctx, p, n, (REAL)0, bc);
+    const int st5 = MG_CAT(mgx3dxs_set_rim_bc_, R)(ctx, q, n, (REAL)0, bc);
     mg->v_rim_zero[0] = v_rim0;
     mg->f_rim_zero[0] = f_rim0;
     mg->e_rim_valid[0] = 0;
-    if (!st) st = st2 ? st2 : st3;
+    if (!st) st = st2 ? st2 : st3 ? st3 : st4 ? st4 : st5;
     if (!st) st = mgx_ctx_sync(ctx);
     return st;
 }
@@ -1006,15 +1030,30 @@ int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* i
     MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "PCG"));
     if (MG_CAT(has_coef3_, R)(mg)) MG_TRY(MG_CAT(coef_ok3_, R)(mg, "PCG"));
     MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "PCG"));
-    MG_TRY(MG_CAT(bc_singular3_, R)(mg, "PCG"));
-    MG_REQUIRE(!mg->bc || !krylov, MGX_ERR_INVALID,
-               "PCG: krylov != 0 is not available with Neumann faces (the CG vector kernels are interior-only); use krylov = 0");
+    const int weighted = krylov == MG_KRYLOV_WEIGHTED;
+    if (!weighted) MG_TRY(MG_CAT(bc_singular3_, R)(mg, "PCG")); /* (krylov = 2 solves the closed box without a shift, projected) */
+    MG_REQUIRE(!mg->bc || !krylov || weighted, MGX_ERR_INVALID,
+               "PCG: krylov = %d is not available with Neumann faces (its CG vector kernels are interior-only); use krylov = 2 "
+               "(MG_KRYLOV_WEIGHTED: CG in the weighted inner product over all unknowns) or krylov = 0", krylov);
     *iters = 0;
     *rel_res = 0.0;
     *converged = 0;
     MG_TRY(MG_CAT(pcg_alloc3_, R)(mg));
+    MG_TRY(mgx_memset_zero(mg->ctx, mg->pcg_state + MGX_CG_FMEAN, sizeof(double)));
     if (!krylov) return MG_CAT(pcg_plain3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);
-    return MG_CAT(pcg_krylov3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);
+    const int singular = mg->bc == 63 && mg->shift == 0;
+    mg->bc_reserved = singular; /* "inside a projected solve": cleared on every way out */
+    const int st = MG_CAT(pcg_krylov3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap, mg->bc, singular);
+    mg->bc_reserved = 0;
+    return st;
+}
+
+/* the weighted mean the last PCG removed from the right-hand side (0 unless it solved the closed box without a shift) */
+int FN(pcg_removed_mean)(MGRID* mg, double* mean) {
+    MG_REQUIRE(mg && mean, MGX_ERR_INVALID, "pcg_removed_mean: NULL argument");
+    *mean = 0.0;
+    if (!mg->pcg_state) return MGX_OK;
+    return mgx_memcpy_d2h(mg->ctx, mean, mg->pcg_state + MGX_CG_FMEAN, sizeof(double));
 }
 
 /* implicit steps of u_t = kappa Laplacian(u) + q (an addition; mg_multigrid.h) */
@@ -1026,8 +1065,9 @@ int FN(BackwardEuler)(MGRID* mg, int nsteps, double dt, double kappa, const REAL
     const REAL s = (REAL)(1.0 / (kappa * dt)), qscale = (REAL)(1.0 / kappa);
     MG_REQUIRE(s > 0, MGX_ERR_INVALID, "BackwardEuler: 1 / (kappa dt) = %g is not a positive number of the hierarchy's precision", (double)s);
     MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "BackwardEuler"));
-    MG_REQUIRE(!mg->bc || !krylov, MGX_ERR_INVALID,
-               "BackwardEuler: krylov != 0 is not available with Neumann faces (the CG vector kernels are interior-only); use krylov = 0");
+    MG_REQUIRE(!mg->bc || !krylov || krylov == MG_KRYLOV_WEIGHTED, MGX_ERR_INVALID,
+               "BackwardEuler: krylov = %d is not available with Neumann faces (its CG vector kernels are interior-only); use krylov = 2 "
+               "(MG_KRYLOV_WEIGHTED) or krylov = 0", krylov);
     MG_TRY(FN(set_shift)(mg, s)); /* stays set */
     *iters_total = 0;
     *worst_rel_res = 0.0;

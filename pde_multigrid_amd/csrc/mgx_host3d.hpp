@@ -99,6 +99,16 @@ int relax3d_resident(mgx_ctx* ctx, real* v, const real* f, const int n[3], real 
 // ---- mgx_krylov3d.hip
 // dev_sum[s] = the sum of work[s * count .. (s + 1) * count) for s < nsums, in a fixed order (also used by mgx_stencil3d.hpp)
 int krylov_final(mgx_ctx* ctx, const double* work, size_t count, int nsums, double* dev_sum);
+// the interior launches of mgx3dxs_cg_update / _dot2 / _cg_direction.  finalize = false: no final sum, the partials stay in dev_work
+// (count = the blocks of the row walk's grid; cg_update's and dot2's <a, b> in [0, count), dot2's <a, c> in [count, 2 count)) for
+// a caller that adds partials of its own (mgx_rim3d.hip: the face unknowns)
+template <class real>
+int cg_update3d(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3], const double* dev_alpha, double* dev_work,
+                double* dev_sum, bool finalize);
+template <class real>
+int dot2_3d(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3], double* dev_work, double* dev_sum, bool finalize);
+template <class real>
+int cg_direction3d(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3], const double* dev_alpha, const double* dev_beta);
 
 #pragma GCC visibility pop
 

@@ -509,7 +509,7 @@ int krylov_final(mgx_ctx* ctx, const double* work, size_t count, int nsums, doub
 
 template <class real>
 int cg_update3d(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3], const double* dev_alpha, double* dev_work,
-                double* dev_sum) {
+                double* dev_sum, bool finalize) {  // (declared in mgx_host3d.hpp, as are the two below)
     MGX_REQUIRE(ctx && r && q && (!x || p) && dev_alpha && dev_work && dev_sum, MGX_ERR_INVALID, "cg_update: NULL argument");
     MGX_USE(ctx);
     MGX_TRY_RET(rows_check(n, "cg_update"));
@@ -517,11 +517,11 @@ int cg_update3d(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, co
     if (x) MGX_LAUNCH((cg_update3d_xs_kernel<real, true>), g, krylov_block(), 0, ctx->compute, x, p, r, q, n[0], n[1], dev_alpha, dev_work);
     else MGX_LAUNCH((cg_update3d_xs_kernel<real, false>), g, krylov_block(), 0, ctx->compute, x, p, r, q, n[0], n[1], dev_alpha, dev_work);
     MGX_LAUNCH_CHECK();
-    return krylov_final(ctx, dev_work, (size_t)g.x * g.y, 1, dev_sum);
+    return finalize ? krylov_final(ctx, dev_work, (size_t)g.x * g.y, 1, dev_sum) : MGX_OK;
 }
 
 template <class real>
-int dot2_3d(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3], double* dev_work, double* dev_sum) {
+int dot2_3d(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3], double* dev_work, double* dev_sum, bool finalize) {
     MGX_REQUIRE(ctx && a && b && dev_work && dev_sum, MGX_ERR_INVALID, "dot2: NULL argument");
     MGX_USE(ctx);
     MGX_TRY_RET(rows_check(n, "dot2"));
@@ -529,7 +529,7 @@ int dot2_3d(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int
     if (c) MGX_LAUNCH((dot2_3d_xs_kernel<real, true>), g, krylov_block(), 0, ctx->compute, a, b, c, n[0], n[1], dev_work);
     else MGX_LAUNCH((dot2_3d_xs_kernel<real, false>), g, krylov_block(), 0, ctx->compute, a, b, c, n[0], n[1], dev_work);
     MGX_LAUNCH_CHECK();
-    return krylov_final(ctx, dev_work, (size_t)g.x * g.y, c ? 2 : 1, dev_sum);
+    return finalize ? krylov_final(ctx, dev_work, (size_t)g.x * g.y, c ? 2 : 1, dev_sum) : MGX_OK;
 }
 
 template <class real>
@@ -552,6 +552,14 @@ int cg_direction3d(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3]
     return MGX_OK;
 }
 
+// (mgx_rim3d.hip calls the three: the interior launches of its entries for all unknowns)
+#define MGX_INSTANTIATE_KRYLOV(real)                                                                                                      \
+    template int cg_update3d<real>(mgx_ctx*, real*, const real*, real*, const real*, const int[3], const double*, double*, double*, bool); \
+    template int dot2_3d<real>(mgx_ctx*, const real*, const real*, const real*, const int[3], double*, double*, bool);                     \
+    template int cg_direction3d<real>(mgx_ctx*, real*, real*, const real*, const int[3], const double*, const double*);
+MGX_INSTANTIATE_KRYLOV(float)
+MGX_INSTANTIATE_KRYLOV(double)
+#undef MGX_INSTANTIATE_KRYLOV
 
 // ---- mixed precision
 // the z-marching pass: TR rows per wave (mixed3d.rows), four waves per block, runs of zchunk planes (mixed3d.zchunk; 0 =
@@ -705,11 +713,11 @@ int mgx_cg_scalars(mgx_ctx* ctx, double* dev_state, int step) {
     }                                                                                                                         \
     int mgx3dxs_cg_update_##SFX(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3],                  \
                                 const double* dev_alpha, double* dev_work, double* dev_sum) {                                 \
-        return mgx::cg_update3d<real>(ctx, x, p, r, q, n, dev_alpha, dev_work, dev_sum);                                      \
+        return mgx::cg_update3d<real>(ctx, x, p, r, q, n, dev_alpha, dev_work, dev_sum, true);                                     \
     }                                                                                                                         \
     int mgx3dxs_dot2_##SFX(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3], double* dev_work,         \
                            double* dev_sum) {                                                                                 \
-        return mgx::dot2_3d<real>(ctx, a, b, c, n, dev_work, dev_sum);                                                        \
+        return mgx::dot2_3d<real>(ctx, a, b, c, n, dev_work, dev_sum, true);                                                     \
     }                                                                                                                         \
     int mgx3dxs_cg_direction_##SFX(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3], const double* dev_alpha,      \
                                    const double* dev_beta) {                                                                  \

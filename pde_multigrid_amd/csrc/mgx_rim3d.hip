@@ -193,6 +193,189 @@ __global__ void __launch_bounds__(RIM_THREADS) rim_set3d_xs_kernel(real* __restr
     RIM_FOR_EACH_POINT(R, g, x, y, z) v[g.row(y, z) + g.pos(x)] = value;
 }
 
+// ------------------------------------------------------------------ the solve's vector kernels on the face unknowns (section 16)
+// The flexible CG of a hierarchy with a mask works in the inner product <a, b>_W = sum of W a b over all unknowns, W = 1/2 per
+// Neumann face an unknown lies on (the trapezoid weights A is symmetric in), 1 in the interior: the interior kernels of
+// mgx_krylov3d.hip run unchanged and the kernels here add the face unknowns' terms, their block partials behind the interior
+// launch's.  W is a power of two: a weighted term is the unweighted one, rescaled exactly.
+__device__ __forceinline__ double rim_weight(const Rim& R, int x, int y, int z) {
+    const int faces = (x == 0 || x == R.sx - 1) + (y == 0 || y == R.sy - 1) + (z == 0 || z == R.sz - 1);
+    return faces == 1 ? 0.5 : faces == 2 ? 0.25 : 0.125;
+}
+
+// the block's sum of acc into *partial: per thread in list order, wavefront-wide shuffles, the four waves in a fixed order
+__device__ __forceinline__ void rim_block_sum(double acc, double* part, double* __restrict__ partial) {
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) *partial = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// q = A p = -(op's residual of (p, 0)) on the reflected star, partials of <p, q>_W
+template <class real, class Op, int MODE>
+__global__ void __launch_bounds__(RIM_THREADS) rim_apply_dot3d_xs_kernel(const real* __restrict__ p, const real* __restrict__ a,
+                                                                         real* __restrict__ q, Rim R, Op op, double* __restrict__ partial) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    double acc = 0.0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const Star7<real> vs = rim_star<real, true>(p, g, R, x, y, z);
+        Star7<real> as = {};
+        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
+        const real t = -op.template residual<MODE>(vs, (real)0, as);  // negation is exact
+        q[g.row(y, z) + g.pos(x)] = t;
+        acc += rim_weight(R, x, y, z) * ((double)vs.C * (double)t);
+    }
+    __shared__ double part[RIM_THREADS / 64];
+    rim_block_sum(acc, part, partial + blockIdx.x);
+}
+
+// [x += alpha p;] r -= alpha q, partials of <r, r> (unweighted: the stopping rule's norm)
+template <class real, bool X>
+__global__ void __launch_bounds__(RIM_THREADS) rim_cg_update3d_xs_kernel(real* __restrict__ xv, const real* __restrict__ p, real* __restrict__ r,
+                                                                         const real* __restrict__ q, Rim R,
+                                                                         const double* __restrict__ dev_alpha, double* __restrict__ partial) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    const real al = (real)*dev_alpha;
+    double acc = 0.0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const size_t i = g.row(y, z) + g.pos(x);
+        if (X) xv[i] = xv[i] + al * p[i];
+        const real t = r[i] - al * q[i];
+        r[i] = t;
+        acc += (double)t * (double)t;
+    }
+    __shared__ double part[RIM_THREADS / 64];
+    rim_block_sum(acc, part, partial + blockIdx.x);
+}
+
+// partials of <a, b>_W at pab[block] and, with TWO, of <a, c>_W at pac[block]
+template <class real, bool TWO>
+__global__ void __launch_bounds__(RIM_THREADS) rim_dot2_3d_xs_kernel(const real* __restrict__ a, const real* __restrict__ b,
+                                                                     const real* __restrict__ c, Rim R, double* __restrict__ pab,
+                                                                     double* __restrict__ pac) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    double ab = 0.0, ac = 0.0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const size_t i = g.row(y, z) + g.pos(x);
+        const double w = rim_weight(R, x, y, z), av = (double)a[i];
+        ab += w * (av * (double)b[i]);
+        if (TWO) ac += w * (av * (double)c[i]);
+    }
+    __shared__ double part[2][RIM_THREADS / 64];
+    rim_block_sum(ab, part[0], pab + blockIdx.x);
+    if (TWO) rim_block_sum(ac, part[1], pac + blockIdx.x);
+}
+
+// X: x += alpha p (the old p); P_: p = z + beta p (BETA) or p = z
+template <class real, bool X, bool P_, bool BETA>
+__global__ void __launch_bounds__(RIM_THREADS) rim_cg_direction3d_xs_kernel(real* __restrict__ xv, real* __restrict__ p,
+                                                                            const real* __restrict__ zv, Rim R,
+                                                                            const double* __restrict__ dev_alpha,
+                                                                            const double* __restrict__ dev_beta) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    const real al = X ? (real)*dev_alpha : (real)0, be = BETA ? (real)*dev_beta : (real)0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const size_t i = g.row(y, z) + g.pos(x);
+        const real pv = (X || BETA) ? p[i] : (real)0;
+        if (X) xv[i] = xv[i] + al * pv;
+        if (P_) p[i] = BETA ? zv[i] + be * pv : zv[i];
+    }
+}
+
+// the projection a -= mean_W(a): partials of sum_W(a) over the face unknowns ...
+template <class real>
+__global__ void __launch_bounds__(RIM_THREADS) rim_sum3d_xs_kernel(const real* __restrict__ a, Rim R, double* __restrict__ partial) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    double acc = 0.0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) acc += rim_weight(R, x, y, z) * (double)a[g.row(y, z) + g.pos(x)];
+    __shared__ double part[RIM_THREADS / 64];
+    rim_block_sum(acc, part, partial + blockIdx.x);
+}
+
+// ... and of sum(a) over the interior, with the row walk of dot2_3d_xs_kernel (mgx_krylov3d.hip)
+template <class real>
+__global__ void __launch_bounds__(256) sum3d_xs_kernel(const real* __restrict__ a, int sx, int sy, double* __restrict__ partial) {
+    const Geo<XSplit, real> g(sx, sy);
+    const int y = 1 + blockIdx.x * KROWS + threadIdx.y, z = 1 + blockIdx.y;
+    const int H = g.H, P = g.P;
+    double acc = 0.0;
+    if (y < sy - 1) {
+        const size_t row = g.row(y, z);
+        for (int j0 = 0; j0 < P; j0 += KSTEP) {
+            real av[KJ];
+            bool in[KJ];
+#pragma unroll
+            for (int k = 0; k < KJ; k++) {
+                const int j = j0 + k * 64 + threadIdx.x, xx = xs_x(j, H);
+                in[k] = j < P && xx >= 1 && xx <= sx - 2;
+                if (in[k]) av[k] = a[row + j];
+            }
+#pragma unroll
+            for (int k = 0; k < KJ; k++)
+                if (in[k]) acc += (double)av[k];
+        }
+    }
+    __shared__ double part[KROWS];
+    block_sum(acc, part, partial);
+}
+
+// *out = (the sum of partial[0 .. count), in cg_final_kernel's order) / sumw: one block
+__global__ void __launch_bounds__(1024) mean_final_kernel(const double* __restrict__ partial, size_t count, double sumw, double* __restrict__ out) {
+    __shared__ double s[1024];
+    double acc = 0.0;
+    for (size_t i = threadIdx.x; i < count; i += 1024) acc += partial[i];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = s[0] / sumw;
+}
+
+// out[s] = the sum of the interior partials work[s nI .. (s + 1) nI) and the rim partials work[2 nI + s nR .. 2 nI + (s + 1) nR),
+// s = 0, 1: dot2's two sums, one block each, fixed order
+__global__ void __launch_bounds__(1024) rim_final2_kernel(const double* __restrict__ work, size_t nI, size_t nR, double* __restrict__ out) {
+    __shared__ double s[1024];
+    const double *pi = work + (size_t)blockIdx.x * nI, *pr = work + 2 * nI + (size_t)blockIdx.x * nR;
+    double acc = 0.0;
+    for (size_t i = threadIdx.x; i < nI; i += 1024) acc += pi[i];
+    for (size_t i = threadIdx.x; i < nR; i += 1024) acc += pr[i];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = s[0];
+}
+
+// a -= (real)*dev_mean on the interior ...
+template <class real>
+__global__ void __launch_bounds__(256) subtract3d_xs_kernel(real* __restrict__ a, int sx, int sy, const double* __restrict__ dev_mean) {
+    const Geo<XSplit, real> g(sx, sy);
+    const int y = 1 + blockIdx.x * KROWS + threadIdx.y, z = 1 + blockIdx.y;
+    if (y >= sy - 1) return;
+    const int H = g.H, P = g.P;
+    const real m = (real)*dev_mean;
+    const size_t row = g.row(y, z);
+    for (int j = threadIdx.x; j < P; j += 64) {
+        const int xx = xs_x(j, H);
+        if (xx >= 1 && xx <= sx - 2) a[row + j] = a[row + j] - m;
+    }
+}
+
+// ... and on the face unknowns
+template <class real>
+__global__ void __launch_bounds__(RIM_THREADS) rim_subtract3d_xs_kernel(real* __restrict__ a, Rim R, const double* __restrict__ dev_mean) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    const real m = (real)*dev_mean;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const size_t i = g.row(y, z) + g.pos(x);
+        a[i] = a[i] - m;
+    }
+}
+
 // =========================================================================== host side
 #define RIM_BC_CHECK(bc, what) MGX_REQUIRE((bc) >= 0 && (bc) <= 63, MGX_ERR_INVALID, "%s: bc = %d is outside 0 .. 63", what, bc)
 
@@ -268,6 +451,136 @@ static int rim_set3d(mgx_ctx* ctx, real* v, const int n[3], real value, int bc) 
     Rim R;
     MGX_TRY_RET(rim_list<real>(n, bc, "set_rim_bc", R));
     MGX_LAUNCH((rim_set3d_xs_kernel<real>), dim3(rim_blocks(R)), dim3(RIM_THREADS), 0, ctx->compute, v, value, R);
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
+// ---- the solve's vector entries for all unknowns.  Each checks its arguments and the mask before it uses any of them; with bc = 0
+// it is the existing entry.  Work array (krylov_work_elems_bc doubles): the interior launch's partials, count = its blocks, as it
+// lays them out, the rim launch's behind them.
+template <class real>
+static size_t krylov_work_elems_bc(const int n[3]) {
+    Rim R;
+    if (rows_check(n, "krylov_work_elems_bc") || rim_list<real>(n, 63, "krylov_work_elems_bc", R)) return 0;
+    const dim3 g = krylov_grid(n);
+    return 2 * ((size_t)g.x * g.y + rim_blocks(R));  // (a mask's list is at most as long as that of all six faces)
+}
+
+template <class Op, class real>
+static int apply_op_dot3d_bc(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3], real s, double* dev_work,
+                             double* dev_sum, int bc, const char* what) {
+    MGX_REQUIRE(ctx && p && (a || !Op::HAS_A) && q && n && h && dev_work && dev_sum, MGX_ERR_INVALID, "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    if (!bc) return apply_op_dot3d<Op, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, what);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd));
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    MGX_USE(ctx);
+    const Op op(ctx, h, s);
+    MGX_TRY_RET((residual_op3d_launch<Op, true>(ctx, p, (const real*)nullptr, a, q, n, op, dev_work, dev_sum, false)));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    const unsigned nb = rim_blocks(R);
+    Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
+        MGX_LAUNCH((rim_apply_dot3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, p, a, q, R, op,
+                   dev_work + interior);
+    });
+    MGX_LAUNCH_CHECK();
+    return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
+}
+
+template <class real>
+static int cg_update3d_bc(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3], const double* dev_alpha,
+                          double* dev_work, double* dev_sum, int bc) {
+    MGX_REQUIRE(ctx && r && q && (!x || p) && n && dev_alpha && dev_work && dev_sum, MGX_ERR_INVALID, "cg_update_bc: NULL argument");
+    RIM_BC_CHECK(bc, "cg_update_bc");
+    if (!bc) return cg_update3d<real>(ctx, x, p, r, q, n, dev_alpha, dev_work, dev_sum, true);
+    MGX_TRY_RET(rows_check(n, "cg_update_bc"));
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, "cg_update_bc", R));
+    MGX_TRY_RET(cg_update3d<real>(ctx, x, p, r, q, n, dev_alpha, dev_work, dev_sum, false));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    const unsigned nb = rim_blocks(R);
+    if (x) MGX_LAUNCH((rim_cg_update3d_xs_kernel<real, true>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, x, p, r, q, R, dev_alpha,
+                      dev_work + interior);
+    else MGX_LAUNCH((rim_cg_update3d_xs_kernel<real, false>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, x, p, r, q, R, dev_alpha,
+                    dev_work + interior);
+    MGX_LAUNCH_CHECK();
+    return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
+}
+
+template <class real>
+static int dot2_3d_bc(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3], double* dev_work, double* dev_sum, int bc) {
+    MGX_REQUIRE(ctx && a && b && n && dev_work && dev_sum, MGX_ERR_INVALID, "dot2_bc: NULL argument");
+    RIM_BC_CHECK(bc, "dot2_bc");
+    if (!bc) return dot2_3d<real>(ctx, a, b, c, n, dev_work, dev_sum, true);
+    MGX_TRY_RET(rows_check(n, "dot2_bc"));
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, "dot2_bc", R));
+    MGX_TRY_RET(dot2_3d<real>(ctx, a, b, c, n, dev_work, dev_sum, false));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    const unsigned nb = rim_blocks(R);
+    if (!c) {
+        MGX_LAUNCH((rim_dot2_3d_xs_kernel<real, false>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, a, b, c, R, dev_work + interior,
+                   (double*)nullptr);
+        MGX_LAUNCH_CHECK();
+        return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
+    }
+    // the interior launch has put <a, c>'s partials directly behind <a, b>'s: the rim's go behind both, summed by a final of their own
+    MGX_LAUNCH((rim_dot2_3d_xs_kernel<real, true>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, a, b, c, R, dev_work + 2 * interior,
+               dev_work + 2 * interior + nb);
+    MGX_LAUNCH(rim_final2_kernel, dim3(2), dim3(1024), 0, ctx->compute, (const double*)dev_work, interior, (size_t)nb, dev_sum);
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
+template <class real>
+static int cg_direction3d_bc(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3], const double* dev_alpha, const double* dev_beta,
+                             int bc) {
+    MGX_REQUIRE(ctx && p && n && (!x || dev_alpha), MGX_ERR_INVALID, "cg_direction_bc: NULL argument");
+    MGX_REQUIRE(x || z, MGX_ERR_INVALID, "cg_direction_bc: nothing to do (x and z are NULL)");
+    RIM_BC_CHECK(bc, "cg_direction_bc");
+    if (!bc) return cg_direction3d<real>(ctx, x, p, z, n, dev_alpha, dev_beta);
+    MGX_TRY_RET(rows_check(n, "cg_direction_bc"));
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, "cg_direction_bc", R));
+    MGX_TRY_RET(cg_direction3d<real>(ctx, x, p, z, n, dev_alpha, dev_beta));
+#define MGX_DIR(X, P_, B)                                                                                                               \
+    MGX_LAUNCH((rim_cg_direction3d_xs_kernel<real, X, P_, B>), dim3(rim_blocks(R)), dim3(RIM_THREADS), 0, ctx->compute, x, p, z, R, dev_alpha, \
+               dev_beta)
+    if (!z) MGX_DIR(true, false, false);
+    else if (x && dev_beta) MGX_DIR(true, true, true);
+    else if (x) MGX_DIR(true, true, false);
+    else if (dev_beta) MGX_DIR(false, true, true);
+    else MGX_DIR(false, true, false);
+#undef MGX_DIR
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
+// *dev_mean = sum_W(a) / sum(W), a -= (real)*dev_mean at every unknown; sum(W) = the product over the axes of the axis's interior
+// points plus half a point per Neumann end
+template <class real>
+static int project3d_bc(mgx_ctx* ctx, real* a, const int n[3], double* dev_work, double* dev_mean, int bc) {
+    MGX_REQUIRE(ctx && a && n && dev_work && dev_mean, MGX_ERR_INVALID, "project_bc: NULL argument");
+    RIM_BC_CHECK(bc, "project_bc");
+    MGX_TRY_RET(rows_check(n, "project_bc"));
+    Rim R = {};
+    if (bc) MGX_TRY_RET(rim_list<real>(n, bc, "project_bc", R));
+    MGX_USE(ctx);
+    double sumw = 1.0;
+    for (int d = 0; d < 3; d++) sumw *= (double)(n[d] - 2) + 0.5 * (((bc >> (2 * d)) & 1) + ((bc >> (2 * d + 1)) & 1));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    const unsigned nb = bc ? rim_blocks(R) : 0;
+    MGX_LAUNCH((sum3d_xs_kernel<real>), g, krylov_block(), 0, ctx->compute, (const real*)a, n[0], n[1], dev_work);
+    if (bc) MGX_LAUNCH((rim_sum3d_xs_kernel<real>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, (const real*)a, R, dev_work + interior);
+    MGX_LAUNCH(mean_final_kernel, dim3(1), dim3(1024), 0, ctx->compute, (const double*)dev_work, interior + nb, sumw, dev_mean);
+    MGX_LAUNCH((subtract3d_xs_kernel<real>), g, krylov_block(), 0, ctx->compute, a, n[0], n[1], (const double*)dev_mean);
+    if (bc) MGX_LAUNCH((rim_subtract3d_xs_kernel<real>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, a, R, (const double*)dev_mean);
     MGX_LAUNCH_CHECK();
     return MGX_OK;
 }
@@ -356,3 +669,32 @@ static int rim_set3d(mgx_ctx* ctx, real* v, const int n[3], real value, int bc) 
 
 MGX_RIM3D_API(f32, float)
 MGX_RIM3D_API(f64, double)
+
+#define MGX_RIM3D_KRYLOV_API(SFX, real)                                                                                                      \
+    extern "C" size_t mgx3dxs_krylov_work_elems_bc_##SFX(const int n[3]) { return mgx::krylov_work_elems_bc<real>(n); }                      \
+    extern "C" int mgx3dxs_laplace_dot_shift_bc_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3], const real h[3], real s,          \
+                                                      double* dev_work, double* dev_sum, int bc) {                                           \
+        return mgx::apply_op_dot3d_bc<mgx::ShiftOp<real>, real>(ctx, p, nullptr, q, n, h, s, dev_work, dev_sum, bc, "laplace_dot_shift_bc"); \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_apply_coef_dot_bc_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3],      \
+                                                   real s, double* dev_work, double* dev_sum, int bc) {                                      \
+        return mgx::apply_op_dot3d_bc<mgx::CoefOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, "apply_coef_dot_bc");           \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_cg_update_bc_##SFX(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3],                  \
+                                              const double* dev_alpha, double* dev_work, double* dev_sum, int bc) {                          \
+        return mgx::cg_update3d_bc<real>(ctx, x, p, r, q, n, dev_alpha, dev_work, dev_sum, bc);                                              \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_dot2_bc_##SFX(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3], double* dev_work,         \
+                                         double* dev_sum, int bc) {                                                                          \
+        return mgx::dot2_3d_bc<real>(ctx, a, b, c, n, dev_work, dev_sum, bc);                                                                \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_cg_direction_bc_##SFX(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3], const double* dev_alpha,      \
+                                                 const double* dev_beta, int bc) {                                                           \
+        return mgx::cg_direction3d_bc<real>(ctx, x, p, z, n, dev_alpha, dev_beta, bc);                                                       \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_project_bc_##SFX(mgx_ctx* ctx, real* a, const int n[3], double* dev_work, double* dev_mean, int bc) {              \
+        return mgx::project3d_bc<real>(ctx, a, n, dev_work, dev_mean, bc);                                                                   \
+    }
+
+MGX_RIM3D_KRYLOV_API(f32, float)
+MGX_RIM3D_KRYLOV_API(f64, double)

@@ -654,11 +654,11 @@ class _Ops3D(_Ops):
         fn.restype = C.c_size_t
         return self._work_alloc(ctx, fn(_ip(n)))
 
-    def _krylov(self, ctx, n, arrays, scalars, call, dtype, nsum):
+    def _krylov(self, ctx, n, arrays, scalars, call, dtype, nsum, work_alloc=None):
         """upload arrays (x-split) and the device doubles `scalars`, run call(work, sums, *scalar ptrs, *array ptrs), return
         (arrays as stored, padded rows, sums)"""
         assert self.xsplit, "the Krylov kernels exist for the x-split layout only"
-        work, welems = self._krylov_work(ctx, n, dtype)
+        work, welems = (work_alloc or self._krylov_work)(ctx, n, dtype)
         dev = [ctx.to_device(np.array(scalars + [0.0] * nsum, np.float64))]
         ptrs = [ctx.to_device(a) if a is not None else None for a in arrays]
         try:
@@ -708,6 +708,70 @@ class _Ops3D(_Ops):
             return fn(ctx._h, xp, pp, zp, _ip(n), a if alpha is not None else None, b if beta is not None else None)
         (xo, po, _), _ = self._krylov(ctx, n, [x, p, z], [float(alpha or 0.0), float(beta or 0.0)], call, dtype, 0)
         return xo, po
+
+    # ---- the same over ALL unknowns of a grid with the face mask bc (mgx3dxs_*_bc): the dots weighted by 1/2 per Neumann face an
+    # unknown lies on, cg_update's <r, r> unweighted; arrays in the reference layout
+    def _krylov_work_bc(self, ctx, n, dtype):
+        fn = getattr(lib, "mgx3dxs_krylov_work_elems_bc_" + _ct(dtype)[0])
+        fn.restype = C.c_size_t
+        return self._work_alloc(ctx, fn(_ip(n)))
+
+    def _krylov_bc(self, ctx, n, arrays, scalars, call, dtype, nsum):
+        """_krylov with the larger work array and arrays given and returned in the reference layout"""
+        packed = [xs_pack(np.ascontiguousarray(a, dtype)) if a is not None else None for a in arrays]
+        outs, sums = self._krylov(ctx, n, packed, scalars, call, dtype, nsum, self._krylov_work_bc)
+        return [xs_unpack(o, n[0]) if o is not None else None for o in outs], sums
+
+    def laplace_dot_shift_bc(self, ctx, p, n, rng, s, bc, q=None, dtype=None):
+        """q = A p at every unknown (A = Laplacian - s) and <p, q>_W: returns (q, pq); q: the array written into (default zeros)"""
+        dtype = dtype or p.dtype
+        fn, ct = self._fn("laplace_dot_shift_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        q = np.zeros(_shape(n), dtype) if q is None else q
+        (_, qo), sums = self._krylov_bc(ctx, n, [p, q], [], lambda w, s0, a, b: fn(ctx._h, a, b, _ip(n), h, ct(s), w, s0, C.c_int(bc)), dtype, 1)
+        return qo, float(sums[0])
+
+    def apply_coef_dot_bc(self, ctx, p, a, n, rng, s, bc, q=None, dtype=None):
+        """q = A p at every unknown (A = div(a grad .) - s) and <p, q>_W: returns (q, pq)"""
+        dtype = dtype or p.dtype
+        fn, ct = self._fn("apply_coef_dot_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        q = np.zeros(_shape(n), dtype) if q is None else q
+        (_, _, qo), sums = self._krylov_bc(ctx, n, [p, a, q], [],
+                                           lambda w, s0, x, c, b: fn(ctx._h, x, c, b, _ip(n), h, ct(s), w, s0, C.c_int(bc)), dtype, 1)
+        return qo, float(sums[0])
+
+    def cg_update_bc(self, ctx, x, p, r, q, n, alpha, bc, dtype=None):
+        """x += (real)alpha p (x None: skipped); r -= (real)alpha q at every unknown.  Returns (x, r, <r, r> unweighted)."""
+        dtype = dtype or r.dtype
+        fn, _ = self._fn("cg_update_bc", dtype)
+        (xo, _, ro, _), sums = self._krylov_bc(ctx, n, [x, p, r, q], [float(alpha)],
+                                               lambda w, a, s0, xp, pp, rp, qp: fn(ctx._h, xp, pp, rp, qp, _ip(n), a, w, s0, C.c_int(bc)), dtype, 1)
+        return xo, ro, float(sums[0])
+
+    def dot2_bc(self, ctx, a, b, c, n, bc, dtype=None):
+        """(<a, b>_W, <a, c>_W) over all unknowns (c None: <a, c>_W is None)"""
+        dtype = dtype or a.dtype
+        fn, _ = self._fn("dot2_bc", dtype)
+        _, sums = self._krylov_bc(ctx, n, [a, b, c], [], lambda w, s0, s1, ap, bp, cp: fn(ctx._h, ap, bp, cp, _ip(n), w, s0, C.c_int(bc)), dtype, 2)
+        return float(sums[0]), (float(sums[1]) if c is not None else None)
+
+    def cg_direction_bc(self, ctx, x, p, z, n, bc, alpha=None, beta=None, dtype=None):
+        """cg_direction at every unknown.  Returns (x, p)."""
+        dtype = dtype or p.dtype
+        fn, _ = self._fn("cg_direction_bc", dtype)
+
+        def call(w, a, b, xp, pp, zp):
+            return fn(ctx._h, xp, pp, zp, _ip(n), a if alpha is not None else None, b if beta is not None else None, C.c_int(bc))
+        (xo, po, _), _ = self._krylov_bc(ctx, n, [x, p, z], [float(alpha or 0.0), float(beta or 0.0)], call, dtype, 0)
+        return xo, po
+
+    def project_bc(self, ctx, a, n, bc, dtype=None):
+        """a -= (real)mean with mean = sum_W(a) / sum(W) over all unknowns.  Returns (a, mean)."""
+        dtype = dtype or a.dtype
+        fn, _ = self._fn("project_bc", dtype)
+        (ao,), sums = self._krylov_bc(ctx, n, [a], [], lambda w, s0, ap: fn(ctx._h, ap, _ip(n), w, s0, C.c_int(bc)), dtype, 1)
+        return ao, float(sums[0])
 
     # ---- vector kernels of the mixed-precision solve (fp64 only): fp64 arrays and fp32 arrays (r32, z32) packed (x-split), each
     # in its own precision's geometry; s / inv_s are applied as given (the solver passes powers of two)
@@ -895,7 +959,8 @@ def _grid3_struct(ct):
         _fields_ = [("grids3D", C.POINTER(C.POINTER(Grid3D))), ("numGrids", C.c_int), ("maxGrids", C.c_int),
                     ("ctx", C.c_void_p), ("residual_mode", C.c_int), ("fuse", C.c_int), ("layout", C.c_int),
                     ("smoother", C.c_int), ("omega", ct), ("use_graph", C.c_int), ("capturing", C.c_int),
-                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 32), ("f_rim_zero", C.c_ubyte * 32),
+                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 31), ("pcg_fproj", C.c_void_p),
+                    ("f_rim_zero", C.c_ubyte * 32),
                     ("v_rim_zero", C.c_ubyte * 32), ("e_rim_valid", C.c_ubyte * 32), ("pcg_x", C.c_void_p),
                     ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
                     ("pcg_work", C.c_void_p), ("pcg_graph_exec", C.c_void_p), ("bc", C.c_int), ("bc_reserved", C.c_int),
@@ -929,6 +994,18 @@ def _grid1_struct(ct):
         _fields_ = [("grids1D", C.POINTER(C.POINTER(Grid1D))), ("numGrids", C.c_int), ("maxGrids", C.c_int)]
 
     return Grid1D, MultiGrid1D
+
+
+def krylov_mode(krylov):
+    """the C value of a `krylov` argument: False / 0 -> 0 (plain cycling), True / 1 -> 1 (flexible CG over the interior),
+    "weighted" / 2 -> 2 (flexible CG in the weighted inner product over all unknowns, MG_KRYLOV_WEIGHTED)"""
+    if isinstance(krylov, str):
+        if krylov != "weighted":
+            raise ValueError("krylov must be False, True, 2 or 'weighted', not %r" % (krylov,))
+        return 2
+    if not isinstance(krylov, (bool, np.bool_)) and krylov == 2:
+        return 2
+    return int(bool(krylov))
 
 
 class _MGBase:
@@ -1038,8 +1115,10 @@ class MultiGrid3D(_MGBase):
         """faces: six truthy values, one per face in the order x-low, x-high, y-low, y-high, z-low, z-high (None: all False).  A
         true one makes that face a wall with du/dn = 0 on every level: its points, but for those on a Dirichlet face too, become
         unknowns, and v there is part of the solution instead of data.  Needs layout="xsplit", the red-black smoother,
-        residual_mode=CORRECT and coarsening="full"; PCG and BackwardEuler then need krylov=False, PCG(precond="f32") is not
-        available, and all six faces need a shift > 0.  A prescribed flux g (du/dn = g, outward) goes into the right-hand side:
+        residual_mode=CORRECT and coarsening="full"; PCG and BackwardEuler then take krylov=False or krylov="weighted" (CG in the
+        inner product weighted by 1/2 per wall an unknown lies on; krylov=True is refused), PCG(precond="f32") is not available,
+        and all six faces need a shift > 0 -- but for PCG(krylov="weighted"), which solves that singular system in the projected
+        sense.  A prescribed flux g (du/dn = g, outward) goes into the right-hand side:
         f -= 2 g a / h at the face.  All False: the hierarchy is what it was without walls."""
         faces = [0] * 6 if faces is None else [int(bool(x)) for x in faces]
         if len(faces) != 6:
@@ -1088,7 +1167,7 @@ class MultiGrid3D(_MGBase):
         in time), source = q (reference layout) or None.  Every step is one PCG(v1, v2, tol, maxit, krylov) solve of
         (Laplacian - s) u' = -s u - q / kappa with s = 1 / (kappa dt), which stays set as the hierarchy's shift afterwards.
         Returns (iterations of all steps, worst true relative residual of a step, converged); it stops at the first step
-        that does not converge."""
+        that does not converge.  krylov as in PCG: with walls False or "weighted"."""
         src = None
         if source is not None:
             source = np.ascontiguousarray(source, self.dtype)
@@ -1098,7 +1177,7 @@ class MultiGrid3D(_MGBase):
         worst = C.c_double()
         try:
             self._call("BackwardEuler", C.c_int(int(nsteps)), C.c_double(dt), C.c_double(kappa), src, C.c_int(v1), C.c_int(v2),
-                       C.c_double(tol), C.c_int(maxit), C.c_int(int(bool(krylov))), C.byref(it), C.byref(worst), C.byref(conv))
+                       C.c_double(tol), C.c_int(maxit), C.c_int(krylov_mode(krylov)), C.byref(it), C.byref(worst), C.byref(conv))
         finally:
             if src is not None:
                 self.ctx.free(src)
@@ -1179,7 +1258,13 @@ class MultiGrid3D(_MGBase):
         precond="f32" (mgMultiGrid3D_f64_PCG_mixed) keeps the iterate, the residual and the stopping test in fp64 and runs
         the V-cycle in fp32 on a twin hierarchy it builds on first use -- fp64 tolerances in close to fp32 time, for the
         twin's extra device memory (four fp32 arrays per level).  With krylov=False that is defect correction, whose
-        history holds true residuals."""
+        history holds true residuals.
+
+        krylov="weighted" (or 2): flexible CG in the inner product that weights an unknown by 1/2 per wall (set_neumann) it lies
+        on, in which the operator with walls is symmetric -- the Krylov solver of a hierarchy with walls, where krylov=True is
+        refused; without walls it is krylov=True bit for bit.  With all six faces walls and shift 0 it solves the singular system
+        in the projected sense: A v = f - mean_W(f), v keeps the weighted mean of the guess, rel_res is against the projected
+        right-hand side and pcg_removed_mean is mean_W(f)."""
         if precond not in ("f64", "f32"):
             raise ValueError("precond must be 'f64' or 'f32', not %r" % (precond,))
         if precond == "f32" and self.dtype != np.float64:
@@ -1187,10 +1272,19 @@ class MultiGrid3D(_MGBase):
         it, conv = C.c_int(), C.c_int()
         rel = C.c_double()
         hist = np.zeros(int(maxit), np.float64)
+        mode = krylov_mode(krylov)
         self._call("PCG_mixed" if precond == "f32" else "PCG", C.c_int(v1), C.c_int(v2), C.c_double(tol), C.c_int(maxit),
-                   C.c_int(int(bool(krylov))), C.byref(it), C.byref(rel), C.byref(conv), hist.ctypes.data_as(C.c_void_p),
+                   C.c_int(min(mode, 1) if precond == "f32" else mode), C.byref(it), C.byref(rel), C.byref(conv), hist.ctypes.data_as(C.c_void_p),
                    C.c_int(len(hist)))
         return int(it.value), float(rel.value), bool(conv.value), hist[:it.value].copy()
+
+    @property
+    def pcg_removed_mean(self):
+        """the weighted mean the last PCG removed from the right-hand side: mean_W(f) after PCG(krylov="weighted") in a closed box
+        without a shift, 0 after every other solve"""
+        out = C.c_double()
+        self._call("pcg_removed_mean", C.byref(out))
+        return float(out.value)
 
 
 class MultiGrid2D(_MGBase):
@@ -1522,7 +1616,8 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
     coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call.
     shift = s > 0: the solve of (Laplacian - s) u = rhs (MultiGrid3D(shift=s)), on a hierarchy built here likewise.
     coefficient = a > 0 at every point: the solve of div(a grad u) - shift u = rhs (MultiGrid3D(coefficient=a)), likewise.
-    neumann = six truthy values: the faces with du/dn = 0 (MultiGrid3D(neumann=...)), likewise; needs krylov=False."""
+    neumann = six truthy values: the faces with du/dn = 0 (MultiGrid3D(neumann=...)), likewise; needs krylov=False or
+    krylov="weighted" (MultiGrid3D.PCG)."""
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
     if precond not in ("f64", "f32"):
@@ -1550,7 +1645,8 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
     rel = C.c_double()
     check(getattr(lib, "mg3d_solve_pcg_" + s)(ctx._h, grid.ctypes.data_as(C.c_void_p), r, _ip(n), _rp(rng, ct), C.c_int(nlevels),
                                               C.c_int(v1), C.c_int(v2), C.c_double(tol), C.c_int(maxit),
-                                              C.c_int(int(bool(krylov))), C.byref(it), C.byref(rel), C.byref(conv)))
+                                              C.c_int(min(krylov_mode(krylov), 1) if precond == "f32" else krylov_mode(krylov)), C.byref(it),
+                                              C.byref(rel), C.byref(conv)))
     return grid, int(it.value), float(rel.value), bool(conv.value)
 
 

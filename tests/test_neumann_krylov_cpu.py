@@ -1,0 +1,153 @@
+"""Flexible CG on hierarchies with Neumann faces without a GPU: the library exports the vector entries for all unknowns and rejects
+NULL arguments and masks outside 0 .. 63 before it uses an argument, the struct mirror keeps the library's size; the restated
+solver (tests/neumann_krylov_restated.py) takes the iteration counts of DESIGN.md 16's table, converges where plain cycling does
+not, and solves the closed box without a shift in the projected sense, to second order."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+import coef_restated as CO
+import neumann_krylov_restated as KR
+import neumann_restated as NR
+import oracle as O
+import pde_multigrid_amd as P
+from neumann_krylov_restated import CASES, EXACT_17, TOL, UNIT
+from pde_multigrid_amd.multigrid import _grid3_struct, krylov_mode
+
+ENTRIES = ("laplace_dot_shift_bc", "apply_coef_dot_bc", "cg_update_bc", "dot2_bc", "cg_direction_bc", "project_bc")
+
+
+# ------------------------------------------------------------------------------------------ the library's new surface
+@pytest.mark.parametrize("sfx", ["f32", "f64"])
+def test_new_symbols_are_exported_and_reject_null_and_bad_masks(sfx):
+    for k in ENTRIES + ("krylov_work_elems_bc",):
+        assert hasattr(P.lib, "mgx3dxs_%s_%s" % (k, sfx)), k
+    assert hasattr(P.lib, "mgMultiGrid3D_%s_pcg_removed_mean" % sfx)
+    ct = C.c_float if sfx == "f32" else C.c_double
+    L, I = P.lib, P.MGX_ERR_INVALID
+    fn = lambda k: getattr(L, "mgx3dxs_%s_%s" % (k, sfx))
+    N = None
+    null_calls = {"laplace_dot_shift_bc": (N, N, N, N, N, ct(1), N, N, 1), "apply_coef_dot_bc": (N, N, N, N, N, N, ct(1), N, N, 1),
+                  "cg_update_bc": (N, N, N, N, N, N, N, N, N, 1), "dot2_bc": (N, N, N, N, N, N, N, 1),
+                  "cg_direction_bc": (N, N, N, N, N, N, N, 1), "project_bc": (N, N, N, N, N, 1)}
+    for k in ENTRIES:
+        assert fn(k)(*null_calls[k]) == I, k
+        assert b"NULL" in L.mgx_last_error(), k
+    # bc = 64 (and -1): the mask is looked at before any argument is used, so host buffers stand in for the context and the arrays
+    buf = (C.c_double * 64)()
+    n, h = (C.c_int * 3)(5, 5, 5), (ct * 3)(0.25, 0.25, 0.25)
+    for bc in (64, -1):
+        bad = {"laplace_dot_shift_bc": (buf, buf, buf, n, h, ct(1), buf, buf, bc), "apply_coef_dot_bc": (buf, buf, buf, buf, n, h, ct(1), buf, buf, bc),
+               "cg_update_bc": (buf, buf, buf, buf, buf, n, buf, buf, buf, bc), "dot2_bc": (buf, buf, buf, buf, n, buf, buf, bc),
+               "cg_direction_bc": (buf, buf, buf, buf, n, buf, buf, bc), "project_bc": (buf, buf, n, buf, buf, bc)}
+        for k in ENTRIES:
+            assert fn(k)(*bad[k]) == I, (k, bc)
+            assert b"bc" in L.mgx_last_error(), (k, L.mgx_last_error())
+    assert getattr(L, "mgMultiGrid3D_%s_pcg_removed_mean" % sfx)(None, None) == I
+
+
+@pytest.mark.parametrize("sfx", ["f32", "f64"])
+def test_work_array_count(sfx):
+    """two sums, each the interior partials plus the rim partials of all six faces (at most 4096 blocks of 256 list entries); the
+    interior-only count keeps its value"""
+    old, new = (getattr(P.lib, "mgx3dxs_krylov_work_elems%s_%s" % (k, sfx)) for k in ("", "_bc"))
+    old.restype = new.restype = C.c_size_t
+    for n3 in [(17, 17, 17), (21, 13, 29), (513, 5, 5), (3, 3, 3), (257, 257, 257)]:
+        n = (C.c_int * 3)(*n3)
+        interior = -(-(n3[1] - 2) // 4) * (n3[2] - 2)
+        assert old(n) == 2 * interior
+        P_ = P.xs_geometry(n3[0], 4 if sfx == "f32" else 8)[1]
+        listed = 2 * P_ * n3[1] + 2 * P_ * (n3[2] - 2) + 2 * (n3[1] - 2) * (n3[2] - 2)
+        assert new(n) == 2 * (interior + min(4096, -(-listed // 256))), n3
+    assert new((C.c_int * 3)(16, 9, 9)) == 0 and new(None) == 0
+
+
+@pytest.mark.parametrize("sfx,ct", [("f32", C.c_float), ("f64", C.c_double)])
+def test_hierarchy_mirror_keeps_its_size(sfx, ct):
+    fn = getattr(P.lib, "mgMultiGrid3D_%s_sizeof" % sfx)
+    fn.restype = C.c_size_t
+    M = _grid3_struct(ct)[1]
+    assert C.sizeof(M) == fn()
+    # the fifth scratch array takes the last eight bytes of the unused graph_key: no member moved
+    assert M.pcg_fproj.offset == M.graph_key.offset + 31 * 8 and M.f_rim_zero.offset == M.graph_key.offset + 32 * 8
+    assert M.bc_reserved.offset == M.bc.offset + 4 and M.graph_rec.offset == M.bc.offset + 8
+    assert M._fields_[-1][0] == "shift"
+
+
+def test_krylov_argument_mapping():
+    assert [krylov_mode(k) for k in (False, True, 0, 1, 2, "weighted", np.bool_(True), 3)] == [0, 1, 0, 1, 2, 2, 1, 1]
+    with pytest.raises(ValueError):
+        krylov_mode("yes")
+
+
+# ------------------------------------------------------------------------------------------ the restated solver
+def test_sum_of_weights_is_separable():
+    for n3, bc in [((5, 7, 9), 63), ((5, 7, 9), 37), ((17, 3, 5), 2), ((3, 3, 3), 0)]:
+        assert KR.sum_weights(n3, bc) == float(NR.weights(n3, bc).sum())
+
+
+def test_operator_is_symmetric_in_the_weighted_product_only():
+    n3, bc = (9, 9, 9), 37
+    g = np.random.default_rng(3)
+    unk = NR.unknown_mask(n3, bc)
+    p, w = (np.where(unk, g.uniform(-1, 1, O.shape(n3)), 0.0) for _ in range(2))
+    a = CO.smooth_coefficient(n3)
+    W = NR.weights(n3, bc)
+    Ap, Aw = NR.apply_A(n3, UNIT, p, a, 0.5, bc, np.float64), NR.apply_A(n3, UNIT, w, a, 0.5, bc, np.float64)
+    scale = math.fsum(np.abs(W * w * Ap).ravel())
+    assert abs(KR.wdot(W, w, Ap) - KR.wdot(W, p, Aw)) < 1e-13 * scale
+    assert abs(math.fsum((w * Ap).ravel()) - math.fsum((p * Aw).ravel())) > 1e-6 * scale
+
+
+@pytest.mark.parametrize("case", EXACT_17)
+def test_iteration_counts_at_17(case):
+    """the counts of the table's 17^3 row for mask 62, (63, 100, jump 100), (37, 0, smooth) and the closed box without a shift with
+    no coefficient and with the smooth one: 7, 9, 7, 7, 8.  The rows of the closed box without a shift start from the zero guess (KR.table_start)."""
+    x, k, hist, conv, rel, _ = KR.solved(case, 17)
+    print("case %r: %d iterations, history end %s, true residual %.3e" % (CASES[case][:3], k, hist[-3:], rel))
+    assert conv and rel < TOL and k == CASES[case][3]
+
+
+def test_jump_1000_in_the_closed_box_converges_where_plain_cycling_does_not():
+    bc, s, jump = CASES[3][:3]
+    x, k, hist, conv, rel, _ = KR.solved(3, 17)
+    print("weighted CG: %d iterations, true residual %.3e" % (k, rel))
+    assert conv and rel < TOL and k <= 40
+    n3 = (17, 17, 17)
+    H = NR.Hierarchy(n3, UNIT, CO.jump_coefficient(n3, jump), s, bc)
+    H.v[0], H.f[0] = KR.start(n3)
+    cycles, rel_plain, conv_plain = H.cycle_to(2, 2, TOL, 60)
+    print("plain cycling: %d cycles, residual %.3e" % (cycles, rel_plain))
+    assert not conv_plain and cycles == 60
+
+
+@pytest.mark.parametrize("case", [6, 7, 8])
+def test_singular_solve_keeps_the_mean_of_the_guess_and_reports_the_removed_mean(case):
+    """from the random guess, whose weighted mean is not zero"""
+    n3 = (17, 17, 17)
+    x, k, hist, conv, rel, removed = KR.solved(case, 17, random_guess=True)
+    v0, f = KR.start(n3)
+    W = NR.weights(n3, 63)
+    assert conv and rel < TOL
+    assert abs(KR.wmean(W, v0)) > 1e-3
+    assert abs(KR.wmean(W, x) - KR.wmean(W, v0)) <= 1e-12 * np.abs(x).max()
+    assert removed == math.fsum((W * f).ravel()) / KR.sum_weights(n3, 63)
+
+
+def test_singular_solve_is_second_order():
+    """u = cos(pi x) cos(pi y) cos(pi z) in the closed unit cube, f = -3 pi^2 u, from zero: after removing the weighted means the
+    maximum error falls by 4 per halving of h, both ratios in [3.5, 4.5]"""
+    errs = []
+    for size in (9, 17, 33):
+        n3 = (size,) * 3
+        xx, yy, zz = CO._nodes(n3)
+        u = np.cos(np.pi * xx) * np.cos(np.pi * yy) * np.cos(np.pi * zz)
+        x, k, hist, conv, rel, removed = KR.wfcg(n3, UNIT, None, 0.0, 63, np.zeros(O.shape(n3)), -3 * np.pi ** 2 * u)
+        assert conv
+        W = NR.weights(n3, 63)
+        errs.append(np.abs((x - KR.wmean(W, x)) - (u - KR.wmean(W, u))).max())
+    ratios = [errs[0] / errs[1], errs[1] / errs[2]]
+    print("max errors %s, ratios %s" % (errs, ratios))
+    assert all(3.5 <= r <= 4.5 for r in ratios), ratios
