@@ -113,6 +113,11 @@ int mgx_ctx_device(const mgx_ctx* ctx, int* device);
  * ".pzchunk" coarse planes per run (0 automatic), ".tyw" waves per workgroup, ".cr" coarse rows per lane, ".rows" fine rows
  * per wave of the pipelined kernel (0 = by level size, 2, 4), ".xcd" 0/1/2 XCD-aware block order, ".rcp" 0/1: with
  * power-of-two squared spacings the residual multiplies by the exact reciprocals instead of dividing (same bits);
+ * "relax3d.zchunk" and "residual_restrict3d.pzchunk" also reach the operators of the shifted, the variable-coefficient and the
+ * Neumann hierarchies: a value > 0 is the planes per run of their colour pass (mgx3dxs_relax_shift / _coef, their _from_zero and
+ * _bc forms; any value >= 1, the same bits for each; the run length launched is the last number of mgx_ctx_last_relax_kernel's
+ * name, relax_coef3d_xs_kernel<double,4,4,4> = runs of 4 planes), respectively the coarse planes per run of
+ * mgx3dxs_residual_restrict_shift and mgx3dxs_residual_restrict_axes (any value >= 1, the same bits); 0 = by the size of the launch.
  * "relax3d.corr_v2" 0/1: fp32 on wide levels, the correcting red pass with two pairs per lane like the plain passes;
  * "relax3d.zero_sweep" 0/1: relax_from_zero on the pipelined levels runs its first red and black pass as one launch;
  * "relax3d.resident" 0 / 1 / 2 and "relax3d.resident_min" (sweeps per call, default 3): all colour passes of a Relax call on a level

@@ -124,7 +124,9 @@ static int residual_restrict_axes3d(mgx_ctx* ctx, const real* v, const real* f, 
             const int gy = ceil_div(cn[1] - 2, TYW * CR);
             // runs of 16 coarse planes, halved while the launch has fewer than four workgroups per CU
             int pzchunk = 16;
-            while (pzchunk > 2 && (long long)gx * gy * ceil_div(cn[2] - 2, pzchunk) < 4LL * ctx->num_cus) pzchunk >>= 1;
+            if (ctx->rr_pzchunk > 0) pzchunk = ctx->rr_pzchunk;  // "residual_restrict3d.pzchunk": the same bits for every run length
+            else
+                while (pzchunk > 2 && (long long)gx * gy * ceil_div(cn[2] - 2, pzchunk) < 4LL * ctx->num_cus) pzchunk >>= 1;
             const int gz = ceil_div(cn[2] - 2, pzchunk);
             with_value<0, 1, 2, 3>(s.mode, [&](auto md) __attribute__((always_inline)) {
                 MGX_LAUNCH((residual_restrict_axes3d_xs_kernel<real, M, decltype(md)::value, CR, TYW>), dim3((unsigned)(gx * gy * gz)),

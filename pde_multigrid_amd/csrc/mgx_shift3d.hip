@@ -90,7 +90,9 @@ static int residual_restrict_shift3d(mgx_ctx* ctx, const real* v, const real* f,
             const int gx = (M & 1) ? ceil_div(cn[0] - 2, 63) : ceil_div((n[0] - 1) / 2, 64);
             const int gy = ceil_div(cn[1] - 2, TYW * CR);
             int pzchunk = 16;  // runs of 16 coarse planes, halved while the launch has fewer than four workgroups per CU
-            while (pzchunk > 2 && (long long)gx * gy * ceil_div(cn[2] - 2, pzchunk) < 4LL * ctx->num_cus) pzchunk >>= 1;
+            if (ctx->rr_pzchunk > 0) pzchunk = ctx->rr_pzchunk;  // "residual_restrict3d.pzchunk": the same bits for every run length
+            else
+                while (pzchunk > 2 && (long long)gx * gy * ceil_div(cn[2] - 2, pzchunk) < 4LL * ctx->num_cus) pzchunk >>= 1;
             const int gz = ceil_div(cn[2] - 2, pzchunk);
             with_value<1, 3>(sc.mode, [&](auto md) __attribute__((always_inline)) {
                 MGX_LAUNCH((residual_restrict_axes3d_xs_kernel<real, M, decltype(md)::value, CR, TYW, true>), dim3((unsigned)(gx * gy * gz)),

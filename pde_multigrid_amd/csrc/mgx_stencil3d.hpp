@@ -257,7 +257,8 @@ __global__ void __launch_bounds__(256) relax_op_zero3d_xs_kernel(real* __restric
 // `what` is the entry point's name in its error texts; `a` is NULL for an operator without a coefficient array.
 
 // one colour pass over the planes 1 .. sz-2: relax3d_xs_kernel's launch geometry (four waves of Op::rows() rows, fewer on small
-// levels; runs of four planes, halved while the launch has fewer than eight workgroups per CU)
+// levels; runs of four planes, halved while the launch has fewer than eight workgroups per CU, or runs of "relax3d.zchunk" planes
+// where that is set: the same bits for every run length).  The run length launched is the last number of last_relax_kernel()
 template <class Op, class real>
 static void relax_op3d_pass(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const Op& op, int colour) {
     const int sx = n[0], sy = n[1], zbeg = 1, zend = n[2] - 1;
@@ -266,13 +267,15 @@ static void relax_op3d_pass(mgx_ctx* ctx, real* v, const real* f, const real* a,
     while (ty > 1 && rows * ty > sy - 2) ty >>= 1;
     const int gx = ceil_div((sx + 1) / 2 - 1, 64), gy = ceil_div(sy - 2, ty * rows);
     int zchunk = 4;
-    while (zchunk > 1 && (long long)gx * gy * ceil_div(zend - zbeg, zchunk) < 8LL * ctx->num_cus) zchunk >>= 1;
+    if (ctx->relax_zchunk > 0) zchunk = ctx->relax_zchunk;
+    else
+        while (zchunk > 1 && (long long)gx * gy * ceil_div(zend - zbeg, zchunk) < 8LL * ctx->num_cus) zchunk >>= 1;
     const unsigned nblocks = (unsigned)gx * gy * ceil_div(zend - zbeg, zchunk);
     const int xcd = ctx->relax_xcd == 1 ? 1 : 0;
     with_value<1, 2, 4>(ty, [&](auto t) __attribute__((always_inline)) {
         with_value<1, 2, 4>(rows, [&](auto r) __attribute__((always_inline)) {
             constexpr int TYW = decltype(t)::value, RR = decltype(r)::value;
-            note_relax_kernel<real>(ctx, Op::relax_kernel, TYW, RR, 0);
+            note_relax_kernel<real>(ctx, Op::relax_kernel, TYW, RR, zchunk);
             MGX_LAUNCH((relax_op3d_xs_kernel<real, Op, TYW, RR>), dim3(nblocks), dim3(64, TYW, 1), 0, ctx->compute, (const real*)v, v, f, a, sx, sy,
                        zbeg, zend, op, colour, zchunk, gx, gy, xcd);
         });
