@@ -43,13 +43,63 @@ inline int check_rr_args(mgx_ctx* ctx, bool nonnull, const int n[3], const int c
 // What one unit defines and others call.  The templates are instantiated explicitly, for float and double, in the unit named
 // above them.
 
+// the largest extent of a level that the one-workgroup kernels of mgx_small3d.hip keep in LDS (the `takes` predicates of the
+// other units leave such levels to them)
+constexpr int SMALL_MAX = 17;
+
 // ---- mgx_kernels3d.hip
-bool relax3d_lds_shape_known(int shape);
 // the colour-pass smoother, x-split layout (mgx_sweep3d.hip falls back to it)
 template <class real>
 int relax3d_xs_colour_passes(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int ncycles);
 template <class real>
 int relax3d_xs_from_zero(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], int ncycles, int rim_is_zero);
+
+// ---- mgx_pipe3d.hip: the pipelined smoothers (relax3d_xs_pipe_kernel, relax3d_xs_pipe_v2_kernel)
+bool relax3d_lds_shape_known(int shape);  // is "relax3d.lds" = 100*WX + 10*WY + R a compiled workgroup shape? (mgx_core.hip)
+// the shortest run of planes the automatic choice hands to the pipelined kernel (relax3d_xs_pass2 merges shorter ones)
+template <class real>
+int pipe_min_planes(int sx);
+// How a pass of the pipelined kernels launches (pipe_plan decides it; false: they do not take the level)
+enum class PipePass { Plain, Zero, Corr };  // a colour pass; the first sweep from zero (VAR = 3); the correcting red pass (VAR = 2)
+
+struct PipePlan {
+    bool v2 = false;            // relax3d_xs_pipe_v2_kernel (two x-pairs per lane)
+    int WX = 2, WY = 8, R = 2;  // waves across x and y, rows per wave
+    bool fnt = false;           // non-temporal loads of f
+    int unr = 0;                // 0: the rolled step loop; unrolled four times: 1 + q0 (entry row parity q0), 3 + q0 requesting two steps ahead
+    int zchunk = 0;             // planes per run (even when unrolled)
+    int gx = 0, gy = 0;         // tiles across x and y
+    dim3 grid, block;
+    int xcd = 0;
+    // the correcting pass corrects every value it reads from a neighbouring tile itself: no set P beforehand
+    bool corrects_edges() const { return !v2 || unr; }
+};
+template <class real>
+bool pipe_plan(const mgx_ctx* ctx, PipePass pass, int sx, int sy, int zbeg, int zend, int colour, PipePlan& p);
+// one colour pass / the first sweep of a zero level on the pipelined kernels; false: not taken, the caller uses relax3d_xs_kernel
+template <class real>
+bool relax3d_xs_pass_lds(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zbeg, int zend, real hx2, real hy2,
+                         real hz2, int colour);
+template <class real>
+bool relax3d_xs_first_sweep_zero(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int sz, real hx2, real hy2, real hz2);
+// the red pass that reads black through the coarse-grid correction (VAR = 2): does a level take it; its launch
+bool corr_fused_takes(const mgx_ctx* ctx, int sx, int sy, int sz_global, int nplanes);
+template <class real>
+void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zb, int ze, real hx2, real hy2, real hz2, int colour,
+                     const real* coarse_sh, int cx, int cy, int szl, int ckmax, int zg0 = 0, real* vout = nullptr);
+
+// ---- mgx_transfer3d.hip: the transfers between levels (the two the composites of mgx_kernels3d.hip call: v += Interpolate(coarse_v)
+// on a run of coarse planes, one colour or both; the set P of the correcting red pass corrected in place)
+template <class real>
+int interpolate_correct3d_slab(mgx_ctx* ctx, real* v, const int n[3], int fzoff, const real* coarse_v, const int cn[3],
+                               int czoff, int pzbeg, int pzend, int colour, bool add = true);
+template <class real>
+void corr_pset_launch(mgx_ctx* ctx, real* v, int sx, int sy, int fzoff, const real* coarse_v, const int cn[3], int czoff, int zmin,
+                      int zmax);
+
+// ---- mgx_small3d.hip: all sweeps of a Relax call on a level of at most SMALL_MAX points per axis in one workgroup
+template <class real, class L>
+int relax3d_small(mgx_ctx* ctx, real* v, const real* f, const int n[3], real hx2, real hy2, real hz2, int ncycles);
 
 // ---- mgx_rr3d.hip: residual + restrict
 // How a residual+restrict launch runs (rr_plan decides it).  The kernels: the LDS rolling window (residual_restrict3d_kernel),
@@ -67,6 +117,11 @@ bool rr_plan(const mgx_ctx* ctx, bool xsplit, bool black, const int n[3], const 
 template <class real, class L>
 int residual_restrict3d(mgx_ctx* ctx, const real* v, const real* f, const int n[3], const real h[3], int mode, real* coarse_f,
                         const int cn[3], bool rim_is_zero = false);
+
+// ---- mgx_semi3d.hip
+// boundary points of an x-split array := 0 (rim_zero3d_xs_kernel; pads are not touched)
+template <class real>
+void rim_zero3d_xs(mgx_ctx* ctx, real* a, const int n[3]);
 
 // ---- mgx_relax_rr3d.hip: the last black pass inside the residual+restrict launch
 bool relax_rr3d_xs_takes(const mgx_ctx* ctx, const int n[3], const int cn[3], size_t elem);

@@ -149,7 +149,7 @@ __global__ void __launch_bounds__(256) set2d_kernel(real* __restrict__ g, int sx
 }
 
 // Levels up to 65^2 (<= 4225 points): all `ncycles` red-black sweeps of a Relax call in ONE workgroup with v and f
-// in LDS and a barrier between colour passes (see relax3d_small_kernel); bit-identical to the multi-launch path.
+// in LDS and a barrier between colour passes (see relax3d_small_kernel, mgx_small3d.hip); bit-identical to the multi-launch path.
 constexpr int SMALL2_MAX = 65;
 template <class real>
 __global__ void __launch_bounds__(1024) relax2d_small_kernel(real* __restrict__ v, const real* __restrict__ f, int sx, int sy,

@@ -1,5 +1,5 @@
 // mgx_kernels3d.hpp -- per-point expressions of the 3D operators (device inline), shared by
-// the kernels of both array layouts (natural and x-split) in mgx_kernels3d.hip, mgx_rr3d.hip and the files of the later families
+// the kernels of both array layouts (natural and x-split) in mgx_kernels3d.hip, mgx_pipe3d.hip, mgx_transfer3d.hip, mgx_small3d.hip, mgx_rr3d.hip and the files of the later families
 // (what their host sides share: mgx_host3d.hpp).
 //
 // These are the ONLY places where the arithmetic of the reference is restated on the device;

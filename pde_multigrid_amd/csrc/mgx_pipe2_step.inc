@@ -1,5 +1,5 @@
 // mgx_pipe2_step.inc -- ONE step (plane z) of relax3d_xs_pipe_v2_kernel's unrolled loop (two x-pairs per lane), included four
-// times with MGX_K = 0 ... 3 (mgx_kernels3d.hip).  Register roles by step as in mgx_pipe_step.inc: planes z - 1, z, z + 1 and the one
+// times with MGX_K = 0 ... 3 (mgx_pipe3d.hip).  Register roles by step as in mgx_pipe_step.inc: planes z - 1, z, z + 1 and the one
 // on its way are c[K & 3], c[(K + 1) & 3], c[(K + 2) & 3], c[(K + 3) & 3]; f / rim / edge rows / results in pairs of sets by step
 // parity; the row parity q = (UNR - 1) ^ (K & 1) is a literal.  The two points a lane updates per row are formed as ONE two-element
 // vector expression (relax3d_num2: packed fp32 multiplies and adds, element-wise IEEE: the bits of the scalar form).

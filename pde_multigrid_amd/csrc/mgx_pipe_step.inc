@@ -1,5 +1,5 @@
 // mgx_pipe_step.inc -- ONE step (plane z) of relax3d_xs_pipe_kernel's unrolled loop, included once per step of a loop trip with
-// MGX_K = 0 ... 3 (DEPTH 1) or 0 ... 5 (DEPTH 2) (mgx_kernels3d.hip).  Register roles by step: the planes z - 1, z, z + 1 are c[K % CR],
+// MGX_K = 0 ... 3 (DEPTH 1) or 0 ... 5 (DEPTH 2) (mgx_pipe3d.hip).  Register roles by step: the planes z - 1, z, z + 1 are c[K % CR],
 // c[(K + 1) % CR], c[(K + 2) % CR]; c[(K + 3) % CR] is the plane that ARRIVES during this step (z + 2) and c[(K + 2 + DEPTH) % CR] the one
 // REQUESTED in it -- the same set with DEPTH 1 (CR = 4: loads one step ahead, waited for with vmcnt(0) at the step's end), one further
 // on with DEPTH 2 (CR = 6: the column and f are requested TWO steps ahead, the step's end waits for everything but the 2 R loads it

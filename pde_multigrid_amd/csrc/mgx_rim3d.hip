@@ -417,8 +417,7 @@ static int residual_op3d_bc(mgx_ctx* ctx, const real* v, const real* f, const re
     Rim R;
     MGX_TRY_RET(rim_list<real>(n, bc, what, R));
     if (r)  // every boundary point first: the Dirichlet points keep the 0
-        MGX_LAUNCH((rim_zero3d_xs_kernel<real>), dim3(ceil_div(n[0], 64), ceil_div(n[1], 4), n[2]), dim3(64, 4, 1), 0, ctx->compute, r, n[0], n[1],
-                   n[2]);
+        rim_zero3d_xs<real>(ctx, r, n);
     const Op op(ctx, h, s);
     MGX_TRY_RET((residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, op, dev_work, dev_sumsq, false)));
     const dim3 g = krylov_grid(n);

@@ -17,7 +17,9 @@
 //                                        recipe); x-neighbours come from the adjacent lanes
 //   interpolate_axes3d_xs_kernel         v (+)= I_m(coarse_v) on the interior, one fine cell of the coarse mesh per thread
 //   restrict_axes3d_xs_kernel            Restrict with the boundary injected (FMG only)
+//   rim_zero3d_xs_kernel                 boundary points := 0; the operators of mgx_stencil3d.hpp call rim_zero3d_xs (mgx_host3d.hpp)
 // The stencils and the first kernel live in mgx_semi3d.hpp: mgx_shift3d.hip instantiates that kernel with a shift.
+#include "mgx_host3d.hpp"
 #include "mgx_semi3d.hpp"
 
 namespace mgx {
@@ -82,8 +84,23 @@ __global__ void __launch_bounds__(256) restrict_axes3d_xs_kernel(const real* __r
     coarse[ci] = semi_restrict_point<real, MASK>([&](int dx, int dy, int dz) { return fine[gf.pos(x + dx) + gf.row(y + dy, z + dz)]; });
 }
 
+// boundary points of an x-split array := 0 (pads are not touched)
+template <class real>
+__global__ void __launch_bounds__(256) rim_zero3d_xs_kernel(real* __restrict__ a, int sx, int sy, int sz) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y, z = blockIdx.z;
+    if (x >= sx || y >= sy) return;
+    if (!(x == 0 || x == sx - 1 || y == 0 || y == sy - 1 || z == 0 || z == sz - 1)) return;
+    const Geo<XSplit, real> g(sx, sy);
+    a[g.pos(x) + g.row(y, z)] = (real)0;
+}
+
 // =========================================================================== host side
-static inline dim3 blk() { return dim3(64, 4, 1); }
+template <class real>
+void rim_zero3d_xs(mgx_ctx* ctx, real* a, const int n[3]) {
+    MGX_LAUNCH((rim_zero3d_xs_kernel<real>), dim3(ceil_div(n[0], 64), ceil_div(n[1], 4), n[2]), blk(), 0, ctx->compute, a, n[0], n[1], n[2]);
+}
+template void rim_zero3d_xs<float>(mgx_ctx*, float*, const int[3]);
+template void rim_zero3d_xs<double>(mgx_ctx*, double*, const int[3]);
 
 template <class real>
 static int restrict_axes3d(mgx_ctx* ctx, const real* fine, const int fn[3], real* coarse, const int cn[3], int mask) {
@@ -114,8 +131,7 @@ static int residual_restrict_axes3d(mgx_ctx* ctx, const real* v, const real* f, 
     MGX_USE(ctx);
     const ResidualScale<real> s = residual_scale<real>(ctx, h, mode);
     if (!coarse_rim_is_zero)
-        MGX_LAUNCH((rim_zero3d_xs_kernel<real>), dim3(ceil_div(cn[0], 64), ceil_div(cn[1], 4), cn[2]), blk(), 0, ctx->compute, coarse_f,
-                   cn[0], cn[1], cn[2]);
+        rim_zero3d_xs<real>(ctx, coarse_f, cn);
     if (cn[0] > 2 && cn[1] > 2 && cn[2] > 2) {
         constexpr int TYW = 4;
         with_value<1, 2, 3, 4, 5, 6>(mask, [&](auto m) __attribute__((always_inline)) {

@@ -1,5 +1,5 @@
 // mgx_semi3d.hpp -- what the transfers of a semi-coarsened step share with the shifted operators (mgx_shift3d.hip): the
-// restriction stencils, the streaming residual + restrict kernel and the boundary zero fill.  See mgx_semi3d.hip.
+// restriction stencils and the streaming residual + restrict kernel.  See mgx_semi3d.hip.
 #pragma once
 #include "mgx_kernels3d.hpp"
 
@@ -178,16 +178,6 @@ __global__ void __launch_bounds__(64 * TYW)
             for (int r = 0; r < NRR; r++) { rA[0][r] = rA[2][r]; rB[0][r] = rB[2][r]; }
         }
     }
-}
-
-// boundary points of an x-split array := 0 (pads are not touched)
-template <class real>
-__global__ void __launch_bounds__(256) rim_zero3d_xs_kernel(real* __restrict__ a, int sx, int sy, int sz) {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y, z = blockIdx.z;
-    if (x >= sx || y >= sy) return;
-    if (!(x == 0 || x == sx - 1 || y == 0 || y == sy - 1 || z == 0 || z == sz - 1)) return;
-    const Geo<XSplit, real> g(sx, sy);
-    a[g.pos(x) + g.row(y, z)] = (real)0;
 }
 
 // =========================================================================== host side

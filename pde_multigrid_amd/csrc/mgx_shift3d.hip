@@ -81,8 +81,7 @@ static int residual_restrict_shift3d(mgx_ctx* ctx, const real* v, const real* f,
     MGX_USE(ctx);
     const ResidualScale<real> sc = residual_scale<real>(ctx, h, MGX_RESIDUAL_CORRECT);
     if (!coarse_rim_is_zero)
-        MGX_LAUNCH((rim_zero3d_xs_kernel<real>), dim3(ceil_div(cn[0], 64), ceil_div(cn[1], 4), cn[2]), dim3(64, 4, 1), 0, ctx->compute, coarse_f,
-                   cn[0], cn[1], cn[2]);
+        rim_zero3d_xs<real>(ctx, coarse_f, cn);
     if (cn[0] > 2 && cn[1] > 2 && cn[2] > 2) {
         constexpr int TYW = 4;
         with_value<1, 2, 3, 4, 5, 6, 7>(mask, [&](auto m) __attribute__((always_inline)) {

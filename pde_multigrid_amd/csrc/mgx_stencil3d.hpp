@@ -330,8 +330,7 @@ static int residual_op3d(mgx_ctx* ctx, const real* v, const real* f, const real*
     MGX_TRY_RET(rows_check(n, what, Op::HAS_S ? &sd : nullptr));
     MGX_USE(ctx);
     if (r)  // the boundary of r is 0, as mgx3dxs_residual leaves it
-        MGX_LAUNCH((rim_zero3d_xs_kernel<real>), dim3(ceil_div(n[0], 64), ceil_div(n[1], 4), n[2]), dim3(64, 4, 1), 0, ctx->compute, r, n[0], n[1],
-                   n[2]);
+        rim_zero3d_xs<real>(ctx, r, n);
     return residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, Op(ctx, h, s), dev_work, dev_sumsq);
 }
 
