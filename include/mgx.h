@@ -359,6 +359,26 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* over the local planes [zbeg, zend); the planes next to that range are read as ghosts.          */ \
     /* residual_restrict_slab / interpolate_correct_slab: global coarse planes [pzbeg, pzend);        */ \
     /* interpolate_correct writes the fine planes 2pz and 2pz+1 of every listed pz (z = 0 skipped).   */ \
+    /* What the z-slab forms read and write (tests/test_gpu_slab_entries.py holds them to it; zoff,   */ \
+    /* fzoff, czoff of either parity unless stated).  "Reads" = values that reach a result: a kernel   */ \
+    /* may load more inside the planes listed, never outside the local array.  Every word not listed   */ \
+    /* as written stays as it was, pad entries included.                                               */ \
+    /*   relax_colour_slab(2): writes the colour's interior points of the listed planes; reads f at    */ \
+    /*     those points and the OTHER colour of v on the planes [zbeg - 1, zend] (of either run) --     */ \
+    /*     no point of the updated colour, in particular none in the two ghost planes.                */ \
+    /*   relax_zero_colour_slab: the same writes; reads f at those points and nothing of v.            */ \
+    /*   residual_restrict_slab: writes the coarse planes [pzbeg, pzend) whole (boundary and pad       */ \
+    /*     entries as 0); with p0 = max(pzbeg, 1), p1 = min(pzend, cn[2] - 1) it reads v on the fine   */ \
+    /*     planes [2 p0 - 2, 2 p1] and f on [2 p0 - 1, 2 p1 - 1]: fzoff <= 2 p0 - 2, czoff <= pzbeg.    */ \
+    /*   residual_sumsq_slab: reads v on the local planes [zbeg - 1, zend], f on [zbeg, zend).         */ \
+    /*   restrict_slab: writes the data entries of the coarse planes [pzbeg, pzend); reads the fine   */ \
+    /*     planes 2 pz - 1 ... 2 pz + 1 of an interior pz and the plane 2 pz alone of pz = 0 and       */ \
+    /*     cn[2] - 1 (injection).                                                                     */ \
+    /*   interpolate_slab / interpolate_correct(_colour)_slab: pzend <= cn[2] - 1; write the interior  */ \
+    /*     points (of the colour) of the fine planes 2 pz, 2 pz + 1 -- fzoff <= max(2 pzbeg, 1) -- and   */ \
+    /*     read the coarse planes [pzbeg, pzend]; the _correct forms read what they write, plain       */ \
+    /*     interpolate reads nothing of the fine array.                                               */ \
+    /*   set_interior_slab: writes the (x, y)-interior of the local planes [zbeg, zend), zbeg >= 0.   */ \
     int mgx3dxs_relax_colour_slab_##SFX(mgx_ctx* ctx, real* v, const real* f, int sx, int sy,           \
                                         const real h[3], int colour, int zbeg, int zend, int zoff);     \
     /* relax_colour_slab2: the same pass over TWO runs of local planes [zb1, ze1) and [zb2, ze2), ze1   */ \
@@ -414,7 +434,12 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* GLOBAL fine planes [2 pzbeg - 1, 2 pzend - 1] + residual + restrict into the GLOBAL coarse planes   */ \
     /* [pzbeg, pzend).  n / cn are global sizes, v / f start at global plane fzoff (even), coarse_f at     */ \
     /* global coarse plane czoff.  It reads only red values of v (fine planes 2 pzbeg - 3 ... 2 pzend + 1, */ \
-    /* clipped to the grid: they must be present and current) and f.  relax_rr_takes: 1 when a level of   */ \
+    /* clipped to the grid: they must be present and current) and f (planes 2 pzbeg - 2 ... 2 pzend) --    */ \
+    /* and, of the black points, only ones no pass writes: the face entries of the planes [2 pzbeg - 1,    */ \
+    /* 2 pzend - 1] and the grid's planes 0 and n[2] - 1 where they lie next to that range.  No other      */ \
+    /* black value reaches a result, inside or outside the range; the black interior points of the planes  */ \
+    /* [2 pzbeg - 1, 2 pzend - 1] and the coarse planes (whole, boundary and pads 0) are all it writes.    */ \
+    /* An odd fzoff is MGX_ERR_INVALID.  relax_rr_takes: 1 when a level of                                 */ \
     /* these global sizes has the kernel; otherwise relax_rr_slab fails with MGX_ERR_INVALID.              */ \
     int mgx3dxs_relax_rr_takes_##SFX(const mgx_ctx* ctx, const int n[3], const int cn[3]);              \
     int mgx3dxs_relax_rr_slab_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3], int fzoff,    \
@@ -431,6 +456,13 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* relax_corr_colour_slab: the RED                                                                    */ \
     /* pass over the LOCAL planes [zbeg, zend), every other black value read through the correction; the  */ \
     /* black pass that must follow rewrites every black interior point.                                  */ \
+    /* Both refuse (MGX_ERR_INVALID) a level whose rows or switches the kernel does not run on -- the     */ \
+    /* conditions of corr_fused_takes other than nplanes: a short range of an accepted level is fine --   */ \
+    /* and relax_corr_colour_slab an odd fzoff.  correct_pset_slab writes black interior points of the    */ \
+    /* planes [zmin, zmax) only, each either left alone or corrected.  relax_corr_colour_slab writes the  */ \
+    /* red interior points of [zbeg, zend); it reads f there, the black values of v on the planes         */ \
+    /* [zbeg - 1, zend] and the GLOBAL coarse planes (fzoff + zbeg - 1) / 2 ... (fzoff + zend + 1) / 2,    */ \
+    /* all of which must lie within the cplanes planes handed in (the kernel clamps what it requests).     */ \
     int mgx3dxs_corr_fused_takes_##SFX(const mgx_ctx* ctx, const int n[3], int nplanes);                \
     /* block3_up_takes: 1 when mgx3dxs_interpolate_correct_relax_pp on a level of these sizes with      */ \
     /* `ncycles` sweeps runs its passes B, R, B in one launch ("relax3d.block3_up"); such a call brings   */ \
@@ -780,7 +812,12 @@ int mgx_comm_wait(mgx_ctx* ctx);
 /* Half planes for the ghost exchange behind a colour pass: only the half-rows that hold `colour` (even-x half where
  * colour + y + z is even, z = the plane's GLOBAL index) are packed into a staging array of mgx3dxs_halfplane_elems
  * elements (compute stream), exchanged with mgx_comm_halo_exchange, and unpacked into the ghost plane on the stream the
- * receive was enqueued on (mgx_comm_wait covers it).  Two planes per call (either may be NULL). */
+ * receive was enqueued on (mgx_comm_wait covers it).  Two planes per call (either may be NULL).
+ * The staging array has one row of H = roundup((sx + 1) / 2, A) elements per row y of the plane (A, H, H2 as in the x-split
+ * layout).  A row's half is copied WHOLE, pad entries included: H elements of an even-x half, H2 = roundup(sx / 2, A) of an
+ * odd-x half, from / to the start of the staging row; the staging elements H2 ... H - 1 of such a row, everything behind
+ * halfplane_elems, the other half of every row of the plane and every other plane are neither read nor written.  No-ops on a
+ * context without a communicator. */
 size_t mgx3dxs_halfplane_elems_f32(int sx, int sy);
 size_t mgx3dxs_halfplane_elems_f64(int sx, int sy);
 int mgx3dxs_halo_pack_f32(mgx_ctx* ctx, const float* plane_a, int z_a, float* stage_a, const float* plane_b, int z_b, float* stage_b, int sx,

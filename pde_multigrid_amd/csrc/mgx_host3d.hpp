@@ -84,6 +84,8 @@ template <class real>
 bool relax3d_xs_first_sweep_zero(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int sz, real hx2, real hy2, real hz2);
 // the red pass that reads black through the coarse-grid correction (VAR = 2): does a level take it; its launch
 bool corr_fused_takes(const mgx_ctx* ctx, int sx, int sy, int sz_global, int nplanes);
+// ... without the number of planes: the rows and switches alone (what the z-slab entries of that pass check)
+bool corr_fused_level_takes(const mgx_ctx* ctx, int sx, int sy, int sz_global);
 template <class real>
 void corr_red_launch(mgx_ctx* ctx, real* v, const real* f, int sx, int sy, int zb, int ze, real hx2, real hy2, real hz2, int colour,
                      const real* coarse_sh, int cx, int cy, int szl, int ckmax, int zg0 = 0, real* vout = nullptr);

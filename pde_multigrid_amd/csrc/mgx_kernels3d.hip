@@ -682,6 +682,8 @@ int relax3d_corr_colour_slab(mgx_ctx* ctx, real* v, const real* f, const int n[3
     if (st) return st;
     MGX_REQUIRE(fzoff >= 0 && (fzoff & 1) == 0 && czoff >= 0 && fzoff / 2 >= czoff && cplanes >= 1 && zbeg >= 1 && zend >= zbeg,
                 MGX_ERR_INVALID, "relax_corr_colour_slab: bad plane ranges (the slab must start on an even global plane)");
+    MGX_REQUIRE(corr_fused_level_takes(ctx, n[0], n[1], n[2]), MGX_ERR_INVALID,
+                "relax_corr_colour_slab: the level is not taken (ask corr_fused_takes)");
     if (zend == zbeg) return MGX_OK;
     const int ckmax = czoff + cplanes - 1 - fzoff / 2;
     MGX_REQUIRE(ckmax >= (zend >> 1), MGX_ERR_INVALID, "relax_corr_colour_slab: the coarse slab does not reach the plane above the fine range");

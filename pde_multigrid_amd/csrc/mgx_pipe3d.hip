@@ -1346,8 +1346,15 @@ bool relax3d_xs_first_sweep_zero(mgx_ctx* ctx, real* v, const real* f, int sx, i
 // ---- the coarse-grid correction read on the fly by the first red pass of the post-smoothing (relax3d_xs_pipe_kernel, VAR = 2)
 // does a level (rows of sx points, sy rows, `nplanes` planes to update) take it?
 bool corr_fused_takes(const mgx_ctx* ctx, int sx, int sy, int sz_global, int nplanes) {
+    return corr_fused_level_takes(ctx, sx, sy, sz_global) && nplanes >= 8;
+}
+
+// the part of that rule that belongs to the level and the context's switches: the rows the kernel runs on.  The z-slab entries
+// (mgx3dxs_relax_corr_colour_slab, mgx3dxs_correct_pset_slab) refuse a level it does not hold for; the number of planes is the
+// caller's business (the slab driver hands the short edge ranges of an accepted level to the same kernel).
+bool corr_fused_level_takes(const mgx_ctx* ctx, int sx, int sy, int sz_global) {
     const bool small = sx <= SMALL_MAX && sy <= SMALL_MAX && sz_global <= SMALL_MAX && ctx->relax_small;
-    return ctx->corr_fuse && !small && ctx->relax_lds < 0 && (sx + 1) / 2 - 1 >= 128 && sy - 2 >= 64 && nplanes >= 8;
+    return ctx->corr_fuse && !small && ctx->relax_lds < 0 && (sx + 1) / 2 - 1 >= 128 && sy - 2 >= 64;
 }
 
 // the red pass through the correction over the LOCAL planes [zb, ze) of v: `coarse_sh` = the coarse array shifted so that

@@ -573,6 +573,7 @@ int correct_pset3d_slab(mgx_ctx* ctx, real* v, const int n[3], int fzoff, const 
     if (st) return st;
     MGX_REQUIRE(fzoff >= 0 && czoff >= 0 && zmin >= 1 && zmin >= fzoff && zmax <= n[2] - 1 && zmin / 2 >= czoff, MGX_ERR_INVALID,
                 "correct_pset_slab: bad plane window");
+    MGX_REQUIRE(corr_fused_level_takes(ctx, n[0], n[1], n[2]), MGX_ERR_INVALID, "correct_pset_slab: the level is not taken (ask corr_fused_takes)");
     corr_pset_launch<real>(ctx, v, n[0], n[1], fzoff, coarse_v, cn, czoff, zmin, zmax);
     MGX_LAUNCH_CHECK();
     return MGX_OK;
