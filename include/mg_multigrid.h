@@ -121,7 +121,12 @@ typedef struct mgGraphFlags {
                        /* change, or the context's parameters, mgx_ctx_generation).  Default 0.       */ \
         int capturing;                                                                                   \
         void* graph_exec[MG_MAX_LEVELS];                                                                 \
-        long long graph_key[MG_MAX_LEVELS - 1]; /* unused */                                             \
+        long long graph_key[MG_MAX_LEVELS - 2]; /* unused */                                             \
+        /* internal: the capacity c of div(a grad u) - (shift c) u = f, a table of one device array     */ \
+        /* per level, or NULL (no capacity: the scalar-shift operators).  Owned by _set_capacity,       */ \
+        /* freed by _destroy.  Like pcg_fproj below it takes eight bytes of the unused graph_key:       */ \
+        /* every member keeps its offset and the struct its size.                                       */ \
+        void* cap;                                                                                       \
         /* internal: PCG's fifth level-0 scratch array, the projected right-hand side f - mean_W(f) of   */ \
         /* the closed box without a shift (krylov = 2; allocated by the first such call, freed by        */ \
         /* _destroy).  It takes the last eight bytes of the unused graph_key: every member keeps its     */ \
@@ -226,6 +231,26 @@ typedef struct mgGraphFlags {
     int mgMultiGrid3D_##R##_set_coefficient(mgMultiGrid3D_##R* mg, const real* host_a);                  \
     /* the coefficient of level gridID as a host array in the reference layout                           */ \
     int mgMultiGrid3D_##R##_download_coefficient(mgMultiGrid3D_##R* mg, int gridID, real* host);         \
+    /* The operator with a capacity, div(a grad u) - (shift c) u = f (an addition; mgx3dxs_*_cap of     */ \
+    /* mgx.h).  host_c: c at all points of level 0, reference layout, every value finite  */ \
+    /* and >= 0 (else MGX_ERR_INVALID, and the hierarchy stays as it was).  The hierarchy must have a   */ \
+    /* coefficient (_set_coefficient first, an array of ones serves; else MGX_ERR_INVALID), and         */ \
+    /* _set_coefficient(NULL) is MGX_ERR_INVALID while a capacity is set.  Level 0 is uploaded and c    */ \
+    /* goes down all maxGrids levels exactly as the coefficient does (mgx3dxs_restrict /                */ \
+    /* _restrict_axes by the step's mask: full weighting inside, injection on the boundary, so c stays  */ \
+    /* >= 0).  The arrays are allocated by the first call and reused by later ones.  Relax,             */ \
+    /* CalculateResidual (ResidualNorm, download_residual), VCycle, FullMultiGridVCycle and PCG         */ \
+    /* (krylov 0, 1 and, with a mask, 2) then run the _cap entries on every level through the route     */ \
+    /* the coefficient operator takes, on full and semi-coarsened hierarchies and with any mask;        */ \
+    /* BackwardEuler steps c u_t = kappa div(a grad u) + q (s = 1 / (kappa dt) as before, the right-    */ \
+    /* hand side by mgx3dxs_cap_rhs).  PCG_mixed returns MGX_ERR_INVALID.  All six faces Neumann with   */ \
+    /* a capacity that has no positive entry is singular like shift == 0, and MGX_ERR_INVALID where     */ \
+    /* the operator is used (PCG with krylov = 2 included). host_c == NULL frees the arrays: the        */ \
+    /* hierarchy is what it was without one, bit for bit.  use_graph: level 0's array is part of the    */ \
+    /* record, and every call drops the captured graphs.  Blocking.                                     */ \
+    int mgMultiGrid3D_##R##_set_capacity(mgMultiGrid3D_##R* mg, const real* host_c);                     \
+    /* the capacity of level gridID as a host array in the reference layout                              */ \
+    int mgMultiGrid3D_##R##_download_capacity(mgMultiGrid3D_##R* mg, int gridID, real* host);            \
     int mgMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6],     \
                                    mgMultiGrid3D_##R** out);                                             \
     int mgMultiGrid3D_##R##_create_layout(mgx_ctx* ctx, const int finestGridSizeXYZ[3],                  \

@@ -712,7 +712,44 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
                               double* dev_work, double* dev_sum, int bc);                               \
     int mgx3dxs_cg_direction_bc_##SFX(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3],    \
                                       const double* dev_alpha, const double* dev_beta, int bc);         \
-    int mgx3dxs_project_bc_##SFX(mgx_ctx* ctx, real* a, const int n[3], double* dev_work, double* dev_mean, int bc);
+    int mgx3dxs_project_bc_##SFX(mgx_ctx* ctx, real* a, const int n[3], double* dev_work, double* dev_mean, int bc);\
+    /* ---- the operator with a capacity, div(a grad u) - (s c) u = f, c >= 0 at the grid nodes next to */ \
+    /* the coefficient a, x-split layout (csrc/mgx_cap3d.hip).  An addition: the implicit */ \
+    /* step of c u_t = kappa div(a grad u) + q, reaction terms that vary in space.  c is an array of    */ \
+    /* the level's layout, read at the updated point only and never written.  Arithmetic: in `real`, sc */ \
+    /* = s * c_P (one rounding), then the coefficient operator's expressions above with sc where they   */ \
+    /* take s; with c == 1 every entry gives the bits of its _coef entry.  At an unknown on a Neumann   */ \
+    /* face the capacity is that of the point itself.                                                   */ \
+    /* Each entry is the _coef entry (cap_rhs: the shift_rhs entry), argument for argument, plus `const */ \
+    /* real* c` after a (cap_rhs: after u), with that entry's contract: MGX_ERR_INVALID for NULL        */ \
+    /* arguments, a bad s or a bc outside 0 .. 63, MGX_ERR_SIZE for bad sizes; f, a and c are never     */ \
+    /* written, pads are neither read as data nor written, the sums give the same bits on every run.    */ \
+    /* The values of c are not checked here (mgMultiGrid3D_<r>_set_capacity does).                      */ \
+    /* mgx_ctx_last_relax_kernel reports relax_cap3d_xs_kernel / relax_cap_zero3d_xs_kernel.            */ \
+    /* cap_rhs: f = (-((s*c)*u)) - qscale*q, f = -((s*c)*u) when q is NULL.                             */ \
+    int mgx3dxs_relax_cap_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c,     \
+                                const int n[3], const real h[3], real s, int ncycles);                  \
+    int mgx3dxs_relax_cap_from_zero_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,          \
+                                          const real* c, const int n[3], const real h[3], real s,       \
+                                          int ncycles, int rim_is_zero);                                \
+    int mgx3dxs_residual_cap_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a,           \
+                                   const real* c, real* r, const int n[3], const real h[3], real s,     \
+                                   double* dev_work, double* dev_sumsq);                                \
+    int mgx3dxs_apply_cap_dot_##SFX(mgx_ctx* ctx, const real* p, const real* a, const real* c, real* q, \
+                                    const int n[3], const real h[3], real s, double* dev_work,          \
+                                    double* dev_sum);                                                   \
+    int mgx3dxs_cap_rhs_##SFX(mgx_ctx* ctx, const real* u, const real* c, const real* q, real qscale,   \
+                              real s, real* f, const int n[3]);                                         \
+    int mgx3dxs_relax_cap_bc_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c,  \
+                                   const int n[3], const real h[3], real s, int ncycles, int bc);       \
+    int mgx3dxs_residual_cap_bc_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a,        \
+                                      const real* c, real* r, const int n[3], const real h[3], real s,  \
+                                      double* dev_work, double* dev_sumsq, int bc);                     \
+    int mgx3dxs_apply_cap_dot_bc_##SFX(mgx_ctx* ctx, const real* p, const real* a, const real* c,       \
+                                       real* q, const int n[3], const real h[3], real s,                \
+                                       double* dev_work, double* dev_sum, int bc);                      \
+    int mgx3dxs_cap_rhs_bc_##SFX(mgx_ctx* ctx, const real* u, const real* c, const real* q, real qscale,\
+                                 real s, real* f, const int n[3], int bc);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)

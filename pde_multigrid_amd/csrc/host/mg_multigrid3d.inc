@@ -190,8 +190,25 @@ static int MG_CAT(semi_below3_, R)(const MGRID* mg, int from) {
     return 0;
 }
 
+/* the capacity of div(a grad u) - (shift c) u = f: mg->cap points to this table, one device array per level (all maxGrids levels or
+ * no table), and whether level 0 holds a positive entry (without one the operator has no zeroth-order term) */
+typedef struct MG_CAT(mgCapTable3_, R) {
+    REAL* d_c[MG_MAX_LEVELS];
+    int positive;
+} MG_CAT(mgCapTable3_, R);
+#define CAPTAB MG_CAT(mgCapTable3_, R)
+
+static void MG_CAT(cap_table_free3_, R)(MGRID* mg) {
+    CAPTAB* t = (CAPTAB*)mg->cap;
+    if (!t) return;
+    for (int i = 0; i < MG_MAX_LEVELS; i++) mgx_free(mg->ctx, t->d_c[i]);
+    free(t);
+    mg->cap = NULL;
+}
+
 void FN(destroy)(MGRID* mg) {
     if (!mg) return;
+    MG_CAT(cap_table_free3_, R)(mg);
     for (int i = 0; i < MG_MAX_LEVELS; i++)
         if (mg->graph_exec[i]) mgx_graph_destroy(mg->ctx, mg->graph_exec[i]);
     if (mg->pcg_graph_exec) mgx_graph_destroy(mg->ctx, mg->pcg_graph_exec);
@@ -245,6 +262,16 @@ size_t MG_CAT3(mgGrid3D_, R, _sizeof)(void) { return sizeof(GRID); }
 /* "this hierarchy has a coefficient": level 0 holds one (set_coefficient allocates every level or none) */
 static int MG_CAT(has_coef3_, R)(const MGRID* mg) { return mg->grids3D && mg->grids3D[0] && mg->grids3D[0]->d_a != NULL; }
 
+/* "this hierarchy has a capacity" (set_capacity asks for a coefficient first), and the capacity array of grid g (NULL: none, or g
+ * is no level of the hierarchy) */
+static int MG_CAT(has_cap3_, R)(const MGRID* mg) { return mg->cap != NULL; }
+static const REAL* MG_CAT(cap_of3_, R)(const MGRID* mg, const GRID* g) {
+    const CAPTAB* t = (const CAPTAB*)mg->cap;
+    for (int i = 0; t && i < mg->maxGrids; i++)
+        if (mg->grids3D[i] == g) return t->d_c[i];
+    return NULL;
+}
+
 /* what a coefficient needs of the hierarchy (the members are public: checked where the coefficient is used, too) */
 static int MG_CAT(coef_ok3_, R)(const MGRID* mg, const char* what) {
     MG_REQUIRE(isfinite((double)mg->shift) && mg->shift >= 0, MGX_ERR_INVALID, "%s: the shift %g is not finite and >= 0", what, (double)mg->shift);
@@ -278,6 +305,13 @@ static int MG_CAT(bc_singular3_, R)(const MGRID* mg, const char* what) {
                "%s: Neumann data on all six faces with shift = 0 is singular (set a shift > 0 or keep a Dirichlet face)", what);
     return MGX_OK;
 }
+/* ... nor has one whose capacity has no positive entry, whatever the shift: shift * c is zero everywhere */
+static int MG_CAT(cap_singular3_, R)(const MGRID* mg, const char* what) {
+    MG_REQUIRE(!(mg->bc == 63 && mg->cap && !((const CAPTAB*)mg->cap)->positive), MGX_ERR_INVALID,
+               "%s: Neumann data on all six faces with a capacity that has no positive entry is singular (set a capacity with a "
+               "positive entry or keep a Dirichlet face)", what);
+    return MGX_OK;
+}
 
 /* The operators other than the plain Laplacian: the variable-coefficient one where the hierarchy has a coefficient (with any
  * shift), else the shifted one where shift != 0.  What the hierarchy's operator needs of the hierarchy and of the grid g it is
@@ -285,9 +319,11 @@ static int MG_CAT(bc_singular3_, R)(const MGRID* mg, const char* what) {
 static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) {
     MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, what));
     MG_TRY(MG_CAT(bc_singular3_, R)(mg, what));
+    MG_TRY(MG_CAT(cap_singular3_, R)(mg, what));
     if (!MG_CAT(has_coef3_, R)(mg)) return MG_CAT(shift_ok3_, R)(mg, mg->shift, what);
     MG_TRY(MG_CAT(coef_ok3_, R)(mg, what));
     MG_REQUIRE(g->d_a, MGX_ERR_INVALID, "%s: the grid has no coefficient array", what);
+    MG_REQUIRE(!MG_CAT(has_cap3_, R)(mg) || MG_CAT(cap_of3_, R)(mg, g), MGX_ERR_INVALID, "%s: the grid has no capacity array", what);
     return MGX_OK;
 }
 
@@ -295,6 +331,9 @@ static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) 
  * *dev_sumsq (NULL: none; dev_work: the partials).  The plain operator takes mg->residual_mode and sums in a launch of its own. */
 static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, const REAL* f, REAL* r, double* dev_work, double* dev_sumsq) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    if (MG_CAT(has_cap3_, R)(mg))
+        return MG_CAT(mgx3dxs_residual_cap_bc_, R)(mg->ctx, v, f, g->d_a, MG_CAT(cap_of3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift, dev_work,
+                                                   dev_sumsq, mg->bc);
     if (MG_CAT(has_coef3_, R)(mg))
         return MG_CAT(mgx3dxs_residual_coef_bc_, R)(mg->ctx, v, f, g->d_a, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc);
     if (mg->shift != 0 || mg->bc) /* (with a mask the plain Laplacian is the shifted operator with s = 0) */
@@ -307,6 +346,9 @@ static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, con
  * weighted inner product (the plain Laplacian is then the shifted operator with s = 0) */
 static int MG_CAT(op_apply_dot3_, R)(MGRID* mg, const GRID* g, const REAL* p, REAL* q, double* dev_work, double* dev_sum) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    if (MG_CAT(has_cap3_, R)(mg)) /* (with bc = 0 the _bc entry is the interior entry) */
+        return MG_CAT(mgx3dxs_apply_cap_dot_bc_, R)(mg->ctx, p, g->d_a, MG_CAT(cap_of3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
+                                                    dev_sum, mg->bc);
     if (mg->bc && MG_CAT(has_coef3_, R)(mg))
         return MG_CAT(mgx3dxs_apply_coef_dot_bc_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc);
     if (mg->bc) return MG_CAT(mgx3dxs_laplace_dot_shift_bc_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc);
@@ -341,6 +383,8 @@ static int MG_CAT(get3_, R)(MGRID* mg, GRID* g, const REAL* dev, REAL* host);
 int FN(set_coefficient)(MGRID* mg, const REAL* host_a) {
     MG_REQUIRE(mg && mg->grids3D && mg->maxGrids >= 1, MGX_ERR_INVALID, "set_coefficient: NULL");
     if (!host_a) { /* back to the constant-coefficient operators */
+        MG_REQUIRE(!MG_CAT(has_cap3_, R)(mg), MGX_ERR_INVALID,
+                   "set_coefficient: the hierarchy has a capacity, which needs a coefficient: clear it first (set_capacity(NULL))");
         MG_TRY(mgx_ctx_sync(mg->ctx));
         MG_CAT(coef_free3_, R)(mg);
         return MGX_OK;
@@ -383,6 +427,59 @@ int FN(download_coefficient)(MGRID* mg, int gridID, REAL* host) {
     GRID* g = mg->grids3D[gridID];
     MG_REQUIRE(g->d_a, MGX_ERR_INVALID, "download_coefficient: the hierarchy has no coefficient");
     return MG_CAT(get3_, R)(mg, g, g->d_a, host);
+}
+
+/* The capacity (mg_multigrid.h).  The captured graphs hold the arrays of every level: every call drops them. */
+int FN(set_capacity)(MGRID* mg, const REAL* host_c) {
+    MG_REQUIRE(mg && mg->grids3D && mg->maxGrids >= 1, MGX_ERR_INVALID, "set_capacity: NULL");
+    if (!host_c) { /* back to the scalar-shift operators */
+        if (!mg->cap) return MGX_OK;
+        MG_TRY(mgx_ctx_sync(mg->ctx));
+        MG_CAT(coef_drop_graphs3_, R)(mg);
+        MG_CAT(cap_table_free3_, R)(mg);
+        return MGX_OK;
+    }
+    MG_REQUIRE(MG_CAT(has_coef3_, R)(mg), MGX_ERR_INVALID,
+               "set_capacity: a capacity needs a coefficient array: call set_coefficient first (an array of ones serves)");
+    MG_TRY(MG_CAT(coef_ok3_, R)(mg, "set_capacity"));
+    const size_t vol = MG_CAT(vol3_, R)(mg->grids3D[0]);
+    int positive = 0;
+    for (size_t i = 0; i < vol; i++) {
+        MG_REQUIRE(isfinite((double)host_c[i]) && host_c[i] >= 0, MGX_ERR_INVALID, "set_capacity: c[%zu] = %g is not finite and >= 0", i,
+                   (double)host_c[i]);
+        if (host_c[i] > 0) positive = 1;
+    }
+    MG_TRY(mgx_ctx_sync(mg->ctx)); /* (nothing of a captured cycle is in flight any more) */
+    MG_CAT(coef_drop_graphs3_, R)(mg);
+    const int had = mg->cap != NULL;
+    int st = MGX_OK;
+    if (!had) { /* first use: one array per level, pads zero */
+        mg->cap = calloc(1, sizeof(CAPTAB));
+        MG_REQUIRE(mg->cap, MGX_ERR_NOMEM, "set_capacity: out of host memory");
+        for (int i = 0; !st && i < mg->maxGrids; i++) {
+            const size_t bytes = MG_CAT(dvol3_, R)(mg->layout, mg->grids3D[i]) * sizeof(REAL);
+            st = mgx_malloc(mg->ctx, bytes, (void**)&((CAPTAB*)mg->cap)->d_c[i]);
+            if (!st) st = mgx_memset_zero(mg->ctx, ((CAPTAB*)mg->cap)->d_c[i], bytes);
+        }
+    }
+    CAPTAB* t = (CAPTAB*)mg->cap;
+    if (!st) st = MG_CAT(put3_, R)(mg, mg->grids3D[0], t->d_c[0], host_c);
+    for (int i = 0; !st && i + 1 < mg->maxGrids; i++) { /* c_{l+1} = Restrict(c_l) by the step's mask, as the coefficient goes down */
+        GRID *fine = mg->grids3D[i], *coarse = mg->grids3D[i + 1];
+        if (mg->coarsen[i] != 7) st = MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, t->d_c[i], fine->sizeXYZ, t->d_c[i + 1], coarse->sizeXYZ);
+        else st = MG_CAT(mgx3dxs_restrict_, R)(mg->ctx, t->d_c[i], fine->sizeXYZ, t->d_c[i + 1], coarse->sizeXYZ);
+    }
+    if (!st) st = mgx_ctx_sync(mg->ctx);
+    if (!st) t->positive = positive;
+    if (st && !had) MG_CAT(cap_table_free3_, R)(mg); /* nothing half-built stays behind */
+    return st;
+}
+
+int FN(download_capacity)(MGRID* mg, int gridID, REAL* host) {
+    MG_REQUIRE(mg && gridID >= 0 && gridID < mg->maxGrids, MGX_ERR_INVALID, "download_capacity: bad gridID %d", gridID);
+    MG_REQUIRE(host, MGX_ERR_INVALID, "download_capacity: NULL");
+    MG_REQUIRE(mg->cap, MGX_ERR_INVALID, "download_capacity: the hierarchy has no capacity");
+    return MG_CAT(get3_, R)(mg, mg->grids3D[gridID], ((CAPTAB*)mg->cap)->d_c[gridID], host);
 }
 
 /* the mask of the Neumann faces (mg_multigrid.h).  The captured graphs are dropped whenever it changes. */
@@ -446,6 +543,9 @@ int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
     MG_TRY(MG_CAT(op_ok3_, R)(mg, curGrid, "Relax"));
     /* the coefficient and the shifted operator: one launch per colour pass; d_e is not used */
     if (mg->bc) MG_CAT(v_touched3_, R)(mg, curGrid->d_v); /* with a mask each colour pass is followed by its launch over the face unknowns */
+    if (MG_CAT(has_cap3_, R)(mg))
+        return MG_CAT(mgx3dxs_relax_cap_bc_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(cap_of3_, R)(mg, curGrid),
+                                                curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc);
     if (MG_CAT(has_coef3_, R)(mg))
         return MG_CAT(mgx3dxs_relax_coef_bc_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift, ncycles,
                                                  mg->bc);
@@ -509,6 +609,7 @@ static int MG_CAT(vcycle_graph3_, R)(MGRID* mg, int gridID, int v1, int v2, int 
     s.matrixA_bits[1] = (unsigned long long)(uintptr_t)mg->grids3D[0]->d_a; /* level 0's coefficient array (0 without one): setting or */
                                                                             /* clearing it captures again, new values in it are read  */
     s.matrixA_bits[2] = (unsigned long long)mg->bc; /* the mask of the Neumann faces (0 without one) */
+    s.matrixA_bits[3] = (unsigned long long)(uintptr_t)(mg->cap ? ((CAPTAB*)mg->cap)->d_c[0] : NULL); /* level 0's capacity array */
     MG_TRY(mgx_ctx_generation(mg->ctx, &s.generation));
     for (int k = 0; k < 3; k++)
         for (int i = gridID; i < mg->numGrids; i++) s.flags.a[k][i] = flags[k][i];
@@ -579,7 +680,10 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
     const int bc = mg->bc; /* Neumann faces: no from-zero shortcut (v := 0 on all points, then Relax), the stored-residual route */
     if (!bc && v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
         if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
-        if (coef)
+        if (MG_CAT(has_cap3_, R)(mg))
+            MG_TRY(MG_CAT(mgx3dxs_relax_cap_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, ((CAPTAB*)mg->cap)->d_c[gridID],
+                                                           fine->sizeXYZ, h, mg->shift, v1, mg->v_rim_zero[gridID]));
+        else if (coef)
             MG_TRY(MG_CAT(mgx3dxs_relax_coef_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, fine->sizeXYZ, h, mg->shift, v1,
                                                             mg->v_rim_zero[gridID]));
         else
@@ -864,7 +968,10 @@ static int MG_CAT(pcg_precond3_, R)(MGRID* mg, int v1, int v2) {
 static int MG_CAT(pcg_true_sumsq3_, R)(MGRID* mg, const REAL* x, const REAL* b, double* ss) {
     GRID* g = mg->grids3D[0];
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
-    if (g->d_a)
+    if (MG_CAT(has_cap3_, R)(mg))
+        MG_TRY(MG_CAT(mgx3dxs_residual_cap_bc_, R)(mg->ctx, x, b, g->d_a, ((CAPTAB*)mg->cap)->d_c[0], NULL, g->sizeXYZ, h, mg->shift,
+                                                   mg->pcg_work, mg->pcg_state + MGX_CG_RR, mg->bc));
+    else if (g->d_a)
         MG_TRY(MG_CAT(mgx3dxs_residual_coef_bc_, R)(mg->ctx, x, b, g->d_a, NULL, g->sizeXYZ, h, mg->shift, mg->pcg_work,
                                                     mg->pcg_state + MGX_CG_RR, mg->bc));
     else if (mg->shift != 0 || mg->bc) /* (with a mask: over all unknowns, unweighted) */
@@ -1029,6 +1136,8 @@ int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* i
                "PCG: bad arguments (tol %g, maxit %d, v1 %d, v2 %d)", tol, maxit, v1, v2);
     MG_TRY(MG_CAT(shift_ok3_, R)(mg, mg->shift, "PCG"));
     if (MG_CAT(has_coef3_, R)(mg)) MG_TRY(MG_CAT(coef_ok3_, R)(mg, "PCG"));
+    MG_REQUIRE(!MG_CAT(has_cap3_, R)(mg) || MG_CAT(has_coef3_, R)(mg), MGX_ERR_INVALID, "PCG: a capacity needs a coefficient (set_coefficient)");
+    MG_TRY(MG_CAT(cap_singular3_, R)(mg, "PCG")); /* (not solved in the projected sense: its null space is not the shift's) */
     MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "PCG"));
     const int weighted = krylov == MG_KRYLOV_WEIGHTED;
     if (!weighted) MG_TRY(MG_CAT(bc_singular3_, R)(mg, "PCG")); /* (krylov = 2 solves the closed box without a shift, projected) */
@@ -1078,7 +1187,10 @@ int FN(BackwardEuler)(MGRID* mg, int nsteps, double dt, double kappa, const REAL
         double rel = 0.0;
         /* the unknowns only: the Dirichlet entries of d_f[0] are read by nobody and stay as they are (f_rim_zero too, without a mask) */
         if (mg->bc) mg->f_rim_zero[0] = 0;
-        MG_TRY(MG_CAT(mgx3dxs_shift_rhs_bc_, R)(mg->ctx, g->d_v, d_source, qscale, s, g->d_f, g->sizeXYZ, mg->bc));
+        if (MG_CAT(has_cap3_, R)(mg)) /* c u_t = kappa div(a grad u) + q: the old u enters weighted by the capacity */
+            MG_TRY(MG_CAT(mgx3dxs_cap_rhs_bc_, R)(mg->ctx, g->d_v, ((CAPTAB*)mg->cap)->d_c[0], d_source, qscale, s, g->d_f, g->sizeXYZ, mg->bc));
+        else
+            MG_TRY(MG_CAT(mgx3dxs_shift_rhs_bc_, R)(mg->ctx, g->d_v, d_source, qscale, s, g->d_f, g->sizeXYZ, mg->bc));
         MG_TRY(FN(PCG)(mg, v1, v2, tol, maxit, krylov, &it, &rel, &conv, NULL, 0));
         *iters_total += it;
         if (rel > *worst_rel_res || !(rel == rel)) *worst_rel_res = rel;
@@ -1138,6 +1250,7 @@ int MG_CAT(mg3d_solve_from_zero_, R)(mgx_ctx* ctx, REAL* grid_out, const REAL* r
     return MG_CAT(solve3_, R)(ctx, grid_out, rhs, sizeXYZ, range, nlevels, fmg, v0, v1, v2, ncycles, residual_mode, 1);
 }
 
+#undef CAPTAB
 #undef GRID
 #undef MGRID
 #undef FN

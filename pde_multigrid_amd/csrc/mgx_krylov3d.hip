@@ -22,7 +22,7 @@ namespace mgx {
 // sign of a zero residual)
 template <class real>
 struct PlainOp {
-    static constexpr bool HAS_A = false, HAS_S = false;
+    static constexpr bool HAS_A = false, HAS_S = false, HAS_C = false;
     real qx, qy, qz;  // as mgx3dxs_residual forms them: residual_scale's, MODE 1, or 3 with exact reciprocals
     int mode;
     PlainOp(const mgx_ctx* ctx, const real h[3], real) {

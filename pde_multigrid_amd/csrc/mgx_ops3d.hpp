@@ -1,7 +1,8 @@
 // mgx_ops3d.hpp -- the operator policies of mgx_stencil3d.hpp that more than one file instantiates: ShiftOp, (Laplacian - s) u = f
-// (its arithmetic is described in mgx_shift3d.hip), and CoefOp, div(a grad u) - s u = f (mgx_coef3d.hip,
-// section 14).  mgx_shift3d.hip and mgx_coef3d.hip build the interior kernels from them, mgx_rim3d.hip the kernels of the
-// Neumann faces (section 15): the point expressions exist once.
+// (its arithmetic is described in mgx_shift3d.hip), CoefOp, div(a grad u) - s u = f (mgx_coef3d.hip,
+// section 14), and CapOp, div(a grad u) - (s c) u = f with a capacity c at every node (mgx_cap3d.hip, section 17).
+// mgx_shift3d.hip and mgx_coef3d.hip build the interior kernels from the first two, mgx_rim3d.hip their kernels of the Neumann faces
+// (section 15), mgx_cap3d.hip both kinds for CapOp: the point expressions exist once.
 #pragma once
 #include "mgx_stencil3d.hpp"
 
@@ -24,7 +25,7 @@ __device__ __forceinline__ real relax_shift3d_point(real O, real E, real N, real
 // den and, for fp32's route, rd = 1 / den in double are the same for every point of a level
 template <class real>
 struct ShiftOp {
-    static constexpr bool HAS_A = false, HAS_S = true;
+    static constexpr bool HAS_A = false, HAS_S = true, HAS_C = false;
     static constexpr const char *relax_kernel = "relax_shift3d_xs_kernel", *zero_kernel = "relax_shift_zero3d_xs_kernel";
     real hx2, hy2, hz2, den;  // the smoother's
     double rd;
@@ -73,7 +74,7 @@ __device__ __forceinline__ real residual_coef3d_point(real O, real E, real N, re
 // qx = (real)0.5 / hx2 .. : half the reciprocal squared spacings (the 1/2 of the face means)
 template <class real>
 struct CoefOp {
-    static constexpr bool HAS_A = true, HAS_S = true;
+    static constexpr bool HAS_A = true, HAS_S = true, HAS_C = false;
     static constexpr const char *relax_kernel = "relax_coef3d_xs_kernel", *zero_kernel = "relax_coef_zero3d_xs_kernel";
     static constexpr int mode = 1;  // (the expressions divide by nothing the host could invert: one MODE)
     real qx, qy, qz, s;
@@ -95,6 +96,40 @@ struct CoefOp {
     template <int MODE>
     __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a) const {
         return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, s);
+    }
+};
+
+// div(a grad u) - (s c) u = f: CoefOp's expressions with sc = s * c_P, one rounding in `real`, where they take s.  c is the
+// capacity at the updated point only (f's index), read through the policy: the kernels of the other policies take no further
+// argument.  c == 1 gives CoefOp's bits (s * 1 = s).
+template <class real>
+struct CapOp {
+    static constexpr bool HAS_A = true, HAS_S = true, HAS_C = true;
+    static constexpr const char *relax_kernel = "relax_cap3d_xs_kernel", *zero_kernel = "relax_cap_zero3d_xs_kernel";
+    static constexpr int mode = 1;
+    real qx, qy, qz, s;
+    const real* c;  // the level's capacity array (never written)
+    CapOp(const mgx_ctx*, const real h[3], real s_, const real* c_) : s(s_), c(c_) {
+        const real hx2 = h[0] * h[0], hy2 = h[1] * h[1], hz2 = h[2] * h[2];
+        qx = (real)0.5 / hx2;
+        qy = (real)0.5 / hy2;
+        qz = (real)0.5 / hz2;
+    }
+    // "relax3d.rows" below 4 lowers the rows per lane, as for CoefOp.  fp64 with four rows: 132 VGPRs, three waves per SIMD, 638 us
+    // per colour pass at 513^3; with two: 78, six waves, 658 us -- four stays the default
+    static int rows(const mgx_ctx* ctx) { return ctx->relax_rows < 4 ? ctx->relax_rows : 4; }
+    template <class F>
+    static void with_mode(int, F&& f) {
+        f(std::integral_constant<int, 1>());
+    }
+    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>& a, real cP) const {
+        const real sc = s * cP;
+        return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, sc);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a, real cP) const {
+        const real sc = s * cP;
+        return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, sc);
     }
 };
 

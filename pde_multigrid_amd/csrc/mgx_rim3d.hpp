@@ -1,0 +1,251 @@
+// mgx_rim3d.hpp -- what the kernels of the Neumann faces (mgx_rim3d.hip) share with a unit that builds them for
+// an operator policy of its own (mgx_cap3d.hip): the list of face points, the reflected star, the rim kernels that take a policy and
+// their host drivers.  Everything else of the faces -- the transfers, the vector kernels of the solve -- is in mgx_rim3d.hip.
+#pragma once
+#include "mgx_ops3d.hpp"
+
+namespace mgx {
+
+typedef unsigned long long u64;
+
+// the list of face points of a grid: the faces in the order z-low, z-high, y-low, y-high, x-low, x-high, end[k] = the number of
+// listed points of the faces 0 .. k (a face whose bit is clear lists none)
+// -- in 32 bits, so that a thread finds its point with 32-bit divisions: a grid whose list is longer is MGX_ERR_SIZE
+struct Rim {
+    int sx, sy, sz, bc;
+    unsigned end[6];
+};
+
+template <class real>
+static int rim_list(const int n[3], int bc, const char* what, Rim& r) {
+    r.sx = n[0], r.sy = n[1], r.sz = n[2], r.bc = bc;
+    const u64 P = (u64)Geo<XSplit, real>(n[0], n[1]).P;
+    const u64 cnt[6] = {P * (u64)n[1], P * (u64)n[1], P * (u64)(n[2] - 2), P * (u64)(n[2] - 2), (u64)(n[1] - 2) * (u64)(n[2] - 2),
+                        (u64)(n[1] - 2) * (u64)(n[2] - 2)};
+    const int bit[6] = {4, 5, 2, 3, 0, 1};
+    u64 acc = 0;
+    for (int k = 0; k < 6; k++) {
+        if ((bc >> bit[k]) & 1) acc += cnt[k];
+        MGX_REQUIRE(acc < 0xffffffffull, MGX_ERR_SIZE, "%s: %llu face points are too many", what, acc);
+        r.end[k] = (unsigned)acc;
+    }
+    return MGX_OK;
+}
+
+constexpr int RIM_THREADS = 256;
+constexpr int RIM_MAX_BLOCKS = 4096;
+static unsigned rim_blocks(const Rim& r) {
+    const u64 b = ((u64)r.end[5] + RIM_THREADS - 1) / RIM_THREADS;
+    return (unsigned)(b < 1 ? 1 : b > RIM_MAX_BLOCKS ? RIM_MAX_BLOCKS : b);
+}
+
+// i reflected into [0, n) for -1 <= i <= n
+__device__ __forceinline__ int rim_reflect(int i, int n) { return i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i; }
+
+// point t of the list: its coordinates; false for a pad position and for a point that is no unknown
+template <class real>
+__device__ __forceinline__ bool rim_point(const Rim& R, const Geo<XSplit, real>& g, unsigned t, int& x, int& y, int& z) {
+    int k = 0;
+    while (k < 5 && t >= R.end[k]) k++;
+    const unsigned u = t - (k ? R.end[k - 1] : 0);
+    if (k < 4) {  // whole rows: storage position j of row u / P
+        const unsigned row = u / (unsigned)g.P;
+        x = xs_x((int)(u - row * (unsigned)g.P), g.H);
+        if (x >= R.sx) return false;
+        if (k < 2) y = (int)row, z = k == 0 ? 0 : R.sz - 1;
+        else y = k == 2 ? 0 : R.sy - 1, z = 1 + (int)row;
+    } else {
+        const unsigned q = u / (unsigned)(R.sy - 2);
+        x = k == 4 ? 0 : R.sx - 1, y = 1 + (int)(u - q * (unsigned)(R.sy - 2)), z = 1 + (int)q;
+    }
+    const int on = (x == 0) | (x == R.sx - 1) << 1 | (y == 0) << 2 | (y == R.sy - 1) << 3 | (z == 0) << 4 | (z == R.sz - 1) << 5;
+    return (on & ~R.bc) == 0;
+}
+
+// the reflected star of p around (x, y, z) (C: the centre too)
+template <class real, bool C>
+__device__ __forceinline__ Star7<real> rim_star(const real* __restrict__ p, const Geo<XSplit, real>& g, const Rim& R, int x, int y, int z) {
+    const int xm = rim_reflect(x - 1, R.sx), xp = rim_reflect(x + 1, R.sx);
+    const int ym = rim_reflect(y - 1, R.sy), yp = rim_reflect(y + 1, R.sy);
+    const int zm = rim_reflect(z - 1, R.sz), zp = rim_reflect(z + 1, R.sz);
+    const size_t row = g.row(y, z);
+    const int j = g.pos(x);
+    Star7<real> s;
+    s.O = p[row + g.pos(xm)];
+    s.E = p[row + g.pos(xp)];
+    s.N = p[g.row(ym, z) + j];
+    s.S = p[g.row(yp, z) + j];
+    s.D = p[g.row(y, zm) + j];
+    s.U = p[g.row(y, zp) + j];
+    s.C = C ? p[row + j] : (real)0;
+    return s;
+}
+
+#define RIM_FOR_EACH_POINT(R, g, x, y, z)                                                                                  \
+    for (u64 t_ = (u64)blockIdx.x * RIM_THREADS + threadIdx.x; t_ < (R).end[5]; t_ += (u64)gridDim.x * RIM_THREADS)        \
+        if (int x, y, z; rim_point<real>(R, g, (unsigned)t_, x, y, z))
+
+// one colour pass on the face unknowns
+template <class real, class Op>
+__global__ void __launch_bounds__(RIM_THREADS) rim_relax3d_xs_kernel(real* __restrict__ v, const real* __restrict__ f, const real* __restrict__ a,
+                                                                     Rim R, Op op, int colour) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        if (((x + y + z) & 1) != colour) continue;
+        const size_t i = g.row(y, z) + g.pos(x);
+        const Star7<real> vs = rim_star<real, false>(v, g, R, x, y, z);
+        Star7<real> as = {};
+        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
+        if constexpr (Op::HAS_C) v[i] = op.relax(vs, f[i], as, op.c[i]);  // (the capacity of the point itself: nothing mirrored)
+        else v[i] = op.relax(vs, f[i], as);
+    }
+}
+
+// r on the face unknowns (out == NULL: not stored) and the block's partial of its squares (partial == NULL: none): per thread in
+// list order, wavefront-wide shuffles, the four waves in a fixed order -- the same bits on every run
+template <class real, class Op, int MODE>
+__global__ void __launch_bounds__(RIM_THREADS) rim_residual3d_xs_kernel(const real* __restrict__ v, const real* __restrict__ f,
+                                                                        const real* __restrict__ a, real* __restrict__ out, Rim R, Op op,
+                                                                        double* __restrict__ partial) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    double acc = 0.0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const size_t i = g.row(y, z) + g.pos(x);
+        const Star7<real> vs = rim_star<real, true>(v, g, R, x, y, z);
+        Star7<real> as = {};
+        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
+        real t;
+        if constexpr (Op::HAS_C) t = op.template residual<MODE>(vs, f[i], as, op.c[i]);
+        else t = op.template residual<MODE>(vs, f[i], as);
+        if (out) out[i] = t;
+        acc += (double)t * (double)t;
+    }
+    if (partial) {  // (uniform over the launch)
+        __shared__ double part[RIM_THREADS / 64];
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) partial[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+    }
+}
+
+// ------------------------------------------------------------------ the operator of the solve on the face unknowns (section 16)
+// The flexible CG of a hierarchy with a mask works in the inner product <a, b>_W = sum of W a b over all unknowns, W = 1/2 per
+// Neumann face an unknown lies on (the trapezoid weights A is symmetric in), 1 in the interior: the interior kernels of
+// mgx_krylov3d.hip run unchanged and the kernels here add the face unknowns' terms, their block partials behind the interior
+// launch's (the vector kernels: mgx_rim3d.hip).  W is a power of two: a weighted term is the unweighted one, rescaled exactly.
+__device__ __forceinline__ double rim_weight(const Rim& R, int x, int y, int z) {
+    const int faces = (x == 0 || x == R.sx - 1) + (y == 0 || y == R.sy - 1) + (z == 0 || z == R.sz - 1);
+    return faces == 1 ? 0.5 : faces == 2 ? 0.25 : 0.125;
+}
+
+// the block's sum of acc into *partial: per thread in list order, wavefront-wide shuffles, the four waves in a fixed order
+__device__ __forceinline__ void rim_block_sum(double acc, double* part, double* __restrict__ partial) {
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) *partial = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// q = A p = -(op's residual of (p, 0)) on the reflected star, partials of <p, q>_W
+template <class real, class Op, int MODE>
+__global__ void __launch_bounds__(RIM_THREADS) rim_apply_dot3d_xs_kernel(const real* __restrict__ p, const real* __restrict__ a,
+                                                                         real* __restrict__ q, Rim R, Op op, double* __restrict__ partial) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    double acc = 0.0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const Star7<real> vs = rim_star<real, true>(p, g, R, x, y, z);
+        Star7<real> as = {};
+        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
+        const size_t i = g.row(y, z) + g.pos(x);
+        real t;
+        if constexpr (Op::HAS_C) t = -op.template residual<MODE>(vs, (real)0, as, op.c[i]);
+        else t = -op.template residual<MODE>(vs, (real)0, as);  // negation is exact
+        q[i] = t;
+        acc += rim_weight(R, x, y, z) * ((double)vs.C * (double)t);
+    }
+    __shared__ double part[RIM_THREADS / 64];
+    rim_block_sum(acc, part, partial + blockIdx.x);
+}
+
+// =========================================================================== host side
+#define RIM_BC_CHECK(bc, what) MGX_REQUIRE((bc) >= 0 && (bc) <= 63, MGX_ERR_INVALID, "%s: bc = %d is outside 0 .. 63", what, bc)
+
+// ncycles red+black sweeps, each colour pass the interior launch and the rim launch of that colour
+template <class Op, class real>
+static int relax_op3d_bc(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int bc,
+                         const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h, MGX_ERR_INVALID, "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    if (!bc) return relax_op3d<Op, real>(ctx, v, f, a, n, h, s, ncycles, 0, 0, what, c);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd, false));
+    MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "%s: ncycles = %d < 0", what, ncycles);
+    MGX_USE(ctx);
+    const Op op = make_op<Op, real>(ctx, h, s, c);
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    for (int p = 0; p < 2 * ncycles; p++) {
+        relax_op3d_pass<Op, real>(ctx, v, f, a, n, op, p & 1);
+        MGX_LAUNCH((rim_relax3d_xs_kernel<real, Op>), dim3(rim_blocks(R)), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, R, op, p & 1);
+    }
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
+// r = the residual on all unknowns, 0 on the Dirichlet points (r == NULL: not stored); *dev_sumsq = the sum of its squares over all
+// unknowns (NULL: none).  The rim launch has at most as many blocks as the interior launch has partials: the work array of
+// mgx3dxs_krylov_work_elems doubles, twice that count, holds both.
+template <class Op, class real>
+static int residual_op3d_bc(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3], const real h[3], real s,
+                            double* dev_work, double* dev_sumsq, int bc, const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h && (r || dev_sumsq) && (!dev_sumsq || dev_work), MGX_ERR_INVALID,
+                "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    if (!bc) return residual_op3d<Op, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, what, c);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd));
+    MGX_USE(ctx);
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    if (r)  // every boundary point first: the Dirichlet points keep the 0
+        rim_zero3d_xs<real>(ctx, r, n);
+    const Op op = make_op<Op, real>(ctx, h, s, c);
+    MGX_TRY_RET((residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, op, dev_work, dev_sumsq, false)));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    unsigned nb = rim_blocks(R);
+    if (dev_sumsq && nb > interior) nb = (unsigned)interior;
+    Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
+        MGX_LAUNCH((rim_residual3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, r, R, op,
+                   dev_sumsq ? dev_work + interior : (double*)nullptr);
+    });
+    MGX_LAUNCH_CHECK();
+    return dev_sumsq ? krylov_final(ctx, dev_work, interior + nb, 1, dev_sumsq) : MGX_OK;
+}
+
+template <class Op, class real>
+static int apply_op_dot3d_bc(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3], real s, double* dev_work,
+                             double* dev_sum, int bc, const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && p && (a || !Op::HAS_A) && (c || !Op::HAS_C) && q && n && h && dev_work && dev_sum, MGX_ERR_INVALID, "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    if (!bc) return apply_op_dot3d<Op, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, what, c);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd));
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    MGX_USE(ctx);
+    const Op op = make_op<Op, real>(ctx, h, s, c);
+    MGX_TRY_RET((residual_op3d_launch<Op, true>(ctx, p, (const real*)nullptr, a, q, n, op, dev_work, dev_sum, false)));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    const unsigned nb = rim_blocks(R);
+    Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
+        MGX_LAUNCH((rim_apply_dot3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, p, a, q, R, op,
+                   dev_work + interior);
+    });
+    MGX_LAUNCH_CHECK();
+    return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
+}
+
+}  // namespace mgx

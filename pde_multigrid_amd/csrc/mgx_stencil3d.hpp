@@ -4,11 +4,15 @@
 //   PlainOp  (mgx_krylov3d.hip)  the CORRECT-mode Laplacian                         q = A p only
 //   ShiftOp  (mgx_ops3d.hpp)     (Laplacian - s) u = f                             DESIGN.md section 13
 //   CoefOp   (mgx_ops3d.hpp)     div(a grad u) - s u = f, a at the grid nodes      DESIGN.md section 14
+//   CapOp    (mgx_ops3d.hpp)     div(a grad u) - (s c) u = f, c at the grid nodes  DESIGN.md section 17
 // A policy holds
 //   Op(ctx, h, s)                          the operator's scalars for a level with spacings h, formed by the host once per call
-//   HAS_A, HAS_S                           does it read a coefficient array / take a shift (checked to be finite and >= 0)
-//   relax(v, f, a)                         the smoother's point expression (v.C is not read)
-//   residual<MODE>(v, f, a), with_mode()   the residual's point expression and the MODEs the host picks from (op.mode)
+//                                          (with HAS_C: Op(ctx, h, s, c), and op.c is the capacity array)
+//   HAS_A, HAS_S, HAS_C                    does it read a coefficient array / take a shift (checked to be finite and >= 0) / read
+//                                          a capacity at the updated point
+//   relax(v, f, a)                         the smoother's point expression (v.C is not read); with HAS_C relax(v, f, a, cP)
+//   residual<MODE>(v, f, a), with_mode()   the residual's point expression (with HAS_C a fourth argument cP) and the MODEs the
+//                                          host picks from (op.mode)
 //   rows(ctx), relax_kernel, zero_kernel   the colour pass: its rows per lane and the names last_relax_kernel() reports
 // and keeps its arithmetic to itself: all in `real`, left to right as written there, nothing contracted.
 #pragma once
@@ -79,7 +83,7 @@ __global__ void __launch_bounds__(256) residual_op3d_xs_kernel(const real* __res
         const size_t row = g.row(y, z);
         for (int j0 = 0; j0 < P; j0 += KSTEP) {
             Star7<real> vs[KJ], as[KJ];  // (as: with Op::HAS_A)
-            real fv[KJ];
+            real fv[KJ], cv[KJ];  // (cv: with Op::HAS_C)
             bool in[KJ];
 #pragma unroll
             for (int k = 0; k < KJ; k++) {
@@ -99,12 +103,15 @@ __global__ void __launch_bounds__(256) residual_op3d_xs_kernel(const real* __res
                     load(vs[k].U, as[k].U, i + PL);
                     load(vs[k].C, as[k].C, i);
                     fv[k] = LAP ? (real)0 : f[i];
+                    if constexpr (Op::HAS_C) cv[k] = op.c[i];
                 }
             }
 #pragma unroll
             for (int k = 0; k < KJ; k++)
                 if (in[k]) {
-                    real t = op.template residual<MODE>(vs[k], fv[k], as[k]);
+                    real t;
+                    if constexpr (Op::HAS_C) t = op.template residual<MODE>(vs[k], fv[k], as[k], cv[k]);
+                    else t = op.template residual<MODE>(vs[k], fv[k], as[k]);
                     if (LAP) t = -t;  // negation is exact
                     if (LAP || out) out[row + j0 + k * 64 + threadIdx.x] = t;
                     acc += LAP ? (double)vs[k].C * (double)t : (double)t * (double)t;
@@ -128,7 +135,8 @@ __global__ void __launch_bounds__(256) residual_op3d_xs_kernel(const real* __res
 // registers: a_c (half q_r) and a_x (half 1 - q_r) at plane z, a_d = the own column at z-1 (the a_x of the step before), and per
 // step BOTH entries at z+1 are loaded (a_uc, a_ux) -- 1.0 word per point of a.  aN / aS are the a_x of the rows above / below
 // (their parity is the opposite one), the two edge rows come from cache, the side value by shuffle exactly as v's.  Without
-// HAS_A none of this exists.
+// HAS_A none of this exists.  With Op::HAS_C the capacity is read at the updated point alone, with f's index: one more streaming
+// load per step and row (3.0 words per point and pass against 2.5), nothing marched.
 template <class real, class Op, int TYW, int R>
 __global__ void __launch_bounds__(64 * TYW)
     relax_op3d_xs_kernel(const real* __restrict__ vin, real* __restrict__ vout, const real* __restrict__ f, const real* __restrict__ a, int sx,
@@ -166,12 +174,13 @@ __global__ void __launch_bounds__(64 * TYW)
         }
     }
     for (int z = z0; z < z1; z++) {
-        real U[R], side[R], fv[R], a_uc[RA], a_ux[RA], a_side[RA];
+        real U[R], side[R], fv[R], a_uc[RA], a_ux[RA], a_side[RA], cv[Op::HAS_C ? R : 1];
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int hq = (q ^ (r & 1)) * H;
             U[r] = vin[rowb[r] + sxy + hq + j];
             fv[r] = f[rowb[r] + hq + j];
+            if constexpr (Op::HAS_C) cv[r] = op.c[rowb[r] + hq + j];
             if constexpr (Op::HAS_A) {
                 a_uc[r] = a[rowb[r] + sxy + hq + j];
                 a_ux[r] = a[rowb[r] + sxy + (H - hq) + j];
@@ -217,7 +226,9 @@ __global__ void __launch_bounds__(64 * TYW)
                 as.U = a_uc[r];
                 as.C = a_c[r];
             }
-            const real out = op.relax(vs, fv[r], as);
+            real out;
+            if constexpr (Op::HAS_C) out = op.relax(vs, fv[r], as, cv[r]);
+            else out = op.relax(vs, fv[r], as);
             if ((qr | j) && r < nrows) __builtin_nontemporal_store(out, &vout[rowb[r] + qr * H + j]);  // x = 2j+q_r >= 1
         }
 #pragma unroll
@@ -250,11 +261,18 @@ __global__ void __launch_bounds__(256) relax_op_zero3d_xs_kernel(real* __restric
     Star7<real> as = {};
     if constexpr (Op::HAS_A)
         as = {a[row + g.pos(x - 1)], a[row + g.pos(x + 1)], a[idx - g.P], a[idx + g.P], a[idx - g.PL], a[idx + g.PL], a[idx]};
-    __builtin_nontemporal_store(op.relax(Star7<real>{}, f[idx], as), &v[idx]);
+    if constexpr (Op::HAS_C) __builtin_nontemporal_store(op.relax(Star7<real>{}, f[idx], as, op.c[idx]), &v[idx]);
+    else __builtin_nontemporal_store(op.relax(Star7<real>{}, f[idx], as), &v[idx]);
 }
 
 // =========================================================================== host side
-// `what` is the entry point's name in its error texts; `a` is NULL for an operator without a coefficient array.
+// `what` is the entry point's name in its error texts; `a` is NULL for an operator without a coefficient array, `c` for one without
+// a capacity array.
+template <class Op, class real>
+static Op make_op(const mgx_ctx* ctx, const real h[3], real s, const real* c) {
+    if constexpr (Op::HAS_C) return Op(ctx, h, s, c);
+    else return Op(ctx, h, s);
+}
 
 // one colour pass over the planes 1 .. sz-2: relax3d_xs_kernel's launch geometry (four waves of Op::rows() rows, fewer on small
 // levels; runs of four planes, halved while the launch has fewer than eight workgroups per CU, or runs of "relax3d.zchunk" planes
@@ -285,13 +303,13 @@ static void relax_op3d_pass(mgx_ctx* ctx, real* v, const real* f, const real* a,
 // ncycles red+black sweeps; from_zero: v counts as all zeros (rim_is_zero: and its boundary is zero in memory)
 template <class Op, class real>
 static int relax_op3d(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int from_zero,
-                      int rim_is_zero, const char* what) {
-    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && h, MGX_ERR_INVALID, "%s: NULL argument", what);
+                      int rim_is_zero, const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && h, MGX_ERR_INVALID, "%s: NULL argument", what);
     const double sd = (double)s;
     MGX_TRY_RET(rows_check(n, what, &sd, false));
     MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "%s: ncycles = %d < 0", what, ncycles);
     MGX_USE(ctx);
-    const Op op(ctx, h, s);
+    const Op op = make_op<Op, real>(ctx, h, s, c);
     int s0 = 0;
     if (from_zero && (!rim_is_zero || ncycles == 0)) {  // v := 0 everywhere, then generic passes
         MGX_TRY_RET(fill_zero(ctx, v, Geo<XSplit, real>(n[0], n[1]).PL * (size_t)n[2] * sizeof(real)));
@@ -323,26 +341,26 @@ static int residual_op3d_launch(mgx_ctx* ctx, const real* v, const real* f, cons
 // r = the residual (r == NULL: not stored; its boundary is 0), *dev_sumsq = <r, r> (NULL: not summed)
 template <class Op, class real>
 static int residual_op3d(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3], const real h[3], real s,
-                         double* dev_work, double* dev_sumsq, const char* what) {
-    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && h && (r || dev_sumsq) && (!dev_sumsq || dev_work), MGX_ERR_INVALID, "%s: NULL argument",
+                         double* dev_work, double* dev_sumsq, const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && h && (r || dev_sumsq) && (!dev_sumsq || dev_work), MGX_ERR_INVALID, "%s: NULL argument",
                 what);
     const double sd = (double)s;
     MGX_TRY_RET(rows_check(n, what, Op::HAS_S ? &sd : nullptr));
     MGX_USE(ctx);
     if (r)  // the boundary of r is 0, as mgx3dxs_residual leaves it
         rim_zero3d_xs<real>(ctx, r, n);
-    return residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, Op(ctx, h, s), dev_work, dev_sumsq);
+    return residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, make_op<Op, real>(ctx, h, s, c), dev_work, dev_sumsq);
 }
 
 // q = A p on the interior, *dev_sum = <p, q>
 template <class Op, class real>
 static int apply_op_dot3d(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3], real s, double* dev_work,
-                          double* dev_sum, const char* what) {
-    MGX_REQUIRE(ctx && p && (a || !Op::HAS_A) && q && h && dev_work && dev_sum, MGX_ERR_INVALID, "%s: NULL argument", what);
+                          double* dev_sum, const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && p && (a || !Op::HAS_A) && (c || !Op::HAS_C) && q && h && dev_work && dev_sum, MGX_ERR_INVALID, "%s: NULL argument", what);
     const double sd = (double)s;
     MGX_TRY_RET(rows_check(n, what, Op::HAS_S ? &sd : nullptr));
     MGX_USE(ctx);
-    return residual_op3d_launch<Op, true>(ctx, p, (const real*)nullptr, a, q, n, Op(ctx, h, s), dev_work, dev_sum);
+    return residual_op3d_launch<Op, true>(ctx, p, (const real*)nullptr, a, q, n, make_op<Op, real>(ctx, h, s, c), dev_work, dev_sum);
 }
 
 }  // namespace mgx

@@ -562,6 +562,57 @@ class _Ops3D(_Ops):
         (_, _, qo), sums = self._krylov(ctx, n, [pp, aa, qq], [], lambda w, s0, x, c, b: fn(ctx._h, x, c, b, _ip(n), h, ct(s), w, s0), dtype, 1)
         return xs_unpack(qo, n[0]), float(sums[0])
 
+    # ---- the operator with a capacity div(a grad u) - (s c) u = f (x-split only, mgx3dxs_*_cap): the _coef wrappers with c after a,
+    # and their _bc forms through bc != None
+    def relax_cap(self, ctx, v, f, a, c, n, rng, s, ncycles, bc=None, dtype=None):
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_cap" if bc is None else "relax_cap_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        tail = [] if bc is None else [C.c_int(bc)]
+        return self._run(ctx, [v, f, a, c], lambda x, b, aa, cc: fn(ctx._h, x, b, aa, cc, _ip(n), h, ct(s), C.c_int(ncycles), *tail), 0,
+                         _shape(n), dtype)
+
+    def relax_cap_from_zero(self, ctx, v, f, a, c, n, rng, s, ncycles, rim_is_zero, dtype=None):
+        """v := 0, then ncycles sweeps; with rim_is_zero the given v must have zero boundary entries (its interior is ignored)"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_cap_from_zero", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [v, f, a, c], lambda x, b, aa, cc: fn(ctx._h, x, b, aa, cc, _ip(n), h, ct(s), C.c_int(ncycles),
+                                                                    C.c_int(int(rim_is_zero))), 0, _shape(n), dtype)
+
+    def residual_cap(self, ctx, v, f, a, c, n, rng, s, bc=None, store=True, want_sum=True, dtype=None):
+        """(r, sum of squares): r None with store=False, the sum None with want_sum=False; with bc over all unknowns"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("residual_cap" if bc is None else "residual_cap_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        tail = [] if bc is None else [C.c_int(bc)]
+        arrays = [xs_pack(np.ascontiguousarray(x, dtype)) for x in (v, f, a, c)] + [xs_pack(np.zeros(_shape(n), dtype)) if store else None]
+        (_, _, _, _, ro), sums = self._krylov(ctx, n, arrays, [],
+                                              lambda w, s0, x, b, aa, cc, d: fn(ctx._h, x, b, aa, cc, d, _ip(n), h, ct(s),
+                                                                                w if want_sum else None, s0 if want_sum else None, *tail),
+                                              dtype, 1, None if bc is None else self._krylov_work_bc)
+        return (xs_unpack(ro, n[0]) if store else None), (float(sums[0]) if want_sum else None)
+
+    def apply_cap_dot(self, ctx, p, a, c, n, rng, s, bc=None, q=None, dtype=None):
+        """q = A p with A = div(a grad .) - s c, and <p, q> (with bc: at every unknown, and <p, q>_W): returns (q, pq)"""
+        dtype = dtype or p.dtype
+        fn, ct = self._fn("apply_cap_dot" if bc is None else "apply_cap_dot_bc", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        tail = [] if bc is None else [C.c_int(bc)]
+        q = np.zeros(_shape(n), dtype) if q is None else q
+        arrays = [xs_pack(np.ascontiguousarray(x, dtype)) for x in (p, a, c, q)]
+        (_, _, _, qo), sums = self._krylov(ctx, n, arrays, [], lambda w, s0, x, aa, cc, b: fn(ctx._h, x, aa, cc, b, _ip(n), h, ct(s), w, s0, *tail),
+                                           dtype, 1, None if bc is None else self._krylov_work_bc)
+        return xs_unpack(qo, n[0]), float(sums[0])
+
+    def cap_rhs(self, ctx, u, c, q, qscale, s, n, bc=None, f=None, dtype=None):
+        """f = (-((s*c)*u)) - qscale*q on the interior, with bc on all unknowns (q None: -((s*c)*u)); f: the array written into"""
+        dtype = dtype or u.dtype
+        fn, ct = self._fn("cap_rhs" if bc is None else "cap_rhs_bc", dtype)
+        tail = [] if bc is None else [C.c_int(bc)]
+        f = np.zeros(_shape(n), dtype) if f is None else f
+        return self._run(ctx, [u, c, q, f], lambda a, cc, b, d: fn(ctx._h, a, cc, b, ct(qscale), ct(s), d, _ip(n), *tail), 3, _shape(n), dtype)
+
     # ---- homogeneous Neumann faces (x-split only, mgx3dxs_*_bc): the wrappers above with the face mask bc as their last argument
     def relax_shift_bc(self, ctx, v, f, n, rng, s, ncycles, bc, dtype=None):
         dtype = dtype or v.dtype
@@ -959,7 +1010,7 @@ def _grid3_struct(ct):
         _fields_ = [("grids3D", C.POINTER(C.POINTER(Grid3D))), ("numGrids", C.c_int), ("maxGrids", C.c_int),
                     ("ctx", C.c_void_p), ("residual_mode", C.c_int), ("fuse", C.c_int), ("layout", C.c_int),
                     ("smoother", C.c_int), ("omega", ct), ("use_graph", C.c_int), ("capturing", C.c_int),
-                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 31), ("pcg_fproj", C.c_void_p),
+                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 30), ("cap", C.c_void_p), ("pcg_fproj", C.c_void_p),
                     ("f_rim_zero", C.c_ubyte * 32),
                     ("v_rim_zero", C.c_ubyte * 32), ("e_rim_valid", C.c_ubyte * 32), ("pcg_x", C.c_void_p),
                     ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
@@ -1066,12 +1117,14 @@ class MultiGrid3D(_MGBase):
     _prefix = "mgMultiGrid3D"
 
     def __init__(self, ctx, finestGridSizeXYZ, rng, dtype=np.float64, nlevels=0, residual_mode=REF_COMPAT, fuse=True,
-                 layout="xsplit", coarsening="full", shift=0.0, coefficient=None, neumann=None):
+                 layout="xsplit", coarsening="full", shift=0.0, coefficient=None, neumann=None, capacity=None):
         """coarsening="semi": every level halves only the axes with the smallest spacing (semi_plan, mg_multigrid.h) -- the
         hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count.
         shift = s >= 0: the hierarchy of (Laplacian - s) u = f (the `shift` property).
         coefficient = a > 0 at every point of the finest grid: the hierarchy of div(a grad u) - s u = f (set_coefficient).
-        neumann = six truthy values (x-low, x-high, y-low, y-high, z-low, z-high): the faces with du/dn = 0 (set_neumann)."""
+        neumann = six truthy values (x-low, x-high, y-low, y-high, z-low, z-high): the faces with du/dn = 0 (set_neumann).
+        capacity = c >= 0 at every point of the finest grid: the hierarchy of div(a grad u) - (s c) u = f (set_capacity; needs
+        a coefficient)."""
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self._sfx, self._ct = _ct(dtype)
@@ -1107,6 +1160,12 @@ class MultiGrid3D(_MGBase):
         if neumann is not None:
             try:
                 self.set_neumann(neumann)
+            except Exception:
+                self.close()
+                raise
+        if capacity is not None:
+            try:
+                self.set_capacity(capacity)
             except Exception:
                 self.close()
                 raise
@@ -1150,6 +1209,29 @@ class MultiGrid3D(_MGBase):
     def download_coefficient(self, gridID=0):
         out = np.empty(_shape(self.size(gridID)), self.dtype)
         self._call("download_coefficient", C.c_int(gridID), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def set_capacity(self, c):
+        """c: the capacity of div(a grad u) - (shift c) u = f at ALL points of level 0 (reference layout, finite and >= 0), restricted
+        down the levels as the coefficient is; every call then works with that operator, and BackwardEuler steps
+        c u_t = kappa div(a grad u) + q.  Needs a coefficient (set_coefficient first; an array of ones serves);
+        PCG(precond="f32") is not available.  None: back to the scalar shift.  New values replace the old ones in the same device
+        arrays."""
+        if c is None:
+            self._call("set_capacity", None)
+            return
+        c = np.ascontiguousarray(c, self.dtype)
+        if c.shape != _shape(self.size(0)):
+            raise ValueError("the capacity has shape %r, level 0 has %r" % (c.shape, _shape(self.size(0))))
+        self._call("set_capacity", c.ctypes.data_as(C.c_void_p))
+
+    @property
+    def has_capacity(self):
+        return bool(self._mg.contents.cap)
+
+    def download_capacity(self, gridID=0):
+        out = np.empty(_shape(self.size(gridID)), self.dtype)
+        self._call("download_capacity", C.c_int(gridID), out.ctypes.data_as(C.c_void_p))
         return out
 
     @property
@@ -1610,14 +1692,15 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
 
 
 def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full",
-                shift=0.0, coefficient=None, neumann=None):
+                shift=0.0, coefficient=None, neumann=None, capacity=None):
     """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
     precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG).
     coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call.
     shift = s > 0: the solve of (Laplacian - s) u = rhs (MultiGrid3D(shift=s)), on a hierarchy built here likewise.
     coefficient = a > 0 at every point: the solve of div(a grad u) - shift u = rhs (MultiGrid3D(coefficient=a)), likewise.
     neumann = six truthy values: the faces with du/dn = 0 (MultiGrid3D(neumann=...)), likewise; needs krylov=False or
-    krylov="weighted" (MultiGrid3D.PCG)."""
+    krylov="weighted" (MultiGrid3D.PCG).
+    capacity = c >= 0 at every point, with a coefficient: the solve of div(a grad u) - (shift c) u = rhs, likewise."""
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
     if precond not in ("f64", "f32"):
@@ -1626,9 +1709,9 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
         raise ValueError("precond='f32' needs an fp64 grid")
     if coarsening not in ("full", "semi"):
         raise ValueError("coarsening must be 'full' or 'semi', not %r" % (coarsening,))
-    if coarsening == "semi" or shift != 0 or coefficient is not None or (neumann is not None and any(neumann)):
+    if coarsening == "semi" or shift != 0 or coefficient is not None or capacity is not None or (neumann is not None and any(neumann)):
         mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening=coarsening,
-                         shift=shift, coefficient=coefficient, neumann=neumann)
+                         shift=shift, coefficient=coefficient, neumann=neumann, capacity=capacity)
         try:
             mg.upload_v(0, grid)
             if rhs is not None:
