@@ -121,7 +121,11 @@ typedef struct mgGraphFlags {
                        /* change, or the context's parameters, mgx_ctx_generation).  Default 0.       */ \
         int capturing;                                                                                   \
         void* graph_exec[MG_MAX_LEVELS];                                                                 \
-        long long graph_key[MG_MAX_LEVELS - 2]; /* unused */                                             \
+        long long graph_key[MG_MAX_LEVELS - 3]; /* unused */                                             \
+        /* internal: the walls of _set_wall (beta and g of the six faces), or NULL (none).  Owned by     */\
+        /* _set_wall, freed by _destroy.  Like cap below it takes eight bytes of the unused graph_key:   */\
+        /* every member keeps its offset and the struct its size.                                        */\
+        void* wall;                                                                                      \
         /* internal: the capacity c of div(a grad u) - (shift c) u = f, a table of one device array     */ \
         /* per level, or NULL (no capacity: the scalar-shift operators).  Owned by _set_capacity,       */ \
         /* freed by _destroy.  Like pcg_fproj below it takes eight bytes of the unused graph_key:       */ \
@@ -201,13 +205,34 @@ typedef struct mgGraphFlags {
     /* where the mask is used); all six faces with shift == 0 is singular and MGX_ERR_INVALID where the  */ \
     /* operator is used -- but PCG(krylov = 2), CG in the weighted inner product over all unknowns,     */ \
     /* solves it in the projected sense (see PCG); PCG(krylov = 1), BackwardEuler(krylov = 1) and        */ \
-    /* PCG_mixed return MGX_ERR_INVALID with a mask.  A prescribed flux g                                */ \
-    /* (du/dn = g, outward) is not an argument: subtract 2 g a / h from f at the face.  All zeros: the   */ \
+    /* PCG_mixed return MGX_ERR_INVALID with a mask.  A prescribed flux or a                             */ \
+    /* convective wall: _set_wall below.  All zeros: the                                                 */ \
     /* hierarchy is what it was without a mask.  A change of the mask drops the captured graphs and      */ \
     /* zeroes, on the levels below the finest, the entries of d_v the old mask made unknowns.  Blocking. */ \
     /* The mask is the member `bc` (bit k = neumann[k]).                                                 */ \
     int mgMultiGrid3D_##R##_set_boundary(mgMultiGrid3D_##R* mg, const int neumann[6]);                   \
     int mgMultiGrid3D_##R##_get_boundary(const mgMultiGrid3D_##R* mg, int neumann[6]);                   \
+    /* Convective (Robin) and prescribed-flux walls (an addition; mgx3dxs_*_wall of mgx.h). */\
+    /* On face k of the mask the wall law is a du/dn + beta[k] u = g[k] (n outward, beta >= 0), in the   */\
+    /* units of the hierarchy's operator div(a grad u) (a = 1 without a coefficient): beta = g = 0 is   */\
+    /* the insulated wall.  With BackwardEuler's kappa a physical kappa a du/dn + B u = G is beta = B /  */\
+    /* kappa, g = G / kappa: nothing is rescaled here.  beta enters the operator of EVERY level as the   */\
+    /* diagonal term 2 beta / h of that level's own spacing (never restricted): Relax, CalculateResidual */\
+    /* (ResidualNorm, download_residual), VCycle, FullMultiGridVCycle, PCG with krylov = 0 and 2 and     */\
+    /* BackwardEuler run the _wall entries where they ran the _bc entries.  g touches level 0's right-   */\
+    /* hand side only: _add_wall_flux subtracts 2 g / h from d_f[0] at the face unknowns (once per      */\
+    /* right-hand side: the caller's business after upload_f; BackwardEuler does it for every step).    */\
+    /* A beta > 0 makes the closed box regular: all six faces with shift == 0 (or a capacity without a  */\
+    /* positive entry) is then accepted everywhere and PCG(krylov = 2) projects nothing.  beta[k] not    */\
+    /* finite or < 0, g[k] not finite, or either != 0 on a face the mask does not flag: MGX_ERR_INVALID, */\
+    /* and _set_boundary refuses to clear a face that still carries either.  Every call syncs and drops */\
+    /* the captured graphs; all zeros frees the table, and the hierarchy is then, launch for launch and */\
+    /* bit for bit, one that never had a wall.  Everything the mask refuses stays refused; PCG_mixed     */\
+    /* returns MGX_ERR_INVALID while walls are set.  Data that vary along a face: fold 2 g(P) / h into f */\
+    /* by hand.                                                                                          */\
+    int mgMultiGrid3D_##R##_set_wall(mgMultiGrid3D_##R* mg, const real beta[6], const real g[6]);        \
+    int mgMultiGrid3D_##R##_get_wall(const mgMultiGrid3D_##R* mg, real beta[6], real g[6]);              \
+    int mgMultiGrid3D_##R##_add_wall_flux(mgMultiGrid3D_##R* mg);                                        \
     /* shift must be finite and >= 0, and a non-zero one needs the settings named at the member          */ \
     int mgMultiGrid3D_##R##_set_shift(mgMultiGrid3D_##R* mg, real shift);                                \
     size_t mgMultiGrid3D_##R##_sizeof(void); /* sizeof(mgMultiGrid3D_<r>): for mirrors of the struct */  \

@@ -749,7 +749,54 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
                                        real* q, const int n[3], const real h[3], real s,                \
                                        double* dev_work, double* dev_sum, int bc);                      \
     int mgx3dxs_cap_rhs_bc_##SFX(mgx_ctx* ctx, const real* u, const real* c, const real* q, real qscale,\
-                                 real s, real* f, const int n[3], int bc);
+                                 real s, real* f, const int n[3], int bc);                              \
+    /* ---- convective (Robin) and prescribed-flux walls, x-split layout (csrc/mgx_wall3d.hip, DESIGN.md */\
+    /* 18).  An addition.  On a face flagged in bc the wall law is a du/dn + beta u = g (n outward, beta */\
+    /* >= 0 and g constants per face, in the units of the entry's operator div(a grad u); a = 1 for the */\
+    /* shifted operator).  beta[k] and g[k] belong to the face of bit k (x-low, x-high, y-low, y-high,  */\
+    /* z-low, z-high).  The half cell at a face unknown gains 2 (g - beta u_P) / h per wall face it     */\
+    /* lies on, h the spacing along the face's axis: the operator a diagonal term, d_k = ((real)2 *     */\
+    /* beta_k) / h_axis(k), summed over the point's faces in the order x, y, z into d(P); where d(P) != */\
+    /* 0 the point is the operator's own expression with the effective shift s + d(P) (capacity: s *   */\
+    /* c_P + d(P)), the shifted smoother a plain division in `real`; where d(P) == 0 it has the bits of */\
+    /* the _bc entry.  Each _wall entry is the _bc entry of its name, argument for argument, plus      */\
+    /* `const real beta[6]` last, with that entry's contract; beta NULL, a beta[k] negative or not      */\
+    /* finite, one != 0 on a face whose bit is clear, or one so large that 2 beta / h is not finite in  */\
+    /* `real` (fp32: beyond about 1.7e38 h): MGX_ERR_INVALID.  All betas zero: the _bc                  */\
+    /* entry is called and nothing else.  bc = 63 with s = 0 is regular as soon as one beta[k] > 0.     */\
+    /* The wall launch replaces the launch over the face unknowns of the _bc entry.                     */\
+    /* wall_rhs: f[P] = f[P] - ((real)2 * g[k]) / h_axis(k) at the face unknowns, successively for the  */\
+    /* flagged faces of P with g[k] != 0 in the order x, y, z; nothing else of f is touched.  g[k] not  */\
+    /* finite or != 0 on a face whose bit is clear: MGX_ERR_INVALID.  A g that varies along a face is   */\
+    /* folded into f by the caller with the same formula, point by point.                               */\
+    int mgx3dxs_relax_shift_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3],            \
+                                       const real h[3], real s, int ncycles, int bc, const real beta[6]);\
+    int mgx3dxs_relax_coef_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,              \
+                                      const int n[3], const real h[3], real s, int ncycles, int bc,     \
+                                      const real beta[6]);                                              \
+    int mgx3dxs_relax_cap_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c,\
+                                     const int n[3], const real h[3], real s, int ncycles, int bc,      \
+                                     const real beta[6]);                                               \
+    int mgx3dxs_residual_shift_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, real* r,          \
+                                          const int n[3], const real h[3], real s, double* dev_work,    \
+                                          double* dev_sumsq, int bc, const real beta[6]);               \
+    int mgx3dxs_residual_coef_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a,     \
+                                         real* r, const int n[3], const real h[3], real s,              \
+                                         double* dev_work, double* dev_sumsq, int bc, const real beta[6]);\
+    int mgx3dxs_residual_cap_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a,      \
+                                        const real* c, real* r, const int n[3], const real h[3], real s,\
+                                        double* dev_work, double* dev_sumsq, int bc, const real beta[6]);\
+    int mgx3dxs_laplace_dot_shift_wall_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3],      \
+                                             const real h[3], real s, double* dev_work, double* dev_sum,\
+                                             int bc, const real beta[6]);                               \
+    int mgx3dxs_apply_coef_dot_wall_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q,          \
+                                          const int n[3], const real h[3], real s, double* dev_work,    \
+                                          double* dev_sum, int bc, const real beta[6]);                 \
+    int mgx3dxs_apply_cap_dot_wall_##SFX(mgx_ctx* ctx, const real* p, const real* a, const real* c,     \
+                                         real* q, const int n[3], const real h[3], real s,              \
+                                         double* dev_work, double* dev_sum, int bc, const real beta[6]);\
+    int mgx3dxs_wall_rhs_##SFX(mgx_ctx* ctx, real* f, const int n[3], const real h[3], const real g[6], \
+                               int bc);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)

@@ -211,6 +211,7 @@ int mgMultiGrid3D_f64_PCG_mixed(mgMultiGrid3D_f64* mg, int v1, int v2, double to
     MG_REQUIRE(mg->numGrids >= 1 && mg->numGrids <= mg->maxGrids, MGX_ERR_INVALID, "PCG_mixed: numGrids = %d outside [1,%d]",
                mg->numGrids, mg->maxGrids);
     MG_REQUIRE(!mg->cap, MGX_ERR_INVALID, "PCG_mixed: a hierarchy with a capacity is not supported");
+    MG_REQUIRE(!mg->wall, MGX_ERR_INVALID, "PCG_mixed: a hierarchy with wall data (set_wall) is not supported");
     MG_REQUIRE(mg->shift == 0, MGX_ERR_INVALID, "PCG_mixed: a shifted hierarchy (shift = %g) is not supported", mg->shift);
     MG_REQUIRE(!(mg->grids3D && mg->grids3D[0] && mg->grids3D[0]->d_a), MGX_ERR_INVALID,
                "PCG_mixed: a hierarchy with a coefficient is not supported");

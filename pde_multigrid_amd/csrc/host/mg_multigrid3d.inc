@@ -206,9 +206,26 @@ static void MG_CAT(cap_table_free3_, R)(MGRID* mg) {
     mg->cap = NULL;
 }
 
+/* the walls of DESIGN.md 18: mg->wall points to this table, or is NULL (no face has a beta or a g other than 0).  beta and g in the
+ * order of the mask's bits; lossy: some beta > 0 (the operator then has a zeroth-order term on a face: no closed box is singular),
+ * flux: some g != 0 */
+typedef struct MG_CAT(mgWallTable3_, R) {
+    REAL beta[6], g[6];
+    int lossy, flux;
+} MG_CAT(mgWallTable3_, R);
+#define WALLTAB MG_CAT(mgWallTable3_, R)
+
+/* the betas the operators run with: NULL without a positive one (the _bc entries then, launch for launch) */
+static const REAL* MG_CAT(wall_beta3_, R)(const MGRID* mg) {
+    const WALLTAB* t = (const WALLTAB*)mg->wall;
+    return t && t->lossy ? t->beta : NULL;
+}
+
 void FN(destroy)(MGRID* mg) {
     if (!mg) return;
     MG_CAT(cap_table_free3_, R)(mg);
+    free(mg->wall);
+    mg->wall = NULL;
     for (int i = 0; i < MG_MAX_LEVELS; i++)
         if (mg->graph_exec[i]) mgx_graph_destroy(mg->ctx, mg->graph_exec[i]);
     if (mg->pcg_graph_exec) mgx_graph_destroy(mg->ctx, mg->pcg_graph_exec);
@@ -301,12 +318,14 @@ static int MG_CAT(bc_ok3_, R)(const MGRID* mg, int bc, const char* what) {
  * shift is a public member and may still change after set_boundary).  bc_reserved is set while PCG(krylov = 2) solves that
  * system in the projected sense: its preconditioner's Relax and residual then pass. */
 static int MG_CAT(bc_singular3_, R)(const MGRID* mg, const char* what) {
+    if (MG_CAT(wall_beta3_, R)(mg)) return MGX_OK; /* a wall that loses heat makes the closed box regular */
     MG_REQUIRE(!(mg->bc == 63 && mg->shift == 0) || mg->bc_reserved, MGX_ERR_INVALID,
                "%s: Neumann data on all six faces with shift = 0 is singular (set a shift > 0 or keep a Dirichlet face)", what);
     return MGX_OK;
 }
 /* ... nor has one whose capacity has no positive entry, whatever the shift: shift * c is zero everywhere */
 static int MG_CAT(cap_singular3_, R)(const MGRID* mg, const char* what) {
+    if (MG_CAT(wall_beta3_, R)(mg)) return MGX_OK;
     MG_REQUIRE(!(mg->bc == 63 && mg->cap && !((const CAPTAB*)mg->cap)->positive), MGX_ERR_INVALID,
                "%s: Neumann data on all six faces with a capacity that has no positive entry is singular (set a capacity with a "
                "positive entry or keep a Dirichlet face)", what);
@@ -331,6 +350,15 @@ static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) 
  * *dev_sumsq (NULL: none; dev_work: the partials).  The plain operator takes mg->residual_mode and sums in a launch of its own. */
 static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, const REAL* f, REAL* r, double* dev_work, double* dev_sumsq) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    const REAL* wb = MG_CAT(wall_beta3_, R)(mg);
+    if (wb) { /* walls: the _wall entries with the level's own spacings (DESIGN.md 18) */
+        if (MG_CAT(has_cap3_, R)(mg))
+            return MG_CAT(mgx3dxs_residual_cap_wall_, R)(mg->ctx, v, f, g->d_a, MG_CAT(cap_of3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift,
+                                                         dev_work, dev_sumsq, mg->bc, wb);
+        if (MG_CAT(has_coef3_, R)(mg))
+            return MG_CAT(mgx3dxs_residual_coef_wall_, R)(mg->ctx, v, f, g->d_a, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc, wb);
+        return MG_CAT(mgx3dxs_residual_shift_wall_, R)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc, wb);
+    }
     if (MG_CAT(has_cap3_, R)(mg))
         return MG_CAT(mgx3dxs_residual_cap_bc_, R)(mg->ctx, v, f, g->d_a, MG_CAT(cap_of3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift, dev_work,
                                                    dev_sumsq, mg->bc);
@@ -346,6 +374,15 @@ static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, con
  * weighted inner product (the plain Laplacian is then the shifted operator with s = 0) */
 static int MG_CAT(op_apply_dot3_, R)(MGRID* mg, const GRID* g, const REAL* p, REAL* q, double* dev_work, double* dev_sum) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
+    const REAL* wb = MG_CAT(wall_beta3_, R)(mg);
+    if (wb) {
+        if (MG_CAT(has_cap3_, R)(mg))
+            return MG_CAT(mgx3dxs_apply_cap_dot_wall_, R)(mg->ctx, p, g->d_a, MG_CAT(cap_of3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
+                                                          dev_sum, mg->bc, wb);
+        if (MG_CAT(has_coef3_, R)(mg))
+            return MG_CAT(mgx3dxs_apply_coef_dot_wall_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc, wb);
+        return MG_CAT(mgx3dxs_laplace_dot_shift_wall_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc, wb);
+    }
     if (MG_CAT(has_cap3_, R)(mg)) /* (with bc = 0 the _bc entry is the interior entry) */
         return MG_CAT(mgx3dxs_apply_cap_dot_bc_, R)(mg->ctx, p, g->d_a, MG_CAT(cap_of3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
                                                     dev_sum, mg->bc);
@@ -490,6 +527,12 @@ int FN(set_boundary)(MGRID* mg, const int neumann[6]) {
         if (neumann[k]) bc |= 1 << k;
     if (bc == mg->bc) return MGX_OK;
     MG_TRY(MG_CAT(bc_ok3_, R)(mg, bc, "set_boundary"));
+    for (int k = 0; mg->wall && k < 6; k++) {
+        const WALLTAB* t = (const WALLTAB*)mg->wall;
+        MG_REQUIRE(((bc >> k) & 1) || (t->beta[k] == 0 && t->g[k] == 0), MGX_ERR_INVALID,
+                   "set_boundary: face %d still carries wall data (beta %g, g %g): clear them through set_wall first", k, (double)t->beta[k],
+                   (double)t->g[k]);
+    }
     MG_TRY(mgx_ctx_sync(mg->ctx)); /* (nothing of a captured cycle is in flight any more) */
     MG_CAT(coef_drop_graphs3_, R)(mg);
     /* below the finest level the entries the old mask made unknowns go back to the zeros they were before it */
@@ -506,6 +549,70 @@ int FN(get_boundary)(const MGRID* mg, int neumann[6]) {
     MG_REQUIRE(mg && neumann, MGX_ERR_INVALID, "get_boundary: NULL");
     for (int k = 0; k < 6; k++) neumann[k] = (mg->bc >> k) & 1;
     return MGX_OK;
+}
+
+/* the walls (mg_multigrid.h).  Every change drops the captured graphs: their launches hold the d_k by value. */
+int FN(set_wall)(MGRID* mg, const REAL beta[6], const REAL g[6]) {
+    MG_REQUIRE(mg && mg->grids3D && beta && g, MGX_ERR_INVALID, "set_wall: NULL");
+    MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "set_wall"));
+    int lossy = 0, flux = 0;
+    for (int k = 0; k < 6; k++) {
+        MG_REQUIRE(isfinite((double)beta[k]) && beta[k] >= 0, MGX_ERR_INVALID, "set_wall: beta[%d] = %g is not finite and >= 0", k,
+                   (double)beta[k]);
+        MG_REQUIRE(isfinite((double)g[k]), MGX_ERR_INVALID, "set_wall: g[%d] = %g is not finite", k, (double)g[k]);
+        MG_REQUIRE(((mg->bc >> k) & 1) || (beta[k] == 0 && g[k] == 0), MGX_ERR_INVALID,
+                   "set_wall: face %d has wall data (beta %g, g %g) but is not flagged in the mask %d (set_boundary first)", k, (double)beta[k],
+                   (double)g[k], mg->bc);
+        if (beta[k] > 0) lossy = 1;
+        if (g[k] != 0) flux = 1;
+        /* the terms the kernels work with, 2 beta / h on every level and 2 g / h on level 0, have to be finite in REAL */
+        for (int i = 0; i < mg->maxGrids; i++) {
+            const GRID* gl = mg->grids3D[i];
+            const REAL hk = k < 2 ? gl->h_x : k < 4 ? gl->h_y : gl->h_z;
+            MG_REQUIRE(isfinite((double)(((REAL)2 * beta[k]) / hk)), MGX_ERR_INVALID,
+                       "set_wall: 2 * beta[%d] / h = 2 * %g / %g is not finite in this precision on level %d", k, (double)beta[k], (double)hk, i);
+            MG_REQUIRE(i || isfinite((double)(((REAL)2 * g[k]) / hk)), MGX_ERR_INVALID,
+                       "set_wall: 2 * g[%d] / h = 2 * %g / %g is not finite in this precision", k, (double)g[k], (double)hk);
+        }
+    }
+    if (!lossy && !flux && !mg->wall) return MGX_OK;
+    MG_TRY(mgx_ctx_sync(mg->ctx)); /* (nothing of a captured cycle is in flight any more) */
+    MG_CAT(coef_drop_graphs3_, R)(mg);
+    if (!lossy && !flux) { /* all zeros: the hierarchy is one that never had a wall */
+        free(mg->wall);
+        mg->wall = NULL;
+        return MGX_OK;
+    }
+    if (!mg->wall) mg->wall = calloc(1, sizeof(WALLTAB));
+    MG_REQUIRE(mg->wall, MGX_ERR_NOMEM, "set_wall: out of host memory");
+    WALLTAB* t = (WALLTAB*)mg->wall;
+    memcpy(t->beta, beta, sizeof t->beta);
+    memcpy(t->g, g, sizeof t->g);
+    t->lossy = lossy;
+    t->flux = flux;
+    return MGX_OK;
+}
+
+int FN(get_wall)(const MGRID* mg, REAL beta[6], REAL g[6]) {
+    MG_REQUIRE(mg && beta && g, MGX_ERR_INVALID, "get_wall: NULL");
+    const WALLTAB* t = (const WALLTAB*)mg->wall;
+    for (int k = 0; k < 6; k++) {
+        beta[k] = t ? t->beta[k] : (REAL)0;
+        g[k] = t ? t->g[k] : (REAL)0;
+    }
+    return MGX_OK;
+}
+
+/* d_f[0] -= 2 g / h on the face unknowns (mgx3dxs_wall_rhs); without a flux nothing runs */
+int FN(add_wall_flux)(MGRID* mg) {
+    MG_REQUIRE(mg && mg->grids3D && mg->maxGrids >= 1, MGX_ERR_INVALID, "add_wall_flux: NULL");
+    const WALLTAB* t = (const WALLTAB*)mg->wall;
+    if (!t || !t->flux) return MGX_OK;
+    MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "add_wall_flux"));
+    GRID* g0 = mg->grids3D[0];
+    const REAL h[3] = {g0->h_x, g0->h_y, g0->h_z};
+    mg->f_rim_zero[0] = 0;
+    return MG_CAT(mgx3dxs_wall_rhs_, R)(mg->ctx, g0->d_f, g0->sizeXYZ, h, t->g, mg->bc);
 }
 
 int FN(Restrict)(MGRID* mg, const REAL* fine, const int fsizeXYZ[3], REAL* coarse, const int csizeXYZ[3]) {
@@ -543,6 +650,16 @@ int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
     MG_TRY(MG_CAT(op_ok3_, R)(mg, curGrid, "Relax"));
     /* the coefficient and the shifted operator: one launch per colour pass; d_e is not used */
     if (mg->bc) MG_CAT(v_touched3_, R)(mg, curGrid->d_v); /* with a mask each colour pass is followed by its launch over the face unknowns */
+    const REAL* wb = MG_CAT(wall_beta3_, R)(mg);
+    if (wb) { /* walls: that launch is the wall launch */
+        if (MG_CAT(has_cap3_, R)(mg))
+            return MG_CAT(mgx3dxs_relax_cap_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(cap_of3_, R)(mg, curGrid),
+                                                      curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb);
+        if (MG_CAT(has_coef3_, R)(mg))
+            return MG_CAT(mgx3dxs_relax_coef_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift,
+                                                       ncycles, mg->bc, wb);
+        return MG_CAT(mgx3dxs_relax_shift_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb);
+    }
     if (MG_CAT(has_cap3_, R)(mg))
         return MG_CAT(mgx3dxs_relax_cap_bc_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(cap_of3_, R)(mg, curGrid),
                                                 curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc);
@@ -968,7 +1085,9 @@ static int MG_CAT(pcg_precond3_, R)(MGRID* mg, int v1, int v2) {
 static int MG_CAT(pcg_true_sumsq3_, R)(MGRID* mg, const REAL* x, const REAL* b, double* ss) {
     GRID* g = mg->grids3D[0];
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
-    if (MG_CAT(has_cap3_, R)(mg))
+    if (MG_CAT(wall_beta3_, R)(mg)) /* walls: the hierarchy's residual, not stored */
+        MG_TRY(MG_CAT(op_residual3_, R)(mg, g, x, b, NULL, mg->pcg_work, mg->pcg_state + MGX_CG_RR));
+    else if (MG_CAT(has_cap3_, R)(mg))
         MG_TRY(MG_CAT(mgx3dxs_residual_cap_bc_, R)(mg->ctx, x, b, g->d_a, ((CAPTAB*)mg->cap)->d_c[0], NULL, g->sizeXYZ, h, mg->shift,
                                                    mg->pcg_work, mg->pcg_state + MGX_CG_RR, mg->bc));
     else if (g->d_a)
@@ -1150,7 +1269,7 @@ int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* i
     MG_TRY(MG_CAT(pcg_alloc3_, R)(mg));
     MG_TRY(mgx_memset_zero(mg->ctx, mg->pcg_state + MGX_CG_FMEAN, sizeof(double)));
     if (!krylov) return MG_CAT(pcg_plain3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);
-    const int singular = mg->bc == 63 && mg->shift == 0;
+    const int singular = mg->bc == 63 && mg->shift == 0 && !MG_CAT(wall_beta3_, R)(mg); /* (a lossy wall: regular, nothing projected) */
     mg->bc_reserved = singular; /* "inside a projected solve": cleared on every way out */
     const int st = MG_CAT(pcg_krylov3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap, mg->bc, singular);
     mg->bc_reserved = 0;
@@ -1191,6 +1310,7 @@ int FN(BackwardEuler)(MGRID* mg, int nsteps, double dt, double kappa, const REAL
             MG_TRY(MG_CAT(mgx3dxs_cap_rhs_bc_, R)(mg->ctx, g->d_v, ((CAPTAB*)mg->cap)->d_c[0], d_source, qscale, s, g->d_f, g->sizeXYZ, mg->bc));
         else
             MG_TRY(MG_CAT(mgx3dxs_shift_rhs_bc_, R)(mg->ctx, g->d_v, d_source, qscale, s, g->d_f, g->sizeXYZ, mg->bc));
+        MG_TRY(FN(add_wall_flux)(mg)); /* the walls' g, in the units of div(a grad u) (nothing without one) */
         MG_TRY(FN(PCG)(mg, v1, v2, tol, maxit, krylov, &it, &rel, &conv, NULL, 0));
         *iters_total += it;
         if (rel > *worst_rel_res || !(rel == rel)) *worst_rel_res = rel;
@@ -1251,6 +1371,7 @@ int MG_CAT(mg3d_solve_from_zero_, R)(mgx_ctx* ctx, REAL* grid_out, const REAL* r
 }
 
 #undef CAPTAB
+#undef WALLTAB
 #undef GRID
 #undef MGRID
 #undef FN

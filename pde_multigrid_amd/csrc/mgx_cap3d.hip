@@ -123,6 +123,20 @@ static int cap_rhs3d(mgx_ctx* ctx, const real* u, const real* c, const real* q, 
                                                   const real h[3], real s, double* dev_work, double* dev_sum, int bc) {                      \
         return mgx::apply_op_dot3d_bc<mgx::CapOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, "apply_cap_dot_bc", c);          \
     }                                                                                                                                        \
+    extern "C" int mgx3dxs_relax_cap_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c, const int n[3],          \
+                                                const real h[3], real s, int ncycles, int bc, const real beta[6]) {                          \
+        return mgx::relax_op3d_wall<mgx::CapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_cap_wall", c);                  \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_residual_cap_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, const real* c, real* r,        \
+                                                   const int n[3], const real h[3], real s, double* dev_work, double* dev_sumsq, int bc,     \
+                                                   const real beta[6]) {                                                                     \
+        return mgx::residual_op3d_wall<mgx::CapOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, beta, "residual_cap_wall", \
+                                                               c);                                                                           \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_apply_cap_dot_wall_##SFX(mgx_ctx* ctx, const real* p, const real* a, const real* c, real* q, const int n[3],      \
+                                                    const real h[3], real s, double* dev_work, double* dev_sum, int bc, const real beta[6]) {\
+        return mgx::apply_op_dot3d_wall<mgx::CapOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, beta, "apply_cap_dot_wall", c);\
+    }                                                                                                                                        \
     extern "C" int mgx3dxs_cap_rhs_bc_##SFX(mgx_ctx* ctx, const real* u, const real* c, const real* q, real qscale, real s, real* f,         \
                                             const int n[3], int bc) {                                                                        \
         return mgx::cap_rhs3d<real>(ctx, u, c, q, qscale, s, f, n, bc, "cap_rhs_bc");                                                        \

@@ -2,7 +2,8 @@
 // (its arithmetic is described in mgx_shift3d.hip), CoefOp, div(a grad u) - s u = f (mgx_coef3d.hip,
 // section 14), and CapOp, div(a grad u) - (s c) u = f with a capacity c at every node (mgx_cap3d.hip, section 17).
 // mgx_shift3d.hip and mgx_coef3d.hip build the interior kernels from the first two, mgx_rim3d.hip their kernels of the Neumann faces
-// (section 15), mgx_cap3d.hip both kinds for CapOp: the point expressions exist once.
+// (section 15), mgx_cap3d.hip both kinds for CapOp, mgx_wall3d.hip the kernels of the walls of section 18 from all three (the
+// *_wall methods): the point expressions exist once.
 #pragma once
 #include "mgx_stencil3d.hpp"
 
@@ -49,6 +50,19 @@ struct ShiftOp {
     template <int MODE>
     __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>&) const {
         return residual3d_point<real, MODE>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, qx, qy, qz) + s * v.C;
+    }
+    // a wall face (mgx_wall3d.hip) adds d to the zeroth-order term of a face unknown: the effective shift se and
+    // the point expressions with it -- the smoother a plain division in `real` in both precisions
+    __device__ __forceinline__ real wall_shift(real d, real) const { return s + d; }
+    __device__ __forceinline__ real relax_wall(const Star7<real>& v, real f, const Star7<real>&, real se) const {
+        const real num = v.O * (hy2 * hz2) + v.E * (hy2 * hz2) + v.N * (hx2 * hz2) + v.S * (hx2 * hz2) + v.D * (hx2 * hy2) + v.U * (hx2 * hy2) -
+                         f * hx2 * hy2 * hz2;
+        const real denP = 2 * (hy2 * hz2 + hx2 * hz2 + hx2 * hy2) + se * hx2 * hy2 * hz2;
+        return num / denP;
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual_wall(const Star7<real>& v, real f, const Star7<real>&, real se) const {
+        return residual3d_point<real, MODE>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, qx, qy, qz) + se * v.C;
     }
 };
 
@@ -97,6 +111,15 @@ struct CoefOp {
     __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a) const {
         return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, s);
     }
+    // a wall face (section 18): the point expressions with the effective shift se = s + d where they take s
+    __device__ __forceinline__ real wall_shift(real d, real) const { return s + d; }
+    __device__ __forceinline__ real relax_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
+        return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, se);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
+        return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, se);
+    }
 };
 
 // div(a grad u) - (s c) u = f: CoefOp's expressions with sc = s * c_P, one rounding in `real`, where they take s.  c is the
@@ -130,6 +153,15 @@ struct CapOp {
     __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a, real cP) const {
         const real sc = s * cP;
         return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, sc);
+    }
+    // a wall face (section 18): the point expressions with the effective shift se = s * c_P + d where they take s * c_P
+    __device__ __forceinline__ real wall_shift(real d, real cP) const { return s * cP + d; }
+    __device__ __forceinline__ real relax_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
+        return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, se);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
+        return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, se);
     }
 };
 

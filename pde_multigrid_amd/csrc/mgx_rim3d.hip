@@ -373,6 +373,24 @@ static int project3d_bc(mgx_ctx* ctx, real* a, const int n[3], double* dev_work,
                                                   const real h[3], real s, double* dev_work, double* dev_sumsq, int bc) {                    \
         return mgx::residual_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, "residual_coef_bc");        \
     }                                                                                                                                        \
+    extern "C" int mgx3dxs_relax_shift_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], real s, int ncycles,\
+                                                  int bc, const real beta[6]) {                                                              \
+        return mgx::relax_op3d_wall<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, n, h, s, ncycles, bc, beta, "relax_shift_wall");           \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_relax_coef_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s,\
+                                                 int ncycles, int bc, const real beta[6]) {                                                  \
+        return mgx::relax_op3d_wall<mgx::CoefOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_coef_wall");                   \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_residual_shift_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, real* r, const int n[3], const real h[3],   \
+                                                     real s, double* dev_work, double* dev_sumsq, int bc, const real beta[6]) {              \
+        return mgx::residual_op3d_wall<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, r, n, h, s, dev_work, dev_sumsq, bc, beta,              \
+                                                                 "residual_shift_wall");                                                     \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_residual_coef_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3],      \
+                                                    const real h[3], real s, double* dev_work, double* dev_sumsq, int bc,                    \
+                                                    const real beta[6]) {                                                                    \
+        return mgx::residual_op3d_wall<mgx::CoefOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, beta, "residual_coef_wall");\
+    }                                                                                                                                        \
     extern "C" int mgx3dxs_restrict_bc_##SFX(mgx_ctx* ctx, const real* fine, const int fn[3], real* coarse, const int cn[3], int bc) {        \
         MGX_REQUIRE(ctx && fine && fn && coarse && cn, MGX_ERR_INVALID, "restrict_bc: NULL argument");                                       \
         RIM_BC_CHECK(bc, "restrict_bc");                                                                                                     \
@@ -446,6 +464,15 @@ MGX_RIM3D_API(f64, double)
     extern "C" int mgx3dxs_apply_coef_dot_bc_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3],      \
                                                    real s, double* dev_work, double* dev_sum, int bc) {                                      \
         return mgx::apply_op_dot3d_bc<mgx::CoefOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, "apply_coef_dot_bc");           \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_laplace_dot_shift_wall_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3], const real h[3], real s,       \
+                                                        double* dev_work, double* dev_sum, int bc, const real beta[6]) {                     \
+        return mgx::apply_op_dot3d_wall<mgx::ShiftOp<real>, real>(ctx, p, nullptr, q, n, h, s, dev_work, dev_sum, bc, beta,                  \
+                                                                  "laplace_dot_shift_wall");                                                 \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_apply_coef_dot_wall_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3],   \
+                                                     real s, double* dev_work, double* dev_sum, int bc, const real beta[6]) {                \
+        return mgx::apply_op_dot3d_wall<mgx::CoefOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, beta, "apply_coef_dot_wall"); \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_cg_update_bc_##SFX(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3],                  \
                                               const double* dev_alpha, double* dev_work, double* dev_sum, int bc) {                          \

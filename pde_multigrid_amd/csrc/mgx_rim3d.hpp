@@ -1,6 +1,8 @@
 // mgx_rim3d.hpp -- what the kernels of the Neumann faces (mgx_rim3d.hip) share with a unit that builds them for
 // an operator policy of its own (mgx_cap3d.hip): the list of face points, the reflected star, the rim kernels that take a policy and
 // their host drivers.  Everything else of the faces -- the transfers, the vector kernels of the solve -- is in mgx_rim3d.hip.
+// The drivers of the convective and prescribed-flux walls (section 18) are here too: they launch the interior kernels of the unit
+// that instantiates them and the wall kernels of mgx_wall3d.hip through that unit's launch functions.
 #pragma once
 #include "mgx_ops3d.hpp"
 
@@ -244,6 +246,128 @@ static int apply_op_dot3d_bc(mgx_ctx* ctx, const real* p, const real* a, real* q
         MGX_LAUNCH((rim_apply_dot3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, p, a, q, R, op,
                    dev_work + interior);
     });
+    MGX_LAUNCH_CHECK();
+    return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
+}
+
+// ------------------------------------------------------------------ convective and prescribed-flux walls (section 18)
+// On a face of the mask the wall law a du/dn + beta u = g adds 2 (g - beta u_P) / h to the half cell's balance: the operator gains
+// the diagonal d_k = ((real)2 * beta_k) / h_axis(k) at the face unknowns, formed here once per call from the level's own spacings.
+// The kernels (mgx_wall3d.hip, their one home) take the six d_k by value; a wall launch REPLACES the rim launch of the same call,
+// the interior launches are the existing ones.  beta in the order of the mask's bits.
+template <class real>
+struct WallD {
+    real d[6];
+};
+
+template <class Op, class real>
+void wall_relax_launch(mgx_ctx* ctx, real* v, const real* f, const real* a, const Rim& R, const Op& op, const WallD<real>& w, int colour);
+template <class Op, class real>
+void wall_residual_launch(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* out, const Rim& R, const Op& op,
+                          const WallD<real>& w, unsigned nb, double* partial);
+template <class Op, class real>
+void wall_apply_dot_launch(mgx_ctx* ctx, const real* p, const real* a, real* q, const Rim& R, const Op& op, const WallD<real>& w,
+                           unsigned nb, double* partial);
+
+// the wall data of a call against its mask: v[k] finite, >= 0 unless `flux`, 0 on a face whose bit is clear, and small enough for
+// the term ((real)2 * v[k]) / h_axis(k) the kernels work with to be finite in `real` (fp32: a beta near FLT_MAX, or a large one on a
+// fine level, would make it inf and the results NaN); *any = some v[k] != 0
+template <class real>
+static int wall_data_check(const real v[6], const real h[3], int bc, bool flux, const char* what, bool* any) {
+    *any = false;
+    for (int k = 0; k < 6; k++) {
+        MGX_REQUIRE(std::isfinite((double)v[k]) && (flux || v[k] >= 0), MGX_ERR_INVALID, "%s: %s[%d] = %g is not finite%s", what,
+                    flux ? "g" : "beta", k, (double)v[k], flux ? "" : " and >= 0");
+        MGX_REQUIRE(v[k] == 0 || ((bc >> k) & 1), MGX_ERR_INVALID, "%s: %s[%d] = %g on face %d, which the mask %d does not flag", what,
+                    flux ? "g" : "beta", k, (double)v[k], k, bc);
+        MGX_REQUIRE(v[k] == 0 || std::isfinite((double)(((real)2 * v[k]) / h[k >> 1])), MGX_ERR_INVALID,
+                    "%s: 2 * %s[%d] / h = 2 * %g / %g is not finite in this precision", what, flux ? "g" : "beta", k, (double)v[k],
+                    (double)h[k >> 1]);
+        if (v[k] != 0) *any = true;
+    }
+    return MGX_OK;
+}
+
+template <class real>
+static WallD<real> wall_diagonal(const real beta[6], const real h[3]) {
+    WallD<real> w;
+    for (int k = 0; k < 6; k++) w.d[k] = ((real)2 * beta[k]) / h[k >> 1];
+    return w;
+}
+
+// relax_op3d_bc with the wall launch for the rim launch; all betas zero: relax_op3d_bc and nothing else
+template <class Op, class real>
+static int relax_op3d_wall(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int bc,
+                           const real beta[6], const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h && beta, MGX_ERR_INVALID, "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    bool any;
+    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what, &any));
+    if (!any) return relax_op3d_bc<Op, real>(ctx, v, f, a, n, h, s, ncycles, bc, what, c);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd, false));
+    MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "%s: ncycles = %d < 0", what, ncycles);
+    MGX_USE(ctx);
+    const Op op = make_op<Op, real>(ctx, h, s, c);
+    const WallD<real> w = wall_diagonal<real>(beta, h);
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    for (int p = 0; p < 2 * ncycles; p++) {
+        relax_op3d_pass<Op, real>(ctx, v, f, a, n, op, p & 1);
+        wall_relax_launch<Op, real>(ctx, v, f, a, R, op, w, p & 1);
+    }
+    MGX_LAUNCH_CHECK();
+    return MGX_OK;
+}
+
+template <class Op, class real>
+static int residual_op3d_wall(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3], const real h[3], real s,
+                              double* dev_work, double* dev_sumsq, int bc, const real beta[6], const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h && (r || dev_sumsq) && (!dev_sumsq || dev_work) && beta,
+                MGX_ERR_INVALID, "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    bool any;
+    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what, &any));
+    if (!any) return residual_op3d_bc<Op, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, what, c);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd));
+    MGX_USE(ctx);
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    if (r) rim_zero3d_xs<real>(ctx, r, n);
+    const Op op = make_op<Op, real>(ctx, h, s, c);
+    const WallD<real> w = wall_diagonal<real>(beta, h);
+    MGX_TRY_RET((residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, op, dev_work, dev_sumsq, false)));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    unsigned nb = rim_blocks(R);
+    if (dev_sumsq && nb > interior) nb = (unsigned)interior;
+    wall_residual_launch<Op, real>(ctx, v, f, a, r, R, op, w, nb, dev_sumsq ? dev_work + interior : (double*)nullptr);
+    MGX_LAUNCH_CHECK();
+    return dev_sumsq ? krylov_final(ctx, dev_work, interior + nb, 1, dev_sumsq) : MGX_OK;
+}
+
+template <class Op, class real>
+static int apply_op_dot3d_wall(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3], real s, double* dev_work,
+                               double* dev_sum, int bc, const real beta[6], const char* what, const real* c = nullptr) {
+    MGX_REQUIRE(ctx && p && (a || !Op::HAS_A) && (c || !Op::HAS_C) && q && n && h && dev_work && dev_sum && beta, MGX_ERR_INVALID,
+                "%s: NULL argument", what);
+    RIM_BC_CHECK(bc, what);
+    bool any;
+    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what, &any));
+    if (!any) return apply_op_dot3d_bc<Op, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, what, c);
+    const double sd = (double)s;
+    MGX_TRY_RET(rows_check(n, what, &sd));
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    MGX_USE(ctx);
+    const Op op = make_op<Op, real>(ctx, h, s, c);
+    const WallD<real> w = wall_diagonal<real>(beta, h);
+    MGX_TRY_RET((residual_op3d_launch<Op, true>(ctx, p, (const real*)nullptr, a, q, n, op, dev_work, dev_sum, false)));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    const unsigned nb = rim_blocks(R);
+    wall_apply_dot_launch<Op, real>(ctx, p, a, q, R, op, w, nb, dev_work + interior);
     MGX_LAUNCH_CHECK();
     return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
 }

@@ -681,6 +681,49 @@ class _Ops3D(_Ops):
         fn, ct = self._fn("set_rim_bc", dtype)
         return self._run(ctx, [v], lambda a: fn(ctx._h, a, _ip(n), ct(value), C.c_int(bc)), 0, _shape(n), dtype)
 
+    # ---- convective and prescribed-flux walls (x-split only, mgx3dxs_*_wall): the _bc wrappers with the six betas behind bc;
+    # a: None = the shifted operator, c: None = no capacity
+    def _wall_name(self, base, a, c):
+        return {"relax": "relax_%s_wall", "residual": "residual_%s_wall"}[base] % ("cap" if c is not None else "coef" if a is not None else "shift")
+
+    def relax_wall(self, ctx, v, f, a, c, n, rng, s, ncycles, bc, beta, dtype=None):
+        dtype = dtype or v.dtype
+        fn, ct = self._fn(self._wall_name("relax", a, c), dtype)
+        h, b = _rp(grid_spacing(n, rng, dtype), ct), _rp(beta, ct)
+        arrays = [v, f] + [x for x in (a, c) if x is not None]
+        return self._run(ctx, arrays, lambda vp, fp, *ac: fn(ctx._h, vp, fp, *ac, _ip(n), h, ct(s), C.c_int(ncycles), C.c_int(bc), b), 0,
+                         _shape(n), dtype)
+
+    def residual_wall(self, ctx, v, f, a, c, n, rng, s, bc, beta, store=True, want_sum=True, dtype=None):
+        """(r, sum of squares over all unknowns): r None with store=False, the sum None with want_sum=False"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn(self._wall_name("residual", a, c), dtype)
+        h, b = _rp(grid_spacing(n, rng, dtype), ct), _rp(beta, ct)
+        arrays = [xs_pack(np.ascontiguousarray(x, dtype)) for x in (v, f, a, c) if x is not None]
+        arrays.append(xs_pack(np.zeros(_shape(n), dtype)) if store else None)
+        outs, sums = self._krylov(ctx, n, arrays, [],
+                                  lambda w, s0, *ptrs: fn(ctx._h, *ptrs, _ip(n), h, ct(s), w if want_sum else None, s0 if want_sum else None,
+                                                          C.c_int(bc), b), dtype, 1, self._krylov_work_bc)
+        return (xs_unpack(outs[-1], n[0]) if store else None), (float(sums[0]) if want_sum else None)
+
+    def apply_dot_wall(self, ctx, p, a, c, n, rng, s, bc, beta, q=None, dtype=None):
+        """q = A p at every unknown and <p, q>_W: returns (q, pq); q: the array written into (default zeros)"""
+        dtype = dtype or p.dtype
+        name = "apply_cap_dot_wall" if c is not None else "apply_coef_dot_wall" if a is not None else "laplace_dot_shift_wall"
+        fn, ct = self._fn(name, dtype)
+        h, b = _rp(grid_spacing(n, rng, dtype), ct), _rp(beta, ct)
+        q = np.zeros(_shape(n), dtype) if q is None else q
+        outs, sums = self._krylov_bc(ctx, n, [x for x in (p, a, c) if x is not None] + [q], [],
+                                     lambda w, s0, *ptrs: fn(ctx._h, *ptrs, _ip(n), h, ct(s), w, s0, C.c_int(bc), b), dtype, 1)
+        return outs[-1], float(sums[0])
+
+    def wall_rhs(self, ctx, f, n, rng, g, bc, dtype=None):
+        """f -= 2 g / h at the unknowns on the faces of bc with g != 0"""
+        dtype = dtype or f.dtype
+        fn, ct = self._fn("wall_rhs", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [f], lambda fp: fn(ctx._h, fp, _ip(n), h, _rp(g, ct), C.c_int(bc)), 0, _shape(n), dtype)
+
     # ---- vector kernels of the preconditioned CG solve (x-split only; every array in the reference layout on the host)
     # every work array is uploaded with WORK_GUARD sentinel doubles behind the elements the library asks for, and the
     # sentinels are looked at after the call: a kernel that writes into the next WORK_GUARD doubles behind its work array
@@ -1010,7 +1053,7 @@ def _grid3_struct(ct):
         _fields_ = [("grids3D", C.POINTER(C.POINTER(Grid3D))), ("numGrids", C.c_int), ("maxGrids", C.c_int),
                     ("ctx", C.c_void_p), ("residual_mode", C.c_int), ("fuse", C.c_int), ("layout", C.c_int),
                     ("smoother", C.c_int), ("omega", ct), ("use_graph", C.c_int), ("capturing", C.c_int),
-                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 30), ("cap", C.c_void_p), ("pcg_fproj", C.c_void_p),
+                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 29), ("wall", C.c_void_p), ("cap", C.c_void_p), ("pcg_fproj", C.c_void_p),
                     ("f_rim_zero", C.c_ubyte * 32),
                     ("v_rim_zero", C.c_ubyte * 32), ("e_rim_valid", C.c_ubyte * 32), ("pcg_x", C.c_void_p),
                     ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
@@ -1117,14 +1160,17 @@ class MultiGrid3D(_MGBase):
     _prefix = "mgMultiGrid3D"
 
     def __init__(self, ctx, finestGridSizeXYZ, rng, dtype=np.float64, nlevels=0, residual_mode=REF_COMPAT, fuse=True,
-                 layout="xsplit", coarsening="full", shift=0.0, coefficient=None, neumann=None, capacity=None):
+                 layout="xsplit", coarsening="full", shift=0.0, coefficient=None, neumann=None, capacity=None, robin=None,
+                 wall_flux=None):
         """coarsening="semi": every level halves only the axes with the smallest spacing (semi_plan, mg_multigrid.h) -- the
         hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count.
         shift = s >= 0: the hierarchy of (Laplacian - s) u = f (the `shift` property).
         coefficient = a > 0 at every point of the finest grid: the hierarchy of div(a grad u) - s u = f (set_coefficient).
         neumann = six truthy values (x-low, x-high, y-low, y-high, z-low, z-high): the faces with du/dn = 0 (set_neumann).
         capacity = c >= 0 at every point of the finest grid: the hierarchy of div(a grad u) - (s c) u = f (set_capacity; needs
-        a coefficient)."""
+        a coefficient).
+        robin, wall_flux = six numbers each (the faces' order): beta >= 0 and g of the wall law a du/dn + beta u = g on the
+        faces of `neumann` (set_wall)."""
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self._sfx, self._ct = _ct(dtype)
@@ -1169,6 +1215,43 @@ class MultiGrid3D(_MGBase):
             except Exception:
                 self.close()
                 raise
+        if robin is not None or wall_flux is not None:
+            try:
+                self.set_wall(robin, wall_flux)
+            except Exception:
+                self.close()
+                raise
+
+    def set_wall(self, robin=None, flux=None):
+        """robin, flux: six numbers each, one per face in the order x-low, x-high, y-low, y-high, z-low, z-high (None: zeros):
+        beta >= 0 and g of the wall law  a du/dn + beta u = g  (n outward) on the faces flagged by set_neumann, in the units of the
+        hierarchy's operator div(a grad u) (a = 1 without a coefficient); beta = g = 0 is the insulated wall.  With BackwardEuler's
+        kappa a physical  kappa a du/dn + B u = G  is beta = B / kappa, g = G / kappa -- nothing is rescaled here.  beta enters the
+        operator of every level (a diagonal term 2 beta / h at the face unknowns, from the level's own spacing); g enters level 0's
+        right-hand side: call add_wall_flux() once after upload_f (BackwardEuler does it for every step, solve3d_pcg for its
+        rhs).  A beta > 0 makes the closed box regular: all six faces with shift = 0 are then accepted, and
+        PCG(krylov="weighted") projects nothing.  A value other than 0 on a face that is not flagged is refused, and set_neumann
+        refuses to clear a face that still carries one.  PCG(precond="f32") is not available with walls.  All zeros: the hierarchy
+        is, launch for launch, one that never had a wall.  Data that vary along a face: subtract 2 g(P) / h from f at the face
+        yourself (h the spacing along the face's axis)."""
+        vals = []
+        for name, x in (("robin", robin), ("flux", flux)):
+            x = [0.0] * 6 if x is None else [float(t) for t in x]
+            if len(x) != 6:
+                raise ValueError("%s takes six values (x-low, x-high, y-low, y-high, z-low, z-high), not %d" % (name, len(x)))
+            vals.append(x)
+        self._call("set_wall", _rp(vals[0], self._ct), _rp(vals[1], self._ct))
+
+    @property
+    def wall(self):
+        """(robin, flux) as set_wall takes them"""
+        b, g = (self._ct * 6)(), (self._ct * 6)()
+        self._call("get_wall", b, g)
+        return tuple(float(x) for x in b), tuple(float(x) for x in g)
+
+    def add_wall_flux(self):
+        """f[0] -= 2 g / h at the unknowns on the faces with a flux g != 0 (mgx3dxs_wall_rhs): once per right-hand side"""
+        self._call("add_wall_flux")
 
     def set_neumann(self, faces):
         """faces: six truthy values, one per face in the order x-low, x-high, y-low, y-high, z-low, z-high (None: all False).  A
@@ -1177,8 +1260,7 @@ class MultiGrid3D(_MGBase):
         residual_mode=CORRECT and coarsening="full"; PCG and BackwardEuler then take krylov=False or krylov="weighted" (CG in the
         inner product weighted by 1/2 per wall an unknown lies on; krylov=True is refused), PCG(precond="f32") is not available,
         and all six faces need a shift > 0 -- but for PCG(krylov="weighted"), which solves that singular system in the projected
-        sense.  A prescribed flux g (du/dn = g, outward) goes into the right-hand side:
-        f -= 2 g a / h at the face.  All False: the hierarchy is what it was without walls."""
+        sense.  A prescribed flux or a convective wall: set_wall.  All False: the hierarchy is what it was without walls."""
         faces = [0] * 6 if faces is None else [int(bool(x)) for x in faces]
         if len(faces) != 6:
             raise ValueError("neumann takes six values (x-low, x-high, y-low, y-high, z-low, z-high), not %d" % len(faces))
@@ -1692,7 +1774,7 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
 
 
 def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full",
-                shift=0.0, coefficient=None, neumann=None, capacity=None):
+                shift=0.0, coefficient=None, neumann=None, capacity=None, robin=None, wall_flux=None):
     """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
     precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG).
     coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call.
@@ -1700,7 +1782,8 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
     coefficient = a > 0 at every point: the solve of div(a grad u) - shift u = rhs (MultiGrid3D(coefficient=a)), likewise.
     neumann = six truthy values: the faces with du/dn = 0 (MultiGrid3D(neumann=...)), likewise; needs krylov=False or
     krylov="weighted" (MultiGrid3D.PCG).
-    capacity = c >= 0 at every point, with a coefficient: the solve of div(a grad u) - (shift c) u = rhs, likewise."""
+    capacity = c >= 0 at every point, with a coefficient: the solve of div(a grad u) - (shift c) u = rhs, likewise.
+    robin, wall_flux = six numbers each: the walls' beta and g (MultiGrid3D.set_wall); the flux is folded into rhs here."""
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
     if precond not in ("f64", "f32"):
@@ -1709,13 +1792,15 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
         raise ValueError("precond='f32' needs an fp64 grid")
     if coarsening not in ("full", "semi"):
         raise ValueError("coarsening must be 'full' or 'semi', not %r" % (coarsening,))
-    if coarsening == "semi" or shift != 0 or coefficient is not None or capacity is not None or (neumann is not None and any(neumann)):
+    if coarsening == "semi" or shift != 0 or coefficient is not None or capacity is not None or (neumann is not None and any(neumann)) or \
+            robin is not None or wall_flux is not None:
         mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening=coarsening,
-                         shift=shift, coefficient=coefficient, neumann=neumann, capacity=capacity)
+                         shift=shift, coefficient=coefficient, neumann=neumann, capacity=capacity, robin=robin, wall_flux=wall_flux)
         try:
             mg.upload_v(0, grid)
             if rhs is not None:
                 mg.upload_f(0, rhs)
+            mg.add_wall_flux()
             it, rel, conv, _ = mg.PCG(v1, v2, tol, maxit, krylov, precond)
             return mg.download_v(0), it, rel, conv
         finally:
