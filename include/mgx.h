@@ -759,12 +759,12 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     /* beta_k) / h_axis(k), summed over the point's faces in the order x, y, z into d(P); where d(P) != */\
     /* 0 the point is the operator's own expression with the effective shift s + d(P) (capacity: s *   */\
     /* c_P + d(P)), the shifted smoother a plain division in `real`; where d(P) == 0 it has the bits of */\
-    /* the _bc entry.  Each _wall entry is the _bc entry of its name, argument for argument, plus      */\
-    /* `const real beta[6]` last, with that entry's contract; beta NULL, a beta[k] negative or not      */\
+    /* the mirrored star alone.  Each _wall entry is the _bc entry of its name, argument for argument,  */\
+    /* plus `const real beta[6]` last, with that entry's contract; beta NULL, a beta[k] negative or not */\
     /* finite, one != 0 on a face whose bit is clear, or one so large that 2 beta / h is not finite in  */\
-    /* `real` (fp32: beyond about 1.7e38 h): MGX_ERR_INVALID.  All betas zero: the _bc                  */\
-    /* entry is called and nothing else.  bc = 63 with s = 0 is regular as soon as one beta[k] > 0.     */\
-    /* The wall launch replaces the launch over the face unknowns of the _bc entry.                     */\
+    /* `real` (fp32: beyond about 1.7e38 h): MGX_ERR_INVALID.  A _bc entry and its _wall entry are two  */\
+    /* names for one path: the _bc entry passes six zero betas, and one launch over the face unknowns   */\
+    /* serves both.  bc = 63 with s = 0 is regular as soon as one beta[k] > 0.                          */\
     /* wall_rhs: f[P] = f[P] - ((real)2 * g[k]) / h_axis(k) at the face unknowns, successively for the  */\
     /* flagged faces of P with g[k] != 0 in the order x, y, z; nothing else of f is touched.  g[k] not  */\
     /* finite or != 0 on a face whose bit is clear: MGX_ERR_INVALID.  A g that varies along a face is   */\

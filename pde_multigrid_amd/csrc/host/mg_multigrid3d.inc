@@ -215,11 +215,12 @@ typedef struct MG_CAT(mgWallTable3_, R) {
 } MG_CAT(mgWallTable3_, R);
 #define WALLTAB MG_CAT(mgWallTable3_, R)
 
-/* the betas the operators run with: NULL without a positive one (the _bc entries then, launch for launch) */
+/* the betas of a hierarchy with a positive one, else NULL: the operators then pass six zeros, which is the _bc entry by another name */
 static const REAL* MG_CAT(wall_beta3_, R)(const MGRID* mg) {
     const WALLTAB* t = (const WALLTAB*)mg->wall;
     return t && t->lossy ? t->beta : NULL;
 }
+static const REAL MG_CAT(no_wall3_, R)[6] = {0, 0, 0, 0, 0, 0};
 
 void FN(destroy)(MGRID* mg) {
     if (!mg) return;
@@ -350,22 +351,16 @@ static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) 
  * *dev_sumsq (NULL: none; dev_work: the partials).  The plain operator takes mg->residual_mode and sums in a launch of its own. */
 static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, const REAL* f, REAL* r, double* dev_work, double* dev_sumsq) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
-    const REAL* wb = MG_CAT(wall_beta3_, R)(mg);
-    if (wb) { /* walls: the _wall entries with the level's own spacings (DESIGN.md 18) */
-        if (MG_CAT(has_cap3_, R)(mg))
-            return MG_CAT(mgx3dxs_residual_cap_wall_, R)(mg->ctx, v, f, g->d_a, MG_CAT(cap_of3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift,
-                                                         dev_work, dev_sumsq, mg->bc, wb);
-        if (MG_CAT(has_coef3_, R)(mg))
-            return MG_CAT(mgx3dxs_residual_coef_wall_, R)(mg->ctx, v, f, g->d_a, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc, wb);
-        return MG_CAT(mgx3dxs_residual_shift_wall_, R)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc, wb);
-    }
+    const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
+    const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R); /* the _wall entries with the level's own spacings (DESIGN.md 18) */
+    const int faces = mg->bc || wall;                    /* (betas without a mask: the entry refuses them) */
     if (MG_CAT(has_cap3_, R)(mg))
-        return MG_CAT(mgx3dxs_residual_cap_bc_, R)(mg->ctx, v, f, g->d_a, MG_CAT(cap_of3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift, dev_work,
-                                                   dev_sumsq, mg->bc);
+        return MG_CAT(mgx3dxs_residual_cap_wall_, R)(mg->ctx, v, f, g->d_a, MG_CAT(cap_of3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift, dev_work,
+                                                     dev_sumsq, mg->bc, wb);
     if (MG_CAT(has_coef3_, R)(mg))
-        return MG_CAT(mgx3dxs_residual_coef_bc_, R)(mg->ctx, v, f, g->d_a, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc);
-    if (mg->shift != 0 || mg->bc) /* (with a mask the plain Laplacian is the shifted operator with s = 0) */
-        return MG_CAT(mgx3dxs_residual_shift_bc_, R)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc);
+        return MG_CAT(mgx3dxs_residual_coef_wall_, R)(mg->ctx, v, f, g->d_a, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc, wb);
+    if (mg->shift != 0 || faces) /* (with a mask the plain Laplacian is the shifted operator with s = 0) */
+        return MG_CAT(mgx3dxs_residual_shift_wall_, R)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->shift, dev_work, dev_sumsq, mg->bc, wb);
     MG_TRY(MGXL(mg, residual)(mg->ctx, v, f, r, g->sizeXYZ, h, mg->residual_mode));
     return dev_sumsq ? MG_CAT(mgx3dxs_dot2_, R)(mg->ctx, r, r, NULL, g->sizeXYZ, dev_work, dev_sumsq) : MGX_OK;
 }
@@ -374,21 +369,15 @@ static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, con
  * weighted inner product (the plain Laplacian is then the shifted operator with s = 0) */
 static int MG_CAT(op_apply_dot3_, R)(MGRID* mg, const GRID* g, const REAL* p, REAL* q, double* dev_work, double* dev_sum) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
-    const REAL* wb = MG_CAT(wall_beta3_, R)(mg);
-    if (wb) {
-        if (MG_CAT(has_cap3_, R)(mg))
-            return MG_CAT(mgx3dxs_apply_cap_dot_wall_, R)(mg->ctx, p, g->d_a, MG_CAT(cap_of3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
-                                                          dev_sum, mg->bc, wb);
-        if (MG_CAT(has_coef3_, R)(mg))
-            return MG_CAT(mgx3dxs_apply_coef_dot_wall_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc, wb);
-        return MG_CAT(mgx3dxs_laplace_dot_shift_wall_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc, wb);
-    }
-    if (MG_CAT(has_cap3_, R)(mg)) /* (with bc = 0 the _bc entry is the interior entry) */
-        return MG_CAT(mgx3dxs_apply_cap_dot_bc_, R)(mg->ctx, p, g->d_a, MG_CAT(cap_of3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
-                                                    dev_sum, mg->bc);
-    if (mg->bc && MG_CAT(has_coef3_, R)(mg))
-        return MG_CAT(mgx3dxs_apply_coef_dot_bc_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc);
-    if (mg->bc) return MG_CAT(mgx3dxs_laplace_dot_shift_bc_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc);
+    const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
+    const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R);
+    const int faces = mg->bc || wall; /* (betas without a mask: the entry refuses them) */
+    if (MG_CAT(has_cap3_, R)(mg)) /* (with bc = 0 the entry is the interior entry) */
+        return MG_CAT(mgx3dxs_apply_cap_dot_wall_, R)(mg->ctx, p, g->d_a, MG_CAT(cap_of3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
+                                                      dev_sum, mg->bc, wb);
+    if (faces && MG_CAT(has_coef3_, R)(mg))
+        return MG_CAT(mgx3dxs_apply_coef_dot_wall_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc, wb);
+    if (faces) return MG_CAT(mgx3dxs_laplace_dot_shift_wall_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum, mg->bc, wb);
     if (MG_CAT(has_coef3_, R)(mg))
         return MG_CAT(mgx3dxs_apply_coef_dot_, R)(mg->ctx, p, g->d_a, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum);
     if (mg->shift != 0) return MG_CAT(mgx3dxs_laplace_dot_shift_, R)(mg->ctx, p, q, g->sizeXYZ, h, mg->shift, dev_work, dev_sum);
@@ -650,24 +639,17 @@ int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
     MG_TRY(MG_CAT(op_ok3_, R)(mg, curGrid, "Relax"));
     /* the coefficient and the shifted operator: one launch per colour pass; d_e is not used */
     if (mg->bc) MG_CAT(v_touched3_, R)(mg, curGrid->d_v); /* with a mask each colour pass is followed by its launch over the face unknowns */
-    const REAL* wb = MG_CAT(wall_beta3_, R)(mg);
-    if (wb) { /* walls: that launch is the wall launch */
-        if (MG_CAT(has_cap3_, R)(mg))
-            return MG_CAT(mgx3dxs_relax_cap_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(cap_of3_, R)(mg, curGrid),
-                                                      curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb);
-        if (MG_CAT(has_coef3_, R)(mg))
-            return MG_CAT(mgx3dxs_relax_coef_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift,
-                                                       ncycles, mg->bc, wb);
-        return MG_CAT(mgx3dxs_relax_shift_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb);
-    }
+    const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
+    const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R);
+    const int faces = mg->bc || wall; /* (betas without a mask: the entry refuses them) */
     if (MG_CAT(has_cap3_, R)(mg))
-        return MG_CAT(mgx3dxs_relax_cap_bc_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(cap_of3_, R)(mg, curGrid),
-                                                curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc);
+        return MG_CAT(mgx3dxs_relax_cap_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(cap_of3_, R)(mg, curGrid),
+                                                  curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb);
     if (MG_CAT(has_coef3_, R)(mg))
-        return MG_CAT(mgx3dxs_relax_coef_bc_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift, ncycles,
-                                                 mg->bc);
-    if (mg->shift != 0 || mg->bc)
-        return MG_CAT(mgx3dxs_relax_shift_bc_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc);
+        return MG_CAT(mgx3dxs_relax_coef_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift, ncycles,
+                                                   mg->bc, wb);
+    if (mg->shift != 0 || faces)
+        return MG_CAT(mgx3dxs_relax_shift_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb);
     if (mg->smoother == 1) { /* weighted Jacobi: the error scratch doubles as the ping-pong array */
         if (lvl >= 0) mg->e_rim_valid[lvl] = 0;
         return MGXL(mg, jacobi)(mg->ctx, curGrid->d_v, curGrid->d_e, curGrid->d_f, curGrid->sizeXYZ, h, mg->omega, ncycles);

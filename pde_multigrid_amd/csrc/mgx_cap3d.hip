@@ -10,12 +10,12 @@
 // takes the capacity of that point: only the centre is read, so nothing is mirrored.
 //
 // The operator's policy, CapOp, is in mgx_ops3d.hpp and carries the array; the kernels and their host drivers are the shared ones of
-// mgx_stencil3d.hpp and, for the face unknowns, of mgx_rim3d.hpp, instantiated with the policy in this unit only:
+// mgx_stencil3d.hpp, instantiated with the policy in this unit only (the drivers of mgx_rim3d.hpp reach the kernels of the face
+// unknowns, which mgx_wall3d.hip instantiates for CapOp too, through that unit's launch functions):
 //   relax_op3d_xs_kernel<real, CapOp, TYW, R>      one colour pass ("relax_cap3d_xs_kernel" to last_relax_kernel()): the coefficient
 //                                                  pass plus one streaming load of c per step and row, 3.0 words per point and pass
 //   relax_op_zero3d_xs_kernel<real, CapOp>         the first red pass on a level that counts as zero
 //   residual_op3d_xs_kernel<real, CapOp, 1, LAP>   r and / or the partials of <r, r>; with LAP: q = A p and the partials of <p, q>
-//   rim_relax3d_xs_kernel, rim_residual3d_xs_kernel, rim_apply_dot3d_xs_kernel<.., CapOp, ..>   the same on the face unknowns
 //   cap_rhs3d_xs_kernel, rim_cap_rhs3d_xs_kernel   f = (-((s*c)*u)) - qscale*q, the right-hand side of a backward Euler step
 #include "mgx_rim3d.hpp"
 
@@ -113,29 +113,31 @@ static int cap_rhs3d(mgx_ctx* ctx, const real* u, const real* c, const real* q, 
     }                                                                                                                                        \
     extern "C" int mgx3dxs_relax_cap_bc_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c, const int n[3],            \
                                               const real h[3], real s, int ncycles, int bc) {                                                \
-        return mgx::relax_op3d_bc<mgx::CapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, "relax_cap_bc", c);                            \
+        return mgx::relax_op3d_bc<mgx::CapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, mgx::NO_WALL<real>, "relax_cap_bc", c);        \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_residual_cap_bc_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, const real* c, real* r,          \
                                                  const int n[3], const real h[3], real s, double* dev_work, double* dev_sumsq, int bc) {     \
-        return mgx::residual_op3d_bc<mgx::CapOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, "residual_cap_bc", c);       \
+        return mgx::residual_op3d_bc<mgx::CapOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc,                              \
+                                                             mgx::NO_WALL<real>, "residual_cap_bc", c);                                      \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_apply_cap_dot_bc_##SFX(mgx_ctx* ctx, const real* p, const real* a, const real* c, real* q, const int n[3],        \
                                                   const real h[3], real s, double* dev_work, double* dev_sum, int bc) {                      \
-        return mgx::apply_op_dot3d_bc<mgx::CapOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, "apply_cap_dot_bc", c);          \
+        return mgx::apply_op_dot3d_bc<mgx::CapOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc,                                  \
+                                                              mgx::NO_WALL<real>, "apply_cap_dot_bc", c);                                    \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_relax_cap_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c, const int n[3],          \
                                                 const real h[3], real s, int ncycles, int bc, const real beta[6]) {                          \
-        return mgx::relax_op3d_wall<mgx::CapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_cap_wall", c);                  \
+        return mgx::relax_op3d_bc<mgx::CapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_cap_wall", c);                    \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_residual_cap_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, const real* c, real* r,        \
                                                    const int n[3], const real h[3], real s, double* dev_work, double* dev_sumsq, int bc,     \
                                                    const real beta[6]) {                                                                     \
-        return mgx::residual_op3d_wall<mgx::CapOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, beta, "residual_cap_wall", \
+        return mgx::residual_op3d_bc<mgx::CapOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, beta, "residual_cap_wall",   \
                                                                c);                                                                           \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_apply_cap_dot_wall_##SFX(mgx_ctx* ctx, const real* p, const real* a, const real* c, real* q, const int n[3],      \
                                                     const real h[3], real s, double* dev_work, double* dev_sum, int bc, const real beta[6]) {\
-        return mgx::apply_op_dot3d_wall<mgx::CapOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, beta, "apply_cap_dot_wall", c);\
+        return mgx::apply_op_dot3d_bc<mgx::CapOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, beta, "apply_cap_dot_wall", c);  \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_cap_rhs_bc_##SFX(mgx_ctx* ctx, const real* u, const real* c, const real* q, real qscale, real s, real* f,         \
                                             const int n[3], int bc) {                                                                        \

@@ -1,9 +1,10 @@
 // mgx_ops3d.hpp -- the operator policies of mgx_stencil3d.hpp that more than one file instantiates: ShiftOp, (Laplacian - s) u = f
 // (its arithmetic is described in mgx_shift3d.hip), CoefOp, div(a grad u) - s u = f (mgx_coef3d.hip,
 // section 14), and CapOp, div(a grad u) - (s c) u = f with a capacity c at every node (mgx_cap3d.hip, section 17).
-// mgx_shift3d.hip and mgx_coef3d.hip build the interior kernels from the first two, mgx_rim3d.hip their kernels of the Neumann faces
-// (section 15), mgx_cap3d.hip both kinds for CapOp, mgx_wall3d.hip the kernels of the walls of section 18 from all three (the
-// *_wall methods): the point expressions exist once.
+// mgx_shift3d.hip and mgx_coef3d.hip build the interior kernels from the first two, mgx_cap3d.hip those of CapOp, mgx_wall3d.hip
+// the kernels of the face unknowns (Neumann faces, section 15, and the walls of section 18) from all three: the point expressions
+// exist once.  A policy's relax_wall / residual_wall take the zeroth-order coefficient of the point, se, as an argument; CoefOp's and
+// CapOp's relax / residual are these with se = s or s * c_P, ShiftOp's relax keeps its own form with the level's denominator.
 #pragma once
 #include "mgx_stencil3d.hpp"
 
@@ -104,14 +105,12 @@ struct CoefOp {
     static void with_mode(int, F&& f) {
         f(std::integral_constant<int, 1>());
     }
-    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>& a) const {
-        return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, s);
-    }
+    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>& a) const { return relax_wall(v, f, a, s); }
     template <int MODE>
     __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a) const {
-        return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, s);
+        return residual_wall<MODE>(v, f, a, s);
     }
-    // a wall face (section 18): the point expressions with the effective shift se = s + d where they take s
+    // the point expressions with se where they take s; at a wall face (section 18) the effective shift se = s + d
     __device__ __forceinline__ real wall_shift(real d, real) const { return s + d; }
     __device__ __forceinline__ real relax_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
         return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, se);
@@ -146,15 +145,13 @@ struct CapOp {
         f(std::integral_constant<int, 1>());
     }
     __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>& a, real cP) const {
-        const real sc = s * cP;
-        return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, sc);
+        return relax_wall(v, f, a, s * cP);
     }
     template <int MODE>
     __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a, real cP) const {
-        const real sc = s * cP;
-        return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, sc);
+        return residual_wall<MODE>(v, f, a, s * cP);
     }
-    // a wall face (section 18): the point expressions with the effective shift se = s * c_P + d where they take s * c_P
+    // CoefOp's point expressions with se where they take s; at a wall face (section 18) the effective shift se = s * c_P + d
     __device__ __forceinline__ real wall_shift(real d, real cP) const { return s * cP + d; }
     __device__ __forceinline__ real relax_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
         return relax_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, se);

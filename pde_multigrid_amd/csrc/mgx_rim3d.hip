@@ -6,8 +6,8 @@
 // and on no Dirichlet face (Dirichlet wins on shared edges and corners; Dirichlet entries of v are data and are never written).
 // At an unknown on a face every operator is the interior's point expression on a star whose out-of-range entry is replaced by the
 // opposite one (on x-low O := E, for v and for a; on an edge or corner on each axis): there is no new point arithmetic here, the
-// kernels call Op::relax / Op::residual<MODE> (mgx_ops3d.hpp), restrict3d_point and interpolate3d_point (mgx_kernels3d.hpp) on
-// reflected indices.
+// kernels call Op::relax / Op::residual<MODE> (mgx_ops3d.hpp; the operator kernels of mgx_wall3d.hip, with every beta zero),
+// restrict3d_point and interpolate3d_point (mgx_kernels3d.hpp) on reflected indices.
 //
 // The tuned interior kernels run unchanged; every entry below is the existing entry followed by (the colour passes: interleaved
 // with) a RIM launch over the face unknowns, all six faces of a call in one launch.  Points of one colour are independent and the
@@ -21,8 +21,9 @@
 // are the neighbouring lanes' own lines.  Only the faces whose bit is set are listed, and a listed point that lies on a Dirichlet
 // face as well is skipped.  No scratch; the residual's partial sums go behind the interior launch's in the caller's work array.
 //
-// The list, the reflected star, the rim kernels that take an operator policy and their drivers are in mgx_rim3d.hpp (mgx_cap3d.hip
-// builds them for its own policy); this file instantiates them for ShiftOp and CoefOp and holds the transfers and vector kernels.
+// The list, the reflected star and the drivers of the operator entries are in mgx_rim3d.hpp; the kernels of the operators on the
+// face unknowns are in mgx_wall3d.hip, one set for the _bc entries and the _wall entries (section 18).  This file instantiates the
+// drivers for ShiftOp and CoefOp (mgx_cap3d.hip: for CapOp) and holds the transfers and vector kernels.
 #include "mgx_rim3d.hpp"
 
 namespace mgx {
@@ -359,37 +360,39 @@ static int project3d_bc(mgx_ctx* ctx, real* a, const int n[3], double* dev_work,
 #define MGX_RIM3D_API(SFX, real)                                                                                                             \
     extern "C" int mgx3dxs_relax_shift_bc_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], real s, int ncycles,   \
                                                 int bc) {                                                                                    \
-        return mgx::relax_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, n, h, s, ncycles, bc, "relax_shift_bc");                     \
+        return mgx::relax_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, n, h, s, ncycles, bc, mgx::NO_WALL<real>, "relax_shift_bc"); \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_relax_coef_bc_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s,  \
                                                int ncycles, int bc) {                                                                        \
-        return mgx::relax_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, "relax_coef_bc");                             \
+        return mgx::relax_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, mgx::NO_WALL<real>, "relax_coef_bc");         \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_residual_shift_bc_##SFX(mgx_ctx* ctx, const real* v, const real* f, real* r, const int n[3], const real h[3],      \
                                                    real s, double* dev_work, double* dev_sumsq, int bc) {                                    \
-        return mgx::residual_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, r, n, h, s, dev_work, dev_sumsq, bc, "residual_shift_bc"); \
+        return mgx::residual_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, r, n, h, s, dev_work, dev_sumsq, bc,                       \
+                                                               mgx::NO_WALL<real>, "residual_shift_bc");                                      \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_residual_coef_bc_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3],         \
                                                   const real h[3], real s, double* dev_work, double* dev_sumsq, int bc) {                    \
-        return mgx::residual_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, "residual_coef_bc");        \
+        return mgx::residual_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc,                             \
+                                                              mgx::NO_WALL<real>, "residual_coef_bc");                                       \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_relax_shift_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], real s, int ncycles,\
                                                   int bc, const real beta[6]) {                                                              \
-        return mgx::relax_op3d_wall<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, n, h, s, ncycles, bc, beta, "relax_shift_wall");           \
+        return mgx::relax_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, n, h, s, ncycles, bc, beta, "relax_shift_wall");             \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_relax_coef_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s,\
                                                  int ncycles, int bc, const real beta[6]) {                                                  \
-        return mgx::relax_op3d_wall<mgx::CoefOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_coef_wall");                   \
+        return mgx::relax_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_coef_wall");                     \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_residual_shift_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, real* r, const int n[3], const real h[3],   \
                                                      real s, double* dev_work, double* dev_sumsq, int bc, const real beta[6]) {              \
-        return mgx::residual_op3d_wall<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, r, n, h, s, dev_work, dev_sumsq, bc, beta,              \
+        return mgx::residual_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, r, n, h, s, dev_work, dev_sumsq, bc, beta,                \
                                                                  "residual_shift_wall");                                                     \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_residual_coef_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3],      \
                                                     const real h[3], real s, double* dev_work, double* dev_sumsq, int bc,                    \
                                                     const real beta[6]) {                                                                    \
-        return mgx::residual_op3d_wall<mgx::CoefOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, beta, "residual_coef_wall");\
+        return mgx::residual_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, beta, "residual_coef_wall");  \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_restrict_bc_##SFX(mgx_ctx* ctx, const real* fine, const int fn[3], real* coarse, const int cn[3], int bc) {        \
         MGX_REQUIRE(ctx && fine && fn && coarse && cn, MGX_ERR_INVALID, "restrict_bc: NULL argument");                                       \
@@ -459,20 +462,22 @@ MGX_RIM3D_API(f64, double)
     extern "C" size_t mgx3dxs_krylov_work_elems_bc_##SFX(const int n[3]) { return mgx::krylov_work_elems_bc<real>(n); }                      \
     extern "C" int mgx3dxs_laplace_dot_shift_bc_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3], const real h[3], real s,          \
                                                       double* dev_work, double* dev_sum, int bc) {                                           \
-        return mgx::apply_op_dot3d_bc<mgx::ShiftOp<real>, real>(ctx, p, nullptr, q, n, h, s, dev_work, dev_sum, bc, "laplace_dot_shift_bc"); \
+        return mgx::apply_op_dot3d_bc<mgx::ShiftOp<real>, real>(ctx, p, nullptr, q, n, h, s, dev_work, dev_sum, bc,                          \
+                                                                mgx::NO_WALL<real>, "laplace_dot_shift_bc");                                 \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_apply_coef_dot_bc_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3],      \
                                                    real s, double* dev_work, double* dev_sum, int bc) {                                      \
-        return mgx::apply_op_dot3d_bc<mgx::CoefOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, "apply_coef_dot_bc");           \
+        return mgx::apply_op_dot3d_bc<mgx::CoefOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc,                                 \
+                                                               mgx::NO_WALL<real>, "apply_coef_dot_bc");                                     \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_laplace_dot_shift_wall_##SFX(mgx_ctx* ctx, const real* p, real* q, const int n[3], const real h[3], real s,       \
                                                         double* dev_work, double* dev_sum, int bc, const real beta[6]) {                     \
-        return mgx::apply_op_dot3d_wall<mgx::ShiftOp<real>, real>(ctx, p, nullptr, q, n, h, s, dev_work, dev_sum, bc, beta,                  \
+        return mgx::apply_op_dot3d_bc<mgx::ShiftOp<real>, real>(ctx, p, nullptr, q, n, h, s, dev_work, dev_sum, bc, beta,                    \
                                                                   "laplace_dot_shift_wall");                                                 \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_apply_coef_dot_wall_##SFX(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3],   \
                                                      real s, double* dev_work, double* dev_sum, int bc, const real beta[6]) {                \
-        return mgx::apply_op_dot3d_wall<mgx::CoefOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, beta, "apply_coef_dot_wall"); \
+        return mgx::apply_op_dot3d_bc<mgx::CoefOp<real>, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, beta, "apply_coef_dot_wall");   \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_cg_update_bc_##SFX(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q, const int n[3],                  \
                                               const double* dev_alpha, double* dev_work, double* dev_sum, int bc) {                          \

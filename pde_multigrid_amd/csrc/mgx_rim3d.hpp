@@ -1,8 +1,9 @@
-// mgx_rim3d.hpp -- what the kernels of the Neumann faces (mgx_rim3d.hip) share with a unit that builds them for
-// an operator policy of its own (mgx_cap3d.hip): the list of face points, the reflected star, the rim kernels that take a policy and
-// their host drivers.  Everything else of the faces -- the transfers, the vector kernels of the solve -- is in mgx_rim3d.hip.
-// The drivers of the convective and prescribed-flux walls (section 18) are here too: they launch the interior kernels of the unit
-// that instantiates them and the wall kernels of mgx_wall3d.hip through that unit's launch functions.
+// mgx_rim3d.hpp -- what the units that work on the face unknowns share (mgx_rim3d.hip, mgx_wall3d.hip, mgx_cap3d.hip; DESIGN.md
+// sections 15 and 18): the list of face points, the reflected star, the weight and the block sum of the solve's inner product, the
+// wall data, and the host drivers of the operator entries with a mask.  A driver launches the interior kernels of the unit that
+// instantiates it (mgx_rim3d.hip for ShiftOp and CoefOp, mgx_cap3d.hip for CapOp) and the face kernels of mgx_wall3d.hip, their one
+// home, through that unit's launch functions; a homogeneous Neumann face is a wall with beta = 0.  The transfers and the vector
+// kernels of the solve are in mgx_rim3d.hip.
 #pragma once
 #include "mgx_ops3d.hpp"
 
@@ -87,50 +88,6 @@ __device__ __forceinline__ Star7<real> rim_star(const real* __restrict__ p, cons
     for (u64 t_ = (u64)blockIdx.x * RIM_THREADS + threadIdx.x; t_ < (R).end[5]; t_ += (u64)gridDim.x * RIM_THREADS)        \
         if (int x, y, z; rim_point<real>(R, g, (unsigned)t_, x, y, z))
 
-// one colour pass on the face unknowns
-template <class real, class Op>
-__global__ void __launch_bounds__(RIM_THREADS) rim_relax3d_xs_kernel(real* __restrict__ v, const real* __restrict__ f, const real* __restrict__ a,
-                                                                     Rim R, Op op, int colour) {
-    const Geo<XSplit, real> g(R.sx, R.sy);
-    RIM_FOR_EACH_POINT(R, g, x, y, z) {
-        if (((x + y + z) & 1) != colour) continue;
-        const size_t i = g.row(y, z) + g.pos(x);
-        const Star7<real> vs = rim_star<real, false>(v, g, R, x, y, z);
-        Star7<real> as = {};
-        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
-        if constexpr (Op::HAS_C) v[i] = op.relax(vs, f[i], as, op.c[i]);  // (the capacity of the point itself: nothing mirrored)
-        else v[i] = op.relax(vs, f[i], as);
-    }
-}
-
-// r on the face unknowns (out == NULL: not stored) and the block's partial of its squares (partial == NULL: none): per thread in
-// list order, wavefront-wide shuffles, the four waves in a fixed order -- the same bits on every run
-template <class real, class Op, int MODE>
-__global__ void __launch_bounds__(RIM_THREADS) rim_residual3d_xs_kernel(const real* __restrict__ v, const real* __restrict__ f,
-                                                                        const real* __restrict__ a, real* __restrict__ out, Rim R, Op op,
-                                                                        double* __restrict__ partial) {
-    const Geo<XSplit, real> g(R.sx, R.sy);
-    double acc = 0.0;
-    RIM_FOR_EACH_POINT(R, g, x, y, z) {
-        const size_t i = g.row(y, z) + g.pos(x);
-        const Star7<real> vs = rim_star<real, true>(v, g, R, x, y, z);
-        Star7<real> as = {};
-        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
-        real t;
-        if constexpr (Op::HAS_C) t = op.template residual<MODE>(vs, f[i], as, op.c[i]);
-        else t = op.template residual<MODE>(vs, f[i], as);
-        if (out) out[i] = t;
-        acc += (double)t * (double)t;
-    }
-    if (partial) {  // (uniform over the launch)
-        __shared__ double part[RIM_THREADS / 64];
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) partial[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
-    }
-}
-
 // ------------------------------------------------------------------ the operator of the solve on the face unknowns (section 16)
 // The flexible CG of a hierarchy with a mask works in the inner product <a, b>_W = sum of W a b over all unknowns, W = 1/2 per
 // Neumann face an unknown lies on (the trapezoid weights A is symmetric in), 1 in the interior: the interior kernels of
@@ -149,132 +106,39 @@ __device__ __forceinline__ void rim_block_sum(double acc, double* part, double* 
     if (threadIdx.x == 0) *partial = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
-// q = A p = -(op's residual of (p, 0)) on the reflected star, partials of <p, q>_W
-template <class real, class Op, int MODE>
-__global__ void __launch_bounds__(RIM_THREADS) rim_apply_dot3d_xs_kernel(const real* __restrict__ p, const real* __restrict__ a,
-                                                                         real* __restrict__ q, Rim R, Op op, double* __restrict__ partial) {
-    const Geo<XSplit, real> g(R.sx, R.sy);
-    double acc = 0.0;
-    RIM_FOR_EACH_POINT(R, g, x, y, z) {
-        const Star7<real> vs = rim_star<real, true>(p, g, R, x, y, z);
-        Star7<real> as = {};
-        if constexpr (Op::HAS_A) as = rim_star<real, true>(a, g, R, x, y, z);
-        const size_t i = g.row(y, z) + g.pos(x);
-        real t;
-        if constexpr (Op::HAS_C) t = -op.template residual<MODE>(vs, (real)0, as, op.c[i]);
-        else t = -op.template residual<MODE>(vs, (real)0, as);  // negation is exact
-        q[i] = t;
-        acc += rim_weight(R, x, y, z) * ((double)vs.C * (double)t);
-    }
-    __shared__ double part[RIM_THREADS / 64];
-    rim_block_sum(acc, part, partial + blockIdx.x);
-}
-
 // =========================================================================== host side
 #define RIM_BC_CHECK(bc, what) MGX_REQUIRE((bc) >= 0 && (bc) <= 63, MGX_ERR_INVALID, "%s: bc = %d is outside 0 .. 63", what, bc)
-
-// ncycles red+black sweeps, each colour pass the interior launch and the rim launch of that colour
-template <class Op, class real>
-static int relax_op3d_bc(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int bc,
-                         const char* what, const real* c = nullptr) {
-    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h, MGX_ERR_INVALID, "%s: NULL argument", what);
-    RIM_BC_CHECK(bc, what);
-    if (!bc) return relax_op3d<Op, real>(ctx, v, f, a, n, h, s, ncycles, 0, 0, what, c);
-    const double sd = (double)s;
-    MGX_TRY_RET(rows_check(n, what, &sd, false));
-    MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "%s: ncycles = %d < 0", what, ncycles);
-    MGX_USE(ctx);
-    const Op op = make_op<Op, real>(ctx, h, s, c);
-    Rim R;
-    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
-    for (int p = 0; p < 2 * ncycles; p++) {
-        relax_op3d_pass<Op, real>(ctx, v, f, a, n, op, p & 1);
-        MGX_LAUNCH((rim_relax3d_xs_kernel<real, Op>), dim3(rim_blocks(R)), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, R, op, p & 1);
-    }
-    MGX_LAUNCH_CHECK();
-    return MGX_OK;
-}
-
-// r = the residual on all unknowns, 0 on the Dirichlet points (r == NULL: not stored); *dev_sumsq = the sum of its squares over all
-// unknowns (NULL: none).  The rim launch has at most as many blocks as the interior launch has partials: the work array of
-// mgx3dxs_krylov_work_elems doubles, twice that count, holds both.
-template <class Op, class real>
-static int residual_op3d_bc(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3], const real h[3], real s,
-                            double* dev_work, double* dev_sumsq, int bc, const char* what, const real* c = nullptr) {
-    MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h && (r || dev_sumsq) && (!dev_sumsq || dev_work), MGX_ERR_INVALID,
-                "%s: NULL argument", what);
-    RIM_BC_CHECK(bc, what);
-    if (!bc) return residual_op3d<Op, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, what, c);
-    const double sd = (double)s;
-    MGX_TRY_RET(rows_check(n, what, &sd));
-    MGX_USE(ctx);
-    Rim R;
-    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
-    if (r)  // every boundary point first: the Dirichlet points keep the 0
-        rim_zero3d_xs<real>(ctx, r, n);
-    const Op op = make_op<Op, real>(ctx, h, s, c);
-    MGX_TRY_RET((residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, op, dev_work, dev_sumsq, false)));
-    const dim3 g = krylov_grid(n);
-    const size_t interior = (size_t)g.x * g.y;
-    unsigned nb = rim_blocks(R);
-    if (dev_sumsq && nb > interior) nb = (unsigned)interior;
-    Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
-        MGX_LAUNCH((rim_residual3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, r, R, op,
-                   dev_sumsq ? dev_work + interior : (double*)nullptr);
-    });
-    MGX_LAUNCH_CHECK();
-    return dev_sumsq ? krylov_final(ctx, dev_work, interior + nb, 1, dev_sumsq) : MGX_OK;
-}
-
-template <class Op, class real>
-static int apply_op_dot3d_bc(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3], real s, double* dev_work,
-                             double* dev_sum, int bc, const char* what, const real* c = nullptr) {
-    MGX_REQUIRE(ctx && p && (a || !Op::HAS_A) && (c || !Op::HAS_C) && q && n && h && dev_work && dev_sum, MGX_ERR_INVALID, "%s: NULL argument", what);
-    RIM_BC_CHECK(bc, what);
-    if (!bc) return apply_op_dot3d<Op, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, what, c);
-    const double sd = (double)s;
-    MGX_TRY_RET(rows_check(n, what, &sd));
-    Rim R;
-    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
-    MGX_USE(ctx);
-    const Op op = make_op<Op, real>(ctx, h, s, c);
-    MGX_TRY_RET((residual_op3d_launch<Op, true>(ctx, p, (const real*)nullptr, a, q, n, op, dev_work, dev_sum, false)));
-    const dim3 g = krylov_grid(n);
-    const size_t interior = (size_t)g.x * g.y;
-    const unsigned nb = rim_blocks(R);
-    Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
-        MGX_LAUNCH((rim_apply_dot3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, p, a, q, R, op,
-                   dev_work + interior);
-    });
-    MGX_LAUNCH_CHECK();
-    return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
-}
 
 // ------------------------------------------------------------------ convective and prescribed-flux walls (section 18)
 // On a face of the mask the wall law a du/dn + beta u = g adds 2 (g - beta u_P) / h to the half cell's balance: the operator gains
 // the diagonal d_k = ((real)2 * beta_k) / h_axis(k) at the face unknowns, formed here once per call from the level's own spacings.
-// The kernels (mgx_wall3d.hip, their one home) take the six d_k by value; a wall launch REPLACES the rim launch of the same call,
-// the interior launches are the existing ones.  beta in the order of the mask's bits.
+// The face kernels (mgx_wall3d.hip, their one home) take the six d_k by value; a homogeneous Neumann face is the wall with
+// beta = 0, where they compute the plain point expression.  beta in the order of the mask's bits.
 template <class real>
 struct WallD {
     real d[6];
 };
 
+// the betas of a call without a wall (the _bc entries)
+template <class real>
+static const real NO_WALL[6] = {0, 0, 0, 0, 0, 0};
+
+// the launches over the face unknowns, defined and instantiated for the three policies in mgx_wall3d.hip
 template <class Op, class real>
-void wall_relax_launch(mgx_ctx* ctx, real* v, const real* f, const real* a, const Rim& R, const Op& op, const WallD<real>& w, int colour);
+void face_relax_launch(mgx_ctx* ctx, real* v, const real* f, const real* a, const Rim& R, const Op& op, const WallD<real>& w, int colour);
 template <class Op, class real>
-void wall_residual_launch(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* out, const Rim& R, const Op& op,
+void face_residual_launch(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* out, const Rim& R, const Op& op,
                           const WallD<real>& w, unsigned nb, double* partial);
 template <class Op, class real>
-void wall_apply_dot_launch(mgx_ctx* ctx, const real* p, const real* a, real* q, const Rim& R, const Op& op, const WallD<real>& w,
+void face_apply_dot_launch(mgx_ctx* ctx, const real* p, const real* a, real* q, const Rim& R, const Op& op, const WallD<real>& w,
                            unsigned nb, double* partial);
 
 // the wall data of a call against its mask: v[k] finite, >= 0 unless `flux`, 0 on a face whose bit is clear, and small enough for
 // the term ((real)2 * v[k]) / h_axis(k) the kernels work with to be finite in `real` (fp32: a beta near FLT_MAX, or a large one on a
-// fine level, would make it inf and the results NaN); *any = some v[k] != 0
+// fine level, would make it inf and the results NaN); *any = some v[k] != 0 (any == NULL: not asked)
 template <class real>
-static int wall_data_check(const real v[6], const real h[3], int bc, bool flux, const char* what, bool* any) {
-    *any = false;
+static int wall_data_check(const real v[6], const real h[3], int bc, bool flux, const char* what, bool* any = nullptr) {
+    if (any) *any = false;
     for (int k = 0; k < 6; k++) {
         MGX_REQUIRE(std::isfinite((double)v[k]) && (flux || v[k] >= 0), MGX_ERR_INVALID, "%s: %s[%d] = %g is not finite%s", what,
                     flux ? "g" : "beta", k, (double)v[k], flux ? "" : " and >= 0");
@@ -283,7 +147,7 @@ static int wall_data_check(const real v[6], const real h[3], int bc, bool flux, 
         MGX_REQUIRE(v[k] == 0 || std::isfinite((double)(((real)2 * v[k]) / h[k >> 1])), MGX_ERR_INVALID,
                     "%s: 2 * %s[%d] / h = 2 * %g / %g is not finite in this precision", what, flux ? "g" : "beta", k, (double)v[k],
                     (double)h[k >> 1]);
-        if (v[k] != 0) *any = true;
+        if (any && v[k] != 0) *any = true;
     }
     return MGX_OK;
 }
@@ -295,15 +159,16 @@ static WallD<real> wall_diagonal(const real beta[6], const real h[3]) {
     return w;
 }
 
-// relax_op3d_bc with the wall launch for the rim launch; all betas zero: relax_op3d_bc and nothing else
+// ---- the drivers of the entries with a mask: one per operation, for the _bc entries (beta = NO_WALL) and the _wall entries alike.
+// With bc = 0 (no beta can be non-zero then) nothing but the interior driver runs.
+// ncycles red+black sweeps, each colour pass the interior launch and the face launch of that colour
 template <class Op, class real>
-static int relax_op3d_wall(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int bc,
-                           const real beta[6], const char* what, const real* c = nullptr) {
+static int relax_op3d_bc(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int bc,
+                         const real beta[6], const char* what, const real* c = nullptr) {
     MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h && beta, MGX_ERR_INVALID, "%s: NULL argument", what);
     RIM_BC_CHECK(bc, what);
-    bool any;
-    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what, &any));
-    if (!any) return relax_op3d_bc<Op, real>(ctx, v, f, a, n, h, s, ncycles, bc, what, c);
+    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what));
+    if (!bc) return relax_op3d<Op, real>(ctx, v, f, a, n, h, s, ncycles, 0, 0, what, c);
     const double sd = (double)s;
     MGX_TRY_RET(rows_check(n, what, &sd, false));
     MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "%s: ncycles = %d < 0", what, ncycles);
@@ -314,27 +179,30 @@ static int relax_op3d_wall(mgx_ctx* ctx, real* v, const real* f, const real* a, 
     MGX_TRY_RET(rim_list<real>(n, bc, what, R));
     for (int p = 0; p < 2 * ncycles; p++) {
         relax_op3d_pass<Op, real>(ctx, v, f, a, n, op, p & 1);
-        wall_relax_launch<Op, real>(ctx, v, f, a, R, op, w, p & 1);
+        face_relax_launch<Op, real>(ctx, v, f, a, R, op, w, p & 1);
     }
     MGX_LAUNCH_CHECK();
     return MGX_OK;
 }
 
+// r = the residual on all unknowns, 0 on the Dirichlet points (r == NULL: not stored); *dev_sumsq = the sum of its squares over all
+// unknowns (NULL: none).  The face launch has at most as many blocks as the interior launch has partials: the work array of
+// mgx3dxs_krylov_work_elems doubles, twice that count, holds both.
 template <class Op, class real>
-static int residual_op3d_wall(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3], const real h[3], real s,
-                              double* dev_work, double* dev_sumsq, int bc, const real beta[6], const char* what, const real* c = nullptr) {
+static int residual_op3d_bc(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* r, const int n[3], const real h[3], real s,
+                            double* dev_work, double* dev_sumsq, int bc, const real beta[6], const char* what, const real* c = nullptr) {
     MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h && (r || dev_sumsq) && (!dev_sumsq || dev_work) && beta,
                 MGX_ERR_INVALID, "%s: NULL argument", what);
     RIM_BC_CHECK(bc, what);
-    bool any;
-    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what, &any));
-    if (!any) return residual_op3d_bc<Op, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, what, c);
+    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what));
+    if (!bc) return residual_op3d<Op, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, what, c);
     const double sd = (double)s;
     MGX_TRY_RET(rows_check(n, what, &sd));
     MGX_USE(ctx);
     Rim R;
     MGX_TRY_RET(rim_list<real>(n, bc, what, R));
-    if (r) rim_zero3d_xs<real>(ctx, r, n);
+    if (r)  // every boundary point first: the Dirichlet points keep the 0
+        rim_zero3d_xs<real>(ctx, r, n);
     const Op op = make_op<Op, real>(ctx, h, s, c);
     const WallD<real> w = wall_diagonal<real>(beta, h);
     MGX_TRY_RET((residual_op3d_launch<Op, false>(ctx, v, f, a, r, n, op, dev_work, dev_sumsq, false)));
@@ -342,20 +210,20 @@ static int residual_op3d_wall(mgx_ctx* ctx, const real* v, const real* f, const 
     const size_t interior = (size_t)g.x * g.y;
     unsigned nb = rim_blocks(R);
     if (dev_sumsq && nb > interior) nb = (unsigned)interior;
-    wall_residual_launch<Op, real>(ctx, v, f, a, r, R, op, w, nb, dev_sumsq ? dev_work + interior : (double*)nullptr);
+    face_residual_launch<Op, real>(ctx, v, f, a, r, R, op, w, nb, dev_sumsq ? dev_work + interior : (double*)nullptr);
     MGX_LAUNCH_CHECK();
     return dev_sumsq ? krylov_final(ctx, dev_work, interior + nb, 1, dev_sumsq) : MGX_OK;
 }
 
+// q = A p on all unknowns and *dev_sum = <p, q>_W
 template <class Op, class real>
-static int apply_op_dot3d_wall(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3], real s, double* dev_work,
-                               double* dev_sum, int bc, const real beta[6], const char* what, const real* c = nullptr) {
+static int apply_op_dot3d_bc(mgx_ctx* ctx, const real* p, const real* a, real* q, const int n[3], const real h[3], real s, double* dev_work,
+                             double* dev_sum, int bc, const real beta[6], const char* what, const real* c = nullptr) {
     MGX_REQUIRE(ctx && p && (a || !Op::HAS_A) && (c || !Op::HAS_C) && q && n && h && dev_work && dev_sum && beta, MGX_ERR_INVALID,
                 "%s: NULL argument", what);
     RIM_BC_CHECK(bc, what);
-    bool any;
-    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what, &any));
-    if (!any) return apply_op_dot3d_bc<Op, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, bc, what, c);
+    MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what));
+    if (!bc) return apply_op_dot3d<Op, real>(ctx, p, a, q, n, h, s, dev_work, dev_sum, what, c);
     const double sd = (double)s;
     MGX_TRY_RET(rows_check(n, what, &sd));
     Rim R;
@@ -367,7 +235,7 @@ static int apply_op_dot3d_wall(mgx_ctx* ctx, const real* p, const real* a, real*
     const dim3 g = krylov_grid(n);
     const size_t interior = (size_t)g.x * g.y;
     const unsigned nb = rim_blocks(R);
-    wall_apply_dot_launch<Op, real>(ctx, p, a, q, R, op, w, nb, dev_work + interior);
+    face_apply_dot_launch<Op, real>(ctx, p, a, q, R, op, w, nb, dev_work + interior);
     MGX_LAUNCH_CHECK();
     return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
 }

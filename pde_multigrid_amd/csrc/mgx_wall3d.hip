@@ -1,23 +1,24 @@
-// mgx_wall3d.hip -- CONVECTIVE (Robin) and PRESCRIBED-FLUX walls for the shifted, the variable-coefficient and the capacity
-// operator, x-split layout.  DESIGN.md section 18.
+// mgx_wall3d.hip -- the operators on the FACE UNKNOWNS: homogeneous Neumann faces and CONVECTIVE (Robin) and
+// PRESCRIBED-FLUX walls (section 18) for the shifted, the variable-coefficient and the capacity operator, x-split layout.
 //
-// On a face flagged in the Neumann mask the wall law is  a du/dn + beta u = g  (n outward, beta >= 0, both constants per face, in
+// At an unknown on a face of the mask every operator is the interior's point expression on a star whose out-of-range entry is
+// replaced by the opposite one (mgx_rim3d.hip describes the list of face points and the launch).  On such a face the wall law is  a du/dn + beta u = g  (n outward, beta >= 0, both constants per face, in
 // the units of the hierarchy's operator div(a grad u)).  The mirrored star of section 15 is the flux through the inner half-face of
 // the half cell at a face unknown; the wall adds 2 (g - beta u_P) / h per wall face the point lies on, h the spacing along that
 // face's axis.  So the operator gains a DIAGONAL term at the face unknowns and nothing else changes:
 //   d_k  = ((real)2 * beta_k) / h_axis(k)     once per call, on the host, from the level's own spacings (mgx_rim3d.hpp)
 //   d(P) = the sum, in the order x, y, z, of the d_k of the faces P lies on (the d_k of a face whose bit is clear is 0)
-//   d(P) == 0: the point as the rim kernels of mgx_rim3d.hpp compute it, bit for bit (Op::relax / Op::residual)
+//   d(P) == 0: the interior's point expression, Op::relax / Op::residual -- every point of a call without a wall (all betas zero:
+//              the homogeneous Neumann faces), which therefore has the bits of the mirrored star alone
 //   d(P) != 0: the operator's own point expression with the effective shift se = s + d(P) (CapOp: s * c_P + d(P)) where it takes
 //              s -- Op::relax_wall / Op::residual_wall of mgx_ops3d.hpp; the shifted smoother then divides in `real`
 // g touches the right-hand side of level 0 only: f[P] -= ((real)2 * g_k) / h_axis(k), face by face in the order x, y, z
 // (wall_rhs3d_xs_kernel).
 //
-// The kernels are the three rim kernels that take an operator policy, with the six d_k by value, instantiated for ShiftOp, CoefOp
-// and CapOp in this unit only; they walk the same list of face points (Rim, rim_point), read the same reflected stars and keep the
-// order of the partial sums.  The host drivers that put a wall launch where a call had its rim launch are in mgx_rim3d.hpp and are
-// instantiated, with the interior kernels, in mgx_rim3d.hip and mgx_cap3d.hip: they reach the kernels through the launch functions
-// at the end of this file.  No LDS beyond the partial sums' four doubles, no scratch.
+// The three kernels -- colour pass, residual, apply + dot -- take an operator policy and the six d_k by value and are instantiated
+// for ShiftOp, CoefOp and CapOp in this unit only: one instance per operator and precision serves the _bc and the _wall entries.
+// The host drivers are in mgx_rim3d.hpp and are instantiated, with the interior kernels, in mgx_rim3d.hip and mgx_cap3d.hip: they
+// reach the kernels through the launch functions at the end of this file.  No LDS beyond the partial sums' four doubles, no scratch.
 #include "mgx_rim3d.hpp"
 
 namespace mgx {
@@ -33,7 +34,7 @@ __device__ __forceinline__ real wall_diag(const WallD<real>& w, const Rim& R, in
 
 // one colour pass on the face unknowns
 template <class real, class Op>
-__global__ void __launch_bounds__(RIM_THREADS) wall_relax3d_xs_kernel(real* __restrict__ v, const real* __restrict__ f, const real* __restrict__ a,
+__global__ void __launch_bounds__(RIM_THREADS) face_relax3d_xs_kernel(real* __restrict__ v, const real* __restrict__ f, const real* __restrict__ a,
                                                                       Rim R, Op op, WallD<real> w, int colour) {
     const Geo<XSplit, real> g(R.sx, R.sy);
     RIM_FOR_EACH_POINT(R, g, x, y, z) {
@@ -54,10 +55,10 @@ __global__ void __launch_bounds__(RIM_THREADS) wall_relax3d_xs_kernel(real* __re
     }
 }
 
-// r on the face unknowns (out == NULL: not stored) and the block's partial of its squares (partial == NULL: none), in the order of
-// rim_residual3d_xs_kernel
+// r on the face unknowns (out == NULL: not stored) and the block's partial of its squares (partial == NULL: none): per thread in
+// list order, wavefront-wide shuffles, the four waves in a fixed order -- the same bits on every run
 template <class real, class Op, int MODE>
-__global__ void __launch_bounds__(RIM_THREADS) wall_residual3d_xs_kernel(const real* __restrict__ v, const real* __restrict__ f,
+__global__ void __launch_bounds__(RIM_THREADS) face_residual3d_xs_kernel(const real* __restrict__ v, const real* __restrict__ f,
                                                                          const real* __restrict__ a, real* __restrict__ out, Rim R, Op op,
                                                                          WallD<real> w, double* __restrict__ partial) {
     const Geo<XSplit, real> g(R.sx, R.sy);
@@ -85,7 +86,7 @@ __global__ void __launch_bounds__(RIM_THREADS) wall_residual3d_xs_kernel(const r
 
 // q = A p = -(the residual of (p, 0)) on the reflected star, partials of <p, q>_W
 template <class real, class Op, int MODE>
-__global__ void __launch_bounds__(RIM_THREADS) wall_apply_dot3d_xs_kernel(const real* __restrict__ p, const real* __restrict__ a,
+__global__ void __launch_bounds__(RIM_THREADS) face_apply_dot3d_xs_kernel(const real* __restrict__ p, const real* __restrict__ a,
                                                                           real* __restrict__ q, Rim R, Op op, WallD<real> w,
                                                                           double* __restrict__ partial) {
     const Geo<XSplit, real> g(R.sx, R.sy);
@@ -128,34 +129,34 @@ __global__ void __launch_bounds__(RIM_THREADS) wall_rhs3d_xs_kernel(real* __rest
 
 // =========================================================================== host side
 template <class Op, class real>
-void wall_relax_launch(mgx_ctx* ctx, real* v, const real* f, const real* a, const Rim& R, const Op& op, const WallD<real>& w, int colour) {
-    MGX_LAUNCH((wall_relax3d_xs_kernel<real, Op>), dim3(rim_blocks(R)), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, R, op, w, colour);
+void face_relax_launch(mgx_ctx* ctx, real* v, const real* f, const real* a, const Rim& R, const Op& op, const WallD<real>& w, int colour) {
+    MGX_LAUNCH((face_relax3d_xs_kernel<real, Op>), dim3(rim_blocks(R)), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, R, op, w, colour);
 }
 
 template <class Op, class real>
-void wall_residual_launch(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* out, const Rim& R, const Op& op,
+void face_residual_launch(mgx_ctx* ctx, const real* v, const real* f, const real* a, real* out, const Rim& R, const Op& op,
                           const WallD<real>& w, unsigned nb, double* partial) {
     Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
-        MGX_LAUNCH((wall_residual3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, out, R, op,
+        MGX_LAUNCH((face_residual3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, v, f, a, out, R, op,
                    w, partial);
     });
 }
 
 template <class Op, class real>
-void wall_apply_dot_launch(mgx_ctx* ctx, const real* p, const real* a, real* q, const Rim& R, const Op& op, const WallD<real>& w,
+void face_apply_dot_launch(mgx_ctx* ctx, const real* p, const real* a, real* q, const Rim& R, const Op& op, const WallD<real>& w,
                            unsigned nb, double* partial) {
     Op::with_mode(op.mode, [&](auto m) __attribute__((always_inline)) {
-        MGX_LAUNCH((wall_apply_dot3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, p, a, q, R, op, w,
+        MGX_LAUNCH((face_apply_dot3d_xs_kernel<real, Op, decltype(m)::value>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, p, a, q, R, op, w,
                    partial);
     });
 }
 
 #define MGX_WALL3D_LAUNCHERS(Op, real)                                                                                                    \
-    template void wall_relax_launch<Op<real>, real>(mgx_ctx*, real*, const real*, const real*, const Rim&, const Op<real>&,               \
+    template void face_relax_launch<Op<real>, real>(mgx_ctx*, real*, const real*, const real*, const Rim&, const Op<real>&,               \
                                                     const WallD<real>&, int);                                                             \
-    template void wall_residual_launch<Op<real>, real>(mgx_ctx*, const real*, const real*, const real*, real*, const Rim&, const Op<real>&, \
+    template void face_residual_launch<Op<real>, real>(mgx_ctx*, const real*, const real*, const real*, real*, const Rim&, const Op<real>&, \
                                                        const WallD<real>&, unsigned, double*);                                            \
-    template void wall_apply_dot_launch<Op<real>, real>(mgx_ctx*, const real*, const real*, real*, const Rim&, const Op<real>&,            \
+    template void face_apply_dot_launch<Op<real>, real>(mgx_ctx*, const real*, const real*, real*, const Rim&, const Op<real>&,            \
                                                         const WallD<real>&, unsigned, double*);
 MGX_WALL3D_LAUNCHERS(ShiftOp, float)
 MGX_WALL3D_LAUNCHERS(ShiftOp, double)

@@ -3,7 +3,7 @@
 
 --mode kernels (for rocprofv3, counters off): on the same --n^3 arrays, in one process, alternating, --reps times each after
 --warmup rounds: one sweep of mgx3dxs_relax_shift_bc with bc = 63 (per colour the interior launch relax_op3d_xs_kernel<double,
-ShiftOp, 4, 4> and the face launch rim_relax3d_xs_kernel<double, ShiftOp>), one with bc = 0 (the interior launches alone),
+ShiftOp, 4, 4> and the face launch face_relax3d_xs_kernel<double, ShiftOp>), one with bc = 0 (the interior launches alone),
 the same two with mgx3dxs_relax_coef_bc, and residual_shift_bc / restrict_bc / interpolate_correct_bc with bc = 63.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/neumann_kernels.py --mode kernels

@@ -2,10 +2,11 @@
 """Workloads behind DESIGN.md 18 (convective and prescribed-flux walls), fp64 on the unit cube, mask 63.
 
 --mode kernels (for rocprofv3, counters off): on the same --n^3 arrays, in one process, alternating, --reps times each after
---warmup rounds: one sweep of mgx3dxs_relax_shift_wall with beta = 1 on every face (per colour the interior launch and the wall
-launch wall_relax3d_xs_kernel<double, ShiftOp>) and one of mgx3dxs_relax_shift_bc (the interior launch and the Neumann rim launch
-rim_relax3d_xs_kernel<double, ShiftOp>); the same pair with the coefficient entries; residual_shift_wall and residual_shift_bc
-(wall_residual3d_xs_kernel / rim_residual3d_xs_kernel); and wall_rhs.
+--warmup rounds: one sweep of mgx3dxs_relax_shift_wall with beta = 1 on every face (per colour the interior launch and the launch
+over the face unknowns, face_relax3d_xs_kernel<double, ShiftOp>) and one of mgx3dxs_relax_shift_bc (the same two launches with
+six zero diagonals); the same pair with the coefficient entries; residual_shift_wall and residual_shift_bc
+(face_residual3d_xs_kernel); and wall_rhs.  One kernel serves a round's _wall call and its _bc call: in the trace the launches
+of a colour pass alternate in pairs, _wall first, those of the residual one by one.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/wall_kernels.py --mode kernels
 
