@@ -86,6 +86,11 @@ typedef struct mgGraphFlags {
 #define MG_KRYLOV_NONE 0
 #define MG_KRYLOV_CG 1
 #define MG_KRYLOV_WEIGHTED 2
+/* the face coefficients of the variable-coefficient operators (_set_face_mean): the arithmetic mean (aP + aQ) / 2 of the two
+ * nodes' values -- a material boundary on a node plane -- or the harmonic mean 2 aP aQ / (aP + aQ) -- node-valued materials (voxel
+ * data), the boundary midway between two nodes */
+#define MG_FACE_MEAN_ARITHMETIC 0
+#define MG_FACE_MEAN_HARMONIC 1
 #define MG_NORM_HISTORY 255 /* residual-norm history entries a distributed hierarchy keeps on the device */
 #define MG_DECLARE(R, real)                                                                              \
     /* ------------------------------------------------------------------ 3D ------ */                  \
@@ -121,7 +126,14 @@ typedef struct mgGraphFlags {
                        /* change, or the context's parameters, mgx_ctx_generation).  Default 0.       */ \
         int capturing;                                                                                   \
         void* graph_exec[MG_MAX_LEVELS];                                                                 \
-        long long graph_key[MG_MAX_LEVELS - 3]; /* unused */                                             \
+        /* the mean the face coefficients of a hierarchy with a coefficient are formed by, MG_FACE_MEAN_* */\
+        /* (default 0 = arithmetic: every call does what it did without this member).  Set it through    */\
+        /* _set_face_mean, which validates.  It takes the first four bytes of the unused graph_key: every */\
+        /* member keeps its offset and the struct its size, and `shift` stays the last member.           */\
+        union {                                                                                          \
+            long long graph_key[MG_MAX_LEVELS - 3]; /* unused */                                         \
+            int face_mean;                                                                               \
+        };                                                                                               \
         /* internal: the walls of _set_wall (beta and g of the six faces), or NULL (none).  Owned by     */\
         /* _set_wall, freed by _destroy.  Like cap below it takes eight bytes of the unused graph_key:   */\
         /* every member keeps its offset and the struct its size.                                        */\
@@ -276,6 +288,23 @@ typedef struct mgGraphFlags {
     int mgMultiGrid3D_##R##_set_capacity(mgMultiGrid3D_##R* mg, const real* host_c);                     \
     /* the capacity of level gridID as a host array in the reference layout                              */ \
     int mgMultiGrid3D_##R##_download_capacity(mgMultiGrid3D_##R* mg, int gridID, real* host);            \
+    /* Harmonic-mean face coefficients (an addition; mgx3dxs_*_hmean of mgx.h).  mode =    */ \
+    /* MG_FACE_MEAN_HARMONIC: wherever the hierarchy's operator is the coefficient or the capacity one, */ \
+    /* every level is discretised with the face coefficient 2 aP aQ / (aP + aQ) -- Relax,               */ \
+    /* CalculateResidual (ResidualNorm, download_residual), VCycle, FullMultiGridVCycle, PCG (krylov 0, */ \
+    /* 1 and, with a mask, 2), BackwardEuler, with walls, a capacity and use_graph, on full and semi-   */ \
+    /* coarsened hierarchies, launch for launch the route of the arithmetic operator with the _hmean    */ \
+    /* entries.  a goes down the levels exactly as before.  MG_FACE_MEAN_ARITHMETIC (the default): the  */ \
+    /* operators of _set_coefficient.  Any other mode: MGX_ERR_INVALID.  It may be called before or     */ \
+    /* after _set_coefficient and has an effect only while the hierarchy has a coefficient: a plain or  */ \
+    /* shifted hierarchy runs what it ran, launch for launch.  The products aP * aQ have to be normal   */ \
+    /* and finite in `real`: while the mode is harmonic _set_coefficient also refuses an a[i] whose     */ \
+    /* square is below the smallest normal number or not finite, and _set_face_mean(HARMONIC) checks    */ \
+    /* the coefficient a hierarchy already has (MGX_ERR_INVALID naming the value; the hierarchy stays   */ \
+    /* as it was; full weighting keeps the coarse coefficients inside the fine range).  A change of the */ \
+    /* mode syncs and drops the captured graphs.  Everything refused before stays refused (PCG_mixed    */ \
+    /* with a coefficient among it).  Blocking.  The mode is the member `face_mean`.                    */ \
+    int mgMultiGrid3D_##R##_set_face_mean(mgMultiGrid3D_##R* mg, int mode);                              \
     int mgMultiGrid3D_##R##_create(mgx_ctx* ctx, const int finestGridSizeXYZ[3], const real range[6],     \
                                    mgMultiGrid3D_##R** out);                                             \
     int mgMultiGrid3D_##R##_create_layout(mgx_ctx* ctx, const int finestGridSizeXYZ[3],                  \

@@ -796,7 +796,35 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
                                          real* q, const int n[3], const real h[3], real s,              \
                                          double* dev_work, double* dev_sum, int bc, const real beta[6]);\
     int mgx3dxs_wall_rhs_##SFX(mgx_ctx* ctx, real* f, const int n[3], const real h[3], const real g[6], \
-                               int bc);
+                               int bc);                                                                 \
+    /* ---- harmonic-mean face coefficients for the coefficient and the capacity operator, x-split      */ \
+    /* layout (csrc/mgx_hmean3d.hip).  An addition: the discretisation for a coefficient  */ \
+    /* that belongs to the nodes (voxel data), where the interface lies midway between two nodes and a  */ \
+    /* face carries the series conductance 2 aP aQ / (aP + aQ).  Arithmetic: the _coef / _cap           */ \
+    /* expressions above with AW = (real)4 * ((aO * aC) / (aO + aC)) (likewise AE .. AU) where they     */ \
+    /* form AW = aO + aC -- a plain division in `real`; nothing else differs.  A face has the same bits */ \
+    /* seen from either node: the operator is symmetric bit for bit.  A constant coefficient 2^k gives  */ \
+    /* the bits of the _coef / _cap entries.  One set of entries, in the _wall form: each is its        */ \
+    /* _cap_wall namesake (relax_hmean_from_zero: relax_cap_from_zero), argument for argument and with  */ \
+    /* that entry's contract, but c may be NULL: no capacity (the shift is s itself).  bc = 0 is the    */ \
+    /* interior form, all betas zero the _bc form.  The values of a are not checked here: the products  */ \
+    /* aP * aQ have to be normal and finite in `real` (mgMultiGrid3D_<r>_set_face_mean sees to it).     */ \
+    /* mgx_ctx_last_relax_kernel reports relax_hmean3d_xs_kernel / relax_hmean_zero3d_xs_kernel, with a */ \
+    /* capacity relax_hmean_cap3d_xs_kernel / relax_hmean_cap_zero3d_xs_kernel.                         */ \
+    int mgx3dxs_relax_hmean_wall_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,             \
+                                       const real* c, const int n[3], const real h[3], real s,          \
+                                       int ncycles, int bc, const real beta[6]);                        \
+    int mgx3dxs_relax_hmean_from_zero_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,        \
+                                            const real* c, const int n[3], const real h[3], real s,     \
+                                            int ncycles, int rim_is_zero);                              \
+    int mgx3dxs_residual_hmean_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a,    \
+                                          const real* c, real* r, const int n[3], const real h[3],      \
+                                          real s, double* dev_work, double* dev_sumsq, int bc,          \
+                                          const real beta[6]);                                          \
+    int mgx3dxs_apply_hmean_dot_wall_##SFX(mgx_ctx* ctx, const real* p, const real* a, const real* c,   \
+                                           real* q, const int n[3], const real h[3], real s,            \
+                                           double* dev_work, double* dev_sum, int bc,                   \
+                                           const real beta[6]);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)

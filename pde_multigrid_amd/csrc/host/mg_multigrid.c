@@ -1,5 +1,7 @@
 /* mg_multigrid.c -- C host layer of include/mg_multigrid.h: stamps the 1D/2D/3D hierarchy and
  * cycle code for float and double.  Compiled with gcc -std=c11 -ffp-contract=off. */
+#include <float.h>
+
 #include "mg_common.h"
 
 /* numGrids = log2(minSize - 1) truncated to int                   N3/MultiGrid3D.cpp:33-34 */

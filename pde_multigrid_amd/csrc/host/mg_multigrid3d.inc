@@ -290,6 +290,23 @@ static const REAL* MG_CAT(cap_of3_, R)(const MGRID* mg, const GRID* g) {
     return NULL;
 }
 
+/* "this hierarchy's faces carry the harmonic mean" (mg_multigrid.h _set_face_mean, DESIGN.md 19): the mode counts only where there
+ * is a coefficient, and then every operator call takes the _hmean entries, with the capacity of the grid or NULL */
+static int MG_CAT(harm3_, R)(const MGRID* mg) { return mg->face_mean == MG_FACE_MEAN_HARMONIC && MG_CAT(has_coef3_, R)(mg); }
+static const REAL* MG_CAT(harm_cap3_, R)(const MGRID* mg, const GRID* g) { return MG_CAT(has_cap3_, R)(mg) ? MG_CAT(cap_of3_, R)(mg, g) : NULL; }
+
+/* what the harmonic mean needs of a coefficient: the products aP * aQ normal and finite in REAL, that is, every square */
+static int MG_CAT(harm_range3_, R)(const REAL* host_a, size_t vol, const char* what) {
+    const REAL tiny = sizeof(REAL) == 4 ? (REAL)FLT_MIN : (REAL)DBL_MIN;
+    for (size_t i = 0; i < vol; i++) {
+        const REAL sq = host_a[i] * host_a[i];
+        MG_REQUIRE(isfinite((double)sq) && sq >= tiny, MGX_ERR_INVALID,
+                   "%s: a[%zu] = %g is outside the range of the harmonic face mean: its square %g is not a normal, finite number of this "
+                   "precision", what, i, (double)host_a[i], (double)sq);
+    }
+    return MGX_OK;
+}
+
 /* what a coefficient needs of the hierarchy (the members are public: checked where the coefficient is used, too) */
 static int MG_CAT(coef_ok3_, R)(const MGRID* mg, const char* what) {
     MG_REQUIRE(isfinite((double)mg->shift) && mg->shift >= 0, MGX_ERR_INVALID, "%s: the shift %g is not finite and >= 0", what, (double)mg->shift);
@@ -354,6 +371,9 @@ static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, con
     const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
     const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R); /* the _wall entries with the level's own spacings (DESIGN.md 18) */
     const int faces = mg->bc || wall;                    /* (betas without a mask: the entry refuses them) */
+    if (MG_CAT(harm3_, R)(mg))
+        return MG_CAT(mgx3dxs_residual_hmean_wall_, R)(mg->ctx, v, f, g->d_a, MG_CAT(harm_cap3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift, dev_work,
+                                                       dev_sumsq, mg->bc, wb);
     if (MG_CAT(has_cap3_, R)(mg))
         return MG_CAT(mgx3dxs_residual_cap_wall_, R)(mg->ctx, v, f, g->d_a, MG_CAT(cap_of3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift, dev_work,
                                                      dev_sumsq, mg->bc, wb);
@@ -372,6 +392,9 @@ static int MG_CAT(op_apply_dot3_, R)(MGRID* mg, const GRID* g, const REAL* p, RE
     const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
     const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R);
     const int faces = mg->bc || wall; /* (betas without a mask: the entry refuses them) */
+    if (MG_CAT(harm3_, R)(mg)) /* (with bc = 0 the entry is the interior entry) */
+        return MG_CAT(mgx3dxs_apply_hmean_dot_wall_, R)(mg->ctx, p, g->d_a, MG_CAT(harm_cap3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
+                                                        dev_sum, mg->bc, wb);
     if (MG_CAT(has_cap3_, R)(mg)) /* (with bc = 0 the entry is the interior entry) */
         return MG_CAT(mgx3dxs_apply_cap_dot_wall_, R)(mg->ctx, p, g->d_a, MG_CAT(cap_of3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
                                                       dev_sum, mg->bc, wb);
@@ -423,6 +446,7 @@ int FN(set_coefficient)(MGRID* mg, const REAL* host_a) {
     for (size_t i = 0; i < vol; i++)
         MG_REQUIRE(isfinite((double)host_a[i]) && host_a[i] > 0, MGX_ERR_INVALID, "set_coefficient: a[%zu] = %g is not finite and > 0", i,
                    (double)host_a[i]);
+    if (mg->face_mean == MG_FACE_MEAN_HARMONIC) MG_TRY(MG_CAT(harm_range3_, R)(host_a, vol, "set_coefficient"));
     const int had = MG_CAT(has_coef3_, R)(mg);
     int st = MGX_OK;
     if (!had) { /* (nothing of a captured cycle is in flight any more) */
@@ -453,6 +477,30 @@ int FN(download_coefficient)(MGRID* mg, int gridID, REAL* host) {
     GRID* g = mg->grids3D[gridID];
     MG_REQUIRE(g->d_a, MGX_ERR_INVALID, "download_coefficient: the hierarchy has no coefficient");
     return MG_CAT(get3_, R)(mg, g, g->d_a, host);
+}
+
+/* The mean of the face coefficients (mg_multigrid.h).  The captured graphs hold the kernels of the mean they were captured under:
+ * a change of the mode drops them.  A coefficient the hierarchy already has is checked against the harmonic mean's range first. */
+int FN(set_face_mean)(MGRID* mg, int mode) {
+    MG_REQUIRE(mg && mg->grids3D && mg->maxGrids >= 1, MGX_ERR_INVALID, "set_face_mean: NULL");
+    MG_REQUIRE(mode == MG_FACE_MEAN_ARITHMETIC || mode == MG_FACE_MEAN_HARMONIC, MGX_ERR_INVALID,
+               "set_face_mean: the mode %d is neither MG_FACE_MEAN_ARITHMETIC (0) nor MG_FACE_MEAN_HARMONIC (1)", mode);
+    if (mode == mg->face_mean) return MGX_OK;
+    if (mode == MG_FACE_MEAN_HARMONIC && MG_CAT(has_coef3_, R)(mg)) {
+        const size_t vol = MG_CAT(vol3_, R)(mg->grids3D[0]);
+        REAL* host = (REAL*)malloc(vol * sizeof(REAL));
+        MG_REQUIRE(host, MGX_ERR_NOMEM, "set_face_mean: out of host memory");
+        int st = FN(download_coefficient)(mg, 0, host);
+        if (!st) st = MG_CAT(harm_range3_, R)(host, vol, "set_face_mean");
+        free(host);
+        MG_TRY(st);
+    }
+    if (MG_CAT(has_coef3_, R)(mg)) { /* (a plain or shifted hierarchy captured nothing that depends on the mode) */
+        MG_TRY(mgx_ctx_sync(mg->ctx)); /* (nothing of a captured cycle is in flight any more) */
+        MG_CAT(coef_drop_graphs3_, R)(mg);
+    }
+    mg->face_mean = mode;
+    return MGX_OK;
 }
 
 /* The capacity (mg_multigrid.h).  The captured graphs hold the arrays of every level: every call drops them. */
@@ -642,6 +690,9 @@ int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
     const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
     const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R);
     const int faces = mg->bc || wall; /* (betas without a mask: the entry refuses them) */
+    if (MG_CAT(harm3_, R)(mg))
+        return MG_CAT(mgx3dxs_relax_hmean_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(harm_cap3_, R)(mg, curGrid),
+                                                    curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb);
     if (MG_CAT(has_cap3_, R)(mg))
         return MG_CAT(mgx3dxs_relax_cap_wall_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(cap_of3_, R)(mg, curGrid),
                                                   curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb);
@@ -779,7 +830,10 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
     const int bc = mg->bc; /* Neumann faces: no from-zero shortcut (v := 0 on all points, then Relax), the stored-residual route */
     if (!bc && v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
         if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
-        if (MG_CAT(has_cap3_, R)(mg))
+        if (MG_CAT(harm3_, R)(mg))
+            MG_TRY(MG_CAT(mgx3dxs_relax_hmean_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, MG_CAT(harm_cap3_, R)(mg, fine),
+                                                             fine->sizeXYZ, h, mg->shift, v1, mg->v_rim_zero[gridID]));
+        else if (MG_CAT(has_cap3_, R)(mg))
             MG_TRY(MG_CAT(mgx3dxs_relax_cap_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, ((CAPTAB*)mg->cap)->d_c[gridID],
                                                            fine->sizeXYZ, h, mg->shift, v1, mg->v_rim_zero[gridID]));
         else if (coef)
@@ -1069,6 +1123,9 @@ static int MG_CAT(pcg_true_sumsq3_, R)(MGRID* mg, const REAL* x, const REAL* b, 
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
     if (MG_CAT(wall_beta3_, R)(mg)) /* walls: the hierarchy's residual, not stored */
         MG_TRY(MG_CAT(op_residual3_, R)(mg, g, x, b, NULL, mg->pcg_work, mg->pcg_state + MGX_CG_RR));
+    else if (MG_CAT(harm3_, R)(mg))
+        MG_TRY(MG_CAT(mgx3dxs_residual_hmean_wall_, R)(mg->ctx, x, b, g->d_a, MG_CAT(harm_cap3_, R)(mg, g), NULL, g->sizeXYZ, h, mg->shift,
+                                                       mg->pcg_work, mg->pcg_state + MGX_CG_RR, mg->bc, MG_CAT(no_wall3_, R)));
     else if (MG_CAT(has_cap3_, R)(mg))
         MG_TRY(MG_CAT(mgx3dxs_residual_cap_bc_, R)(mg->ctx, x, b, g->d_a, ((CAPTAB*)mg->cap)->d_c[0], NULL, g->sizeXYZ, h, mg->shift,
                                                    mg->pcg_work, mg->pcg_state + MGX_CG_RR, mg->bc));

@@ -5,6 +5,7 @@
 // the kernels of the face unknowns (Neumann faces, section 15, and the walls of section 18) from all three: the point expressions
 // exist once.  A policy's relax_wall / residual_wall take the zeroth-order coefficient of the point, se, as an argument; CoefOp's and
 // CapOp's relax / residual are these with se = s or s * c_P, ShiftOp's relax keeps its own form with the level's denominator.
+// HarmOp and HarmCapOp (mgx_hmean3d.hip, section 19) are CoefOp and CapOp with harmonic-mean face coefficients.
 #pragma once
 #include "mgx_stencil3d.hpp"
 
@@ -67,23 +68,36 @@ struct ShiftOp {
     }
 };
 
+// the point expressions of the conservative 7-point form from its six (doubled) face coefficients AW .. AU on
 template <class real>
-__device__ __forceinline__ real relax_coef3d_point(real O, real E, real N, real S, real D, real U, real f, real aO, real aE, real aN, real aS,
-                                                   real aD, real aU, real aC, real qx, real qy, real qz, real s) {
-    const real AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC;
+__device__ __forceinline__ real relax_faces3d_point(real O, real E, real N, real S, real D, real U, real f, real AW, real AE, real AN, real AS,
+                                                    real AD, real AU, real qx, real qy, real qz, real s) {
     const real den = ((qx * (AW + AE) + qy * (AN + AS)) + qz * (AD + AU)) + s;
     const real num = ((qx * (AW * O + AE * E) + qy * (AN * N + AS * S)) + qz * (AD * D + AU * U)) - f;
     return num / den;
 }
 
 template <class real>
-__device__ __forceinline__ real residual_coef3d_point(real O, real E, real N, real S, real D, real U, real c, real f, real aO, real aE, real aN,
-                                                      real aS, real aD, real aU, real aC, real qx, real qy, real qz, real s) {
-    const real AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC;
+__device__ __forceinline__ real residual_faces3d_point(real O, real E, real N, real S, real D, real U, real c, real f, real AW, real AE, real AN,
+                                                       real AS, real AD, real AU, real qx, real qy, real qz, real s) {
     const real tx = qx * (AW * (O - c) + AE * (E - c));
     const real ty = qy * (AN * (N - c) + AS * (S - c));
     const real tz = qz * (AD * (D - c) + AU * (U - c));
     return (((f - tx) - ty) - tz) + s * c;
+}
+
+template <class real>
+__device__ __forceinline__ real relax_coef3d_point(real O, real E, real N, real S, real D, real U, real f, real aO, real aE, real aN, real aS,
+                                                   real aD, real aU, real aC, real qx, real qy, real qz, real s) {
+    const real AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC;
+    return relax_faces3d_point<real>(O, E, N, S, D, U, f, AW, AE, AN, AS, AD, AU, qx, qy, qz, s);
+}
+
+template <class real>
+__device__ __forceinline__ real residual_coef3d_point(real O, real E, real N, real S, real D, real U, real c, real f, real aO, real aE, real aN,
+                                                      real aS, real aD, real aU, real aC, real qx, real qy, real qz, real s) {
+    const real AW = aO + aC, AE = aE + aC, AN = aN + aC, AS = aS + aC, AD = aD + aC, AU = aU + aC;
+    return residual_faces3d_point<real>(O, E, N, S, D, U, c, f, AW, AE, AN, AS, AD, AU, qx, qy, qz, s);
 }
 
 // qx = (real)0.5 / hx2 .. : half the reciprocal squared spacings (the 1/2 of the face means)
@@ -159,6 +173,76 @@ struct CapOp {
     template <int MODE>
     __device__ __forceinline__ real residual_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
         return residual_coef3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, qx, qy, qz, se);
+    }
+};
+
+// ------------------------------------------------------------------ harmonic-mean faces (mgx_hmean3d.hip)
+// CoefOp's / CapOp's operators for a coefficient that belongs to the nodes (voxel data): the material interface lies midway between
+// two nodes and the face carries the series conductance 2 aP aQ / (aP + aQ).  The one difference is the doubled face coefficient,
+//   AW = (real)4 * ((aO * aC) / (aO + aC))   (likewise AE .. AU)   for   AW = aO + aC,
+// a plain IEEE division in `real` in both precisions; everything after it is relax_faces3d_point / residual_faces3d_point, the
+// expressions relax_coef3d_point / residual_coef3d_point continue with.  Product and sum commute, so a face has the same bits
+// seen from either of its nodes: the operator is symmetric bit for bit.  Where the two values are the same power of two the
+// doubled mean is exactly aO + aC and the results have the arithmetic operator's bits (a == 1: 4 * (1 / 2) = 2).  The host keeps
+// a * a normal and finite.
+template <class real>
+__device__ __forceinline__ real hmean_face(real aQ, real aC) {
+    return (real)4 * ((aQ * aC) / (aQ + aC));
+}
+
+template <class real>
+__device__ __forceinline__ real relax_hmean3d_point(real O, real E, real N, real S, real D, real U, real f, real aO, real aE, real aN, real aS,
+                                                    real aD, real aU, real aC, real qx, real qy, real qz, real s) {
+    return relax_faces3d_point<real>(O, E, N, S, D, U, f, hmean_face(aO, aC), hmean_face(aE, aC), hmean_face(aN, aC), hmean_face(aS, aC),
+                                     hmean_face(aD, aC), hmean_face(aU, aC), qx, qy, qz, s);
+}
+
+template <class real>
+__device__ __forceinline__ real residual_hmean3d_point(real O, real E, real N, real S, real D, real U, real c, real f, real aO, real aE, real aN,
+                                                       real aS, real aD, real aU, real aC, real qx, real qy, real qz, real s) {
+    return residual_faces3d_point<real>(O, E, N, S, D, U, c, f, hmean_face(aO, aC), hmean_face(aE, aC), hmean_face(aN, aC), hmean_face(aS, aC),
+                                        hmean_face(aD, aC), hmean_face(aU, aC), qx, qy, qz, s);
+}
+
+// CoefOp with harmonic faces: its scalars, its flags and its MODE; the point expressions and the kernels' names are its own
+template <class real>
+struct HarmOp : CoefOp<real> {
+    static constexpr const char *relax_kernel = "relax_hmean3d_xs_kernel", *zero_kernel = "relax_hmean_zero3d_xs_kernel";
+    using CoefOp<real>::CoefOp;
+    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>& a) const { return relax_wall(v, f, a, this->s); }
+    template <int MODE>
+    __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a) const {
+        return residual_wall<MODE>(v, f, a, this->s);
+    }
+    __device__ __forceinline__ real relax_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
+        return relax_hmean3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, this->qx, this->qy, this->qz, se);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
+        return residual_hmean3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, this->qx, this->qy,
+                                            this->qz, se);
+    }
+};
+
+// CapOp with harmonic faces
+template <class real>
+struct HarmCapOp : CapOp<real> {
+    static constexpr const char *relax_kernel = "relax_hmean_cap3d_xs_kernel", *zero_kernel = "relax_hmean_cap_zero3d_xs_kernel";
+    using CapOp<real>::CapOp;
+    __device__ __forceinline__ real relax(const Star7<real>& v, real f, const Star7<real>& a, real cP) const {
+        return relax_wall(v, f, a, this->s * cP);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual(const Star7<real>& v, real f, const Star7<real>& a, real cP) const {
+        return residual_wall<MODE>(v, f, a, this->s * cP);
+    }
+    __device__ __forceinline__ real relax_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
+        return relax_hmean3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, this->qx, this->qy, this->qz, se);
+    }
+    template <int MODE>
+    __device__ __forceinline__ real residual_wall(const Star7<real>& v, real f, const Star7<real>& a, real se) const {
+        return residual_hmean3d_point<real>(v.O, v.E, v.N, v.S, v.D, v.U, v.C, f, a.O, a.E, a.N, a.S, a.D, a.U, a.C, this->qx, this->qy,
+                                            this->qz, se);
     }
 };
 

@@ -1,7 +1,7 @@
 // mgx_rim3d.hpp -- what the units that work on the face unknowns share (mgx_rim3d.hip, mgx_wall3d.hip, mgx_cap3d.hip; DESIGN.md
 // sections 15 and 18): the list of face points, the reflected star, the weight and the block sum of the solve's inner product, the
 // wall data, and the host drivers of the operator entries with a mask.  A driver launches the interior kernels of the unit that
-// instantiates it (mgx_rim3d.hip for ShiftOp and CoefOp, mgx_cap3d.hip for CapOp) and the face kernels of mgx_wall3d.hip, their one
+// instantiates it (mgx_rim3d.hip for ShiftOp and CoefOp, mgx_cap3d.hip for CapOp, mgx_hmean3d.hip for HarmOp and HarmCapOp) and the face kernels of mgx_wall3d.hip, their one
 // home, through that unit's launch functions; a homogeneous Neumann face is a wall with beta = 0.  The transfers and the vector
 // kernels of the solve are in mgx_rim3d.hip.
 #pragma once
@@ -123,7 +123,7 @@ struct WallD {
 template <class real>
 static const real NO_WALL[6] = {0, 0, 0, 0, 0, 0};
 
-// the launches over the face unknowns, defined and instantiated for the three policies in mgx_wall3d.hip
+// the launches over the face unknowns, defined and instantiated for every policy of mgx_ops3d.hpp in mgx_wall3d.hip
 template <class Op, class real>
 void face_relax_launch(mgx_ctx* ctx, real* v, const real* f, const real* a, const Rim& R, const Op& op, const WallD<real>& w, int colour);
 template <class Op, class real>

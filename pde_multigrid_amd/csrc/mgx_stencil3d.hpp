@@ -5,6 +5,7 @@
 //   ShiftOp  (mgx_ops3d.hpp)     (Laplacian - s) u = f                             DESIGN.md section 13
 //   CoefOp   (mgx_ops3d.hpp)     div(a grad u) - s u = f, a at the grid nodes      DESIGN.md section 14
 //   CapOp    (mgx_ops3d.hpp)     div(a grad u) - (s c) u = f, c at the grid nodes  DESIGN.md section 17
+//   HarmOp, HarmCapOp (mgx_ops3d.hpp)  CoefOp and CapOp with harmonic-mean faces      DESIGN.md section 19
 // A policy holds
 //   Op(ctx, h, s)                          the operator's scalars for a level with spacings h, formed by the host once per call
 //                                          (with HAS_C: Op(ctx, h, s, c), and op.c is the capacity array)

@@ -16,8 +16,9 @@
 // (wall_rhs3d_xs_kernel).
 //
 // The three kernels -- colour pass, residual, apply + dot -- take an operator policy and the six d_k by value and are instantiated
-// for ShiftOp, CoefOp and CapOp in this unit only: one instance per operator and precision serves the _bc and the _wall entries.
-// The host drivers are in mgx_rim3d.hpp and are instantiated, with the interior kernels, in mgx_rim3d.hip and mgx_cap3d.hip: they
+// for ShiftOp, CoefOp, CapOp and their harmonic-mean forms HarmOp and HarmCapOp in this unit only: one instance per operator and
+// precision serves the _bc and the _wall entries.  The host drivers are in mgx_rim3d.hpp and are instantiated, with the interior
+// kernels, in mgx_rim3d.hip, mgx_cap3d.hip and mgx_hmean3d.hip: they
 // reach the kernels through the launch functions at the end of this file.  No LDS beyond the partial sums' four doubles, no scratch.
 #include "mgx_rim3d.hpp"
 
@@ -164,6 +165,10 @@ MGX_WALL3D_LAUNCHERS(CoefOp, float)
 MGX_WALL3D_LAUNCHERS(CoefOp, double)
 MGX_WALL3D_LAUNCHERS(CapOp, float)
 MGX_WALL3D_LAUNCHERS(CapOp, double)
+MGX_WALL3D_LAUNCHERS(HarmOp, float)  // harmonic-mean faces (section 19): the drivers are instantiated in mgx_hmean3d.hip
+MGX_WALL3D_LAUNCHERS(HarmOp, double)
+MGX_WALL3D_LAUNCHERS(HarmCapOp, float)
+MGX_WALL3D_LAUNCHERS(HarmCapOp, double)
 
 // f -= 2 g / h on the face unknowns of the mask's faces with g_k != 0; all g zero: nothing is launched
 template <class real>

@@ -724,6 +724,46 @@ class _Ops3D(_Ops):
         h = _rp(grid_spacing(n, rng, dtype), ct)
         return self._run(ctx, [f], lambda fp: fn(ctx._h, fp, _ip(n), h, _rp(g, ct), C.c_int(bc)), 0, _shape(n), dtype)
 
+    # ---- harmonic-mean face coefficients (x-split only, mgx3dxs_*_hmean): views of the four entries, which take the _wall form;
+    # c: None = no capacity, bc: None = the interior alone, beta: None = six zeros (homogeneous Neumann faces)
+    def relax_hmean(self, ctx, v, f, a, n, rng, s, ncycles, c=None, bc=None, beta=None, dtype=None):
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_hmean_wall", dtype)
+        h, b = _rp(grid_spacing(n, rng, dtype), ct), _rp(beta if beta is not None else [0.0] * 6, ct)
+        return self._run(ctx, [v, f, a, c], lambda vp, fp, ap, cp: fn(ctx._h, vp, fp, ap, cp, _ip(n), h, ct(s), C.c_int(ncycles),
+                                                                    C.c_int(bc or 0), b), 0, _shape(n), dtype)
+
+    def relax_hmean_from_zero(self, ctx, v, f, a, n, rng, s, ncycles, rim_is_zero, c=None, dtype=None):
+        """v := 0, then ncycles sweeps; with rim_is_zero the given v must have zero boundary entries (its interior is ignored)"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("relax_hmean_from_zero", dtype)
+        h = _rp(grid_spacing(n, rng, dtype), ct)
+        return self._run(ctx, [v, f, a, c], lambda vp, fp, ap, cp: fn(ctx._h, vp, fp, ap, cp, _ip(n), h, ct(s), C.c_int(ncycles),
+                                                                    C.c_int(int(rim_is_zero))), 0, _shape(n), dtype)
+
+    def residual_hmean(self, ctx, v, f, a, n, rng, s, c=None, bc=None, beta=None, store=True, want_sum=True, dtype=None):
+        """(r, sum of squares over all unknowns): r None with store=False, the sum None with want_sum=False"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("residual_hmean_wall", dtype)
+        h, b = _rp(grid_spacing(n, rng, dtype), ct), _rp(beta if beta is not None else [0.0] * 6, ct)
+        arrays = [xs_pack(np.ascontiguousarray(x, dtype)) if x is not None else None for x in (v, f, a, c)]
+        arrays.append(xs_pack(np.zeros(_shape(n), dtype)) if store else None)
+        outs, sums = self._krylov(ctx, n, arrays, [],
+                                  lambda w, s0, *ptrs: fn(ctx._h, *ptrs, _ip(n), h, ct(s), w if want_sum else None, s0 if want_sum else None,
+                                                          C.c_int(bc or 0), b), dtype, 1, self._krylov_work_bc)
+        return (xs_unpack(outs[-1], n[0]) if store else None), (float(sums[0]) if want_sum else None)
+
+    def apply_hmean_dot(self, ctx, p, a, n, rng, s, c=None, bc=None, beta=None, q=None, dtype=None):
+        """q = A p at every unknown and <p, q>_W (without a mask: on the interior, and <p, q>): returns (q, pq); q: the array written
+        into (default zeros)"""
+        dtype = dtype or p.dtype
+        fn, ct = self._fn("apply_hmean_dot_wall", dtype)
+        h, b = _rp(grid_spacing(n, rng, dtype), ct), _rp(beta if beta is not None else [0.0] * 6, ct)
+        q = np.zeros(_shape(n), dtype) if q is None else q
+        outs, sums = self._krylov_bc(ctx, n, [p, a, c, q], [],
+                                     lambda w, s0, *ptrs: fn(ctx._h, *ptrs, _ip(n), h, ct(s), w, s0, C.c_int(bc or 0), b), dtype, 1)
+        return outs[-1], float(sums[0])
+
     # ---- vector kernels of the preconditioned CG solve (x-split only; every array in the reference layout on the host)
     # every work array is uploaded with WORK_GUARD sentinel doubles behind the elements the library asks for, and the
     # sentinels are looked at after the call: a kernel that writes into the next WORK_GUARD doubles behind its work array
@@ -1042,6 +1082,20 @@ class GraphFlags(C.Structure):
     _fields_ = [("a", (C.c_ubyte * 32) * MG_GRAPH_FLAG_ARRAYS)]
 
 
+FACE_MEANS = {"arithmetic": 0, "harmonic": 1}  # MG_FACE_MEAN_*
+
+
+def face_mean_mode(name):
+    if not isinstance(name, str) or name not in FACE_MEANS:
+        raise ValueError("face_mean must be 'arithmetic' or 'harmonic', not %r" % (name,))
+    return FACE_MEANS[name]
+
+
+class _GraphKey(C.Union):
+    """the unused graph_key of mgMultiGrid3D_<r>, whose first four bytes hold face_mean"""
+    _fields_ = [("graph_key", C.c_longlong * 29), ("face_mean", C.c_int)]
+
+
 def _grid3_struct(ct):
     class Grid3D(C.Structure):
         _fields_ = [("h_v", C.c_void_p), ("h_f", C.c_void_p), ("d_v", C.c_void_p), ("d_f", C.c_void_p),
@@ -1050,10 +1104,11 @@ def _grid3_struct(ct):
                     ("y_a", ct), ("y_b", ct), ("z_a", ct), ("z_b", ct), ("d_a", C.c_void_p)]
 
     class MultiGrid3D(C.Structure):
+        _anonymous_ = ("graph_key_",)
         _fields_ = [("grids3D", C.POINTER(C.POINTER(Grid3D))), ("numGrids", C.c_int), ("maxGrids", C.c_int),
                     ("ctx", C.c_void_p), ("residual_mode", C.c_int), ("fuse", C.c_int), ("layout", C.c_int),
                     ("smoother", C.c_int), ("omega", ct), ("use_graph", C.c_int), ("capturing", C.c_int),
-                    ("graph_exec", C.c_void_p * 32), ("graph_key", C.c_longlong * 29), ("wall", C.c_void_p), ("cap", C.c_void_p), ("pcg_fproj", C.c_void_p),
+                    ("graph_exec", C.c_void_p * 32), ("graph_key_", _GraphKey), ("wall", C.c_void_p), ("cap", C.c_void_p), ("pcg_fproj", C.c_void_p),
                     ("f_rim_zero", C.c_ubyte * 32),
                     ("v_rim_zero", C.c_ubyte * 32), ("e_rim_valid", C.c_ubyte * 32), ("pcg_x", C.c_void_p),
                     ("pcg_b", C.c_void_p), ("pcg_p", C.c_void_p), ("pcg_q", C.c_void_p), ("pcg_state", C.c_void_p),
@@ -1161,7 +1216,7 @@ class MultiGrid3D(_MGBase):
 
     def __init__(self, ctx, finestGridSizeXYZ, rng, dtype=np.float64, nlevels=0, residual_mode=REF_COMPAT, fuse=True,
                  layout="xsplit", coarsening="full", shift=0.0, coefficient=None, neumann=None, capacity=None, robin=None,
-                 wall_flux=None):
+                 wall_flux=None, face_mean="arithmetic"):
         """coarsening="semi": every level halves only the axes with the smallest spacing (semi_plan, mg_multigrid.h) -- the
         hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count.
         shift = s >= 0: the hierarchy of (Laplacian - s) u = f (the `shift` property).
@@ -1170,7 +1225,9 @@ class MultiGrid3D(_MGBase):
         capacity = c >= 0 at every point of the finest grid: the hierarchy of div(a grad u) - (s c) u = f (set_capacity; needs
         a coefficient).
         robin, wall_flux = six numbers each (the faces' order): beta >= 0 and g of the wall law a du/dn + beta u = g on the
-        faces of `neumann` (set_wall)."""
+        faces of `neumann` (set_wall).
+        face_mean = "arithmetic" or "harmonic": the mean of the two nodes' coefficients a face carries (set_face_mean)."""
+        mean = face_mean_mode(face_mean)
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
         self._sfx, self._ct = _ct(dtype)
@@ -1194,6 +1251,12 @@ class MultiGrid3D(_MGBase):
         if shift != 0:  # (a NaN too: rejected by the setter)
             try:
                 self.shift = shift
+            except Exception:
+                self.close()
+                raise
+        if mean:
+            try:
+                self.set_face_mean(face_mean)
             except Exception:
                 self.close()
                 raise
@@ -1306,6 +1369,20 @@ class MultiGrid3D(_MGBase):
         if c.shape != _shape(self.size(0)):
             raise ValueError("the capacity has shape %r, level 0 has %r" % (c.shape, _shape(self.size(0))))
         self._call("set_capacity", c.ctypes.data_as(C.c_void_p))
+
+    def set_face_mean(self, mean):
+        """mean: "arithmetic" (the default) or "harmonic" -- the coefficient a face between two nodes carries: (aP + aQ) / 2, right
+        where a material boundary lies on a node plane, or 2 aP aQ / (aP + aQ), the series conductance, right for node-valued
+        materials (voxel data, a layer one node thick) whose boundary lies midway between two nodes.  It may be set before or after
+        the coefficient and counts only while the hierarchy has one; every level is re-discretised with it, the coefficient goes
+        down the levels as before, and every call (cycles, PCG, BackwardEuler, walls, capacity, use_graph) works with it.  The
+        harmonic mean needs every a * a to be a normal, finite number of the hierarchy's precision: a coefficient outside that range
+        is refused here and by set_coefficient.  Anything else raises ValueError."""
+        self._call("set_face_mean", C.c_int(face_mean_mode(mean)))
+
+    @property
+    def face_mean(self):
+        return "harmonic" if self._mg.contents.face_mean == FACE_MEANS["harmonic"] else "arithmetic"
 
     @property
     def has_capacity(self):
@@ -1774,7 +1851,7 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
 
 
 def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full",
-                shift=0.0, coefficient=None, neumann=None, capacity=None, robin=None, wall_flux=None):
+                shift=0.0, coefficient=None, neumann=None, capacity=None, robin=None, wall_flux=None, face_mean="arithmetic"):
     """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
     precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG).
     coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call.
@@ -1783,7 +1860,9 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
     neumann = six truthy values: the faces with du/dn = 0 (MultiGrid3D(neumann=...)), likewise; needs krylov=False or
     krylov="weighted" (MultiGrid3D.PCG).
     capacity = c >= 0 at every point, with a coefficient: the solve of div(a grad u) - (shift c) u = rhs, likewise.
-    robin, wall_flux = six numbers each: the walls' beta and g (MultiGrid3D.set_wall); the flux is folded into rhs here."""
+    robin, wall_flux = six numbers each: the walls' beta and g (MultiGrid3D.set_wall); the flux is folded into rhs here.
+    face_mean = "arithmetic" or "harmonic": the face coefficients of a solve with a coefficient (MultiGrid3D.set_face_mean)."""
+    face_mean_mode(face_mean)
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
     if precond not in ("f64", "f32"):
@@ -1795,7 +1874,8 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
     if coarsening == "semi" or shift != 0 or coefficient is not None or capacity is not None or (neumann is not None and any(neumann)) or \
             robin is not None or wall_flux is not None:
         mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening=coarsening,
-                         shift=shift, coefficient=coefficient, neumann=neumann, capacity=capacity, robin=robin, wall_flux=wall_flux)
+                         shift=shift, coefficient=coefficient, neumann=neumann, capacity=capacity, robin=robin, wall_flux=wall_flux,
+                         face_mean=face_mean)
         try:
             mg.upload_v(0, grid)
             if rhs is not None:
