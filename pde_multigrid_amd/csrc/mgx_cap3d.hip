@@ -3,7 +3,7 @@
 // jump together in a composite), a reaction term that varies in space, screened problems that are purely elliptic where c = 0.
 // DESIGN.md section 17.
 //
-// The arithmetic is mgx_coef3d.hip's (restated in tests/cap_restated.py) with ONE more operation per point, in `real`:
+// The arithmetic is mgx_coef3d.hip's (restated in tests/op_restated.py) with ONE more operation per point, in `real`:
 //   sc = s * c_P            c_P the capacity at the updated point itself (f's index; nothing of c is read around it)
 // and then relax_coef3d_point / residual_coef3d_point with sc where they take s.  With c == 1 every result has the bits of the
 // coefficient operator.  c is never written and its values are not checked here.  At an unknown on a Neumann face the operator

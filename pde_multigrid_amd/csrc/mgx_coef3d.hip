@@ -1,7 +1,7 @@
 // mgx_coef3d.hip -- the operators of the VARIABLE-COEFFICIENT problem div(a grad u) - s u = f, a > 0 given at the grid nodes,
 // s >= 0, x-split layout: heterogeneous diffusion (conductivity, permeability, 1 / density).  DESIGN.md section 14.
 //
-// The reference has no such operator; the arithmetic is fixed here (and restated in tests/coef_restated.py), all in `real`,
+// The reference has no such operator; the arithmetic is fixed here (and restated in tests/op_restated.py), all in `real`,
 // left to right as written, nothing contracted.  O/E = x-1/x+1, N/S = y-1/y+1, D/U = z-1/z+1, c the centre; aO .. aU, aC the
 // coefficient at the same seven points; qx = (real)0.5 / (h[0]*h[0]) (likewise qy, qz), formed by the host once per call:
 //   AW = aO + aC  AE = aE + aC  AN = aN + aC  AS = aS + aC  AD = aD + aC  AU = aU + aC

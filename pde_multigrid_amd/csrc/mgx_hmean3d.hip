@@ -3,7 +3,7 @@
 // node thick), where the material interface lies midway between two nodes and the face carries the series conductance
 // 2 aP aQ / (aP + aQ).  DESIGN.md section 19.
 //
-// The arithmetic is mgx_coef3d.hip's / mgx_cap3d.hip's (restated in tests/hmean_restated.py) with ONE difference, in `real`:
+// The arithmetic is mgx_coef3d.hip's / mgx_cap3d.hip's (restated in tests/op_restated.py) with ONE difference, in `real`:
 //   AW = (real)4 * ((aO * aC) / (aO + aC))   (likewise AE .. AU)   where those form   AW = aO + aC
 // the doubled harmonic mean, a plain IEEE division in both precisions; q* = (real)0.5 / h*^2, den, num, tx, ty, tz and the se forms
 // of the walls are unchanged and in the same association.  Product and sum commute: a face has the same bits seen from either of

@@ -1,7 +1,7 @@
 // mgx_shift3d.hip -- the operators of the SHIFTED problem (Laplacian - s) u = f, s >= 0, x-split layout: the implicit step of
 // diffusion (s = 1 / (kappa dt)) and the screened Poisson equation.  DESIGN.md section 13.
 //
-// The reference has no such operator; the arithmetic is fixed here (and restated in tests/shift_restated.py), all in `real`,
+// The reference has no such operator; the arithmetic is fixed here (and restated in tests/op_restated.py), all in `real`,
 // left to right as written, nothing contracted.  hx2 .. are the squared spacings, the names those of relax3d_point /
 // residual3d_point (mgx_kernels3d.hpp):
 //   smoother   v = num / den, num = relax3d_point's numerator, den = 2*(hy2*hz2 + hx2*hz2 + hx2*hy2) + s*hx2*hy2*hz2.  den is

@@ -1,6 +1,6 @@
 """The operator with a capacity, div(a grad u) - (s c) u = f, without a GPU: the library exports the new entries, rejects NULL
-arguments and keeps the sizes and offsets of both struct mirrors; the restatement of the arithmetic (tests/cap_restated.py) has the
-bits of coef_restated / neumann_restated at c == 1, is symmetric under the trapezoid weights and negative definite, exact where the
+arguments and keeps the sizes and offsets of both struct mirrors; the restatement of the arithmetic (tests/op_restated.py) has the
+bits of the operator without a capacity at c == 1, is symmetric under the trapezoid weights and negative definite, exact where the
 discretisation is, its cycle is a solver and its implicit steps in a closed box keep the heat content sum(w c u)."""
 import ctypes as C
 import math
@@ -8,12 +8,10 @@ import math
 import numpy as np
 import pytest
 
-import cap_restated as CA
-import coef_restated as CO
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-import shift_restated as SH
 from pde_multigrid_amd.multigrid import _grid3_struct
 
 UNIT = [0, 1, 0, 1, 0, 1]
@@ -93,32 +91,32 @@ def _same(x, y):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("s", [0.0, 0.75, 1e4])
 def test_unit_capacity_is_the_coefficient_operator_in_bits(s, dtype):
-    """c == 1: s * 1 = s exactly, so relax, residual, A p and the right-hand side have the bits of coef_restated (no mask),
-    neumann_restated (masks 1, 37, 63) and shift_restated.rhs"""
+    """c == 1: s * 1 = s exactly, so relax, residual, A p and the right-hand side have the bits of the operator without a capacity (no mask
+    and masks 1, 37, 63)"""
     n3 = (21, 13, 9)
     g = np.random.default_rng(2)
     v, f = (g.uniform(-1, 1, O.shape(n3)).astype(dtype) for _ in range(2))
     a = g.uniform(0.5, 2, O.shape(n3)).astype(dtype)
     one = np.ones(O.shape(n3), dtype)
-    assert _same(CA.relax(n3, RG, v, f, a, one, s, 2, dtype), CO.relax(n3, RG, v, f, a, s, 2, dtype))
-    assert _same(CA.residual(n3, RG, v, f, a, one, s, dtype), CO.residual(n3, RG, v, f, a, s, dtype))
-    assert _same(CA.apply_A(n3, RG, v, a, one, s, dtype), CO.apply_A(n3, RG, v, a, s, dtype))
-    assert _same(CA.rhs(v, one, f, 0.3, s, dtype), SH.rhs(v, f, 0.3, s, dtype))
+    assert _same(OP.Op(n3, RG, dtype, s, a, one).relax(v, f, 2), OP.Op(n3, RG, dtype, s, a).relax(v, f, 2))
+    assert _same(OP.Op(n3, RG, dtype, s, a, one).residual(v, f), OP.Op(n3, RG, dtype, s, a).residual(v, f))
+    assert _same(OP.Op(n3, RG, dtype, s, a, one).apply_A(v), OP.Op(n3, RG, dtype, s, a).apply_A(v))
+    assert _same(OP.Op(n3, RG, dtype, s, c=one).rhs(v, f, 0.3), OP.Op(n3, RG, dtype, s).rhs(v, f, 0.3))
     for bc in (1, 37, 63):
-        assert _same(CA.relax(n3, RG, v, f, a, one, s, 2, dtype, bc), NR.relax(n3, RG, v, f, a, s, 2, bc, dtype)), bc
-        assert _same(CA.residual(n3, RG, v, f, a, one, s, dtype, bc), NR.residual(n3, RG, v, f, a, s, bc, dtype)), bc
-        assert _same(CA.rhs(v, one, f, 0.3, s, dtype, bc), NR.rhs(v, f, 0.3, s, bc, dtype)), bc
+        assert _same(OP.Op(n3, RG, dtype, s, a, one, bc).relax(v, f, 2), OP.Op(n3, RG, dtype, s, a, bc=bc).relax(v, f, 2)), bc
+        assert _same(OP.Op(n3, RG, dtype, s, a, one, bc).residual(v, f), OP.Op(n3, RG, dtype, s, a, bc=bc).residual(v, f)), bc
+        assert _same(OP.Op(n3, RG, dtype, s, c=one, bc=bc).rhs(v, f, 0.3), OP.Op(n3, RG, dtype, s, bc=bc).rhs(v, f, 0.3)), bc
 
 
 def test_capacity_goes_down_the_levels_as_the_coefficient_and_stays_nonnegative():
     for n3, coarsening in (((33, 33, 33), "full"), ((65, 33, 17), "semi")):
-        c = CA.random_capacity(n3, np.float64, 7)
-        H = CA.Hierarchy(n3, UNIT, np.ones(O.shape(n3)), c, 1.0, 0, np.float64, coarsening)
+        c = OC.random_capacity(n3, np.float64, 7)
+        H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 1.0, np.ones(O.shape(n3)), c), coarsening)
         assert len(H.c) == len(H.sizes) and (c == 0).any()
         for l, cl in enumerate(H.c):
             assert cl.shape == O.shape(H.sizes[l]) and cl.min() >= 0.0, l
         for l in range(len(H.sizes) - 1):
-            assert _same(H.c[l + 1], np.ascontiguousarray(CO.restrict(H.sizes[l], H.c[l], H.masks[l], np.float64)))
+            assert _same(H.c[l + 1], np.ascontiguousarray(OP.restrict(H.sizes[l], H.c[l], 0, np.float64, H.masks[l])))
 
 
 @pytest.mark.parametrize("bc", [1, 21, 63])
@@ -126,14 +124,14 @@ def test_weighted_operator_is_symmetric_and_negative_definite(bc):
     n3, s = (9, 9, 9), 0.75
     g = np.random.default_rng(5)
     a = g.uniform(0.5, 2, O.shape(n3))
-    c = CA.random_capacity(n3, np.float64, 6)
+    c = OC.random_capacity(n3, np.float64, 6)
     assert (c == 0).any() and c.max() > 1
     p, w = g.uniform(-1, 1, O.shape(n3)), g.uniform(-1, 1, O.shape(n3))
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     p[~unk] = 0
     w[~unk] = 0
-    W = NR.weights(n3, bc)
-    Ap, Aw = CA.apply_A(n3, UNIT, p, a, c, s, np.float64, bc), CA.apply_A(n3, UNIT, w, a, c, s, np.float64, bc)
+    W = OP.weights(n3, bc)
+    Ap, Aw = OP.Op(n3, UNIT, np.float64, s, a, c, bc).apply_A(p), OP.Op(n3, UNIT, np.float64, s, a, c, bc).apply_A(w)
     wAp, pAw, pAp = float((W * w * Ap).sum()), float((W * p * Aw).sum()), float((W * p * Ap).sum())
     print("bc %d: <w, A p>_W = %.15e, <p, A w>_W = %.15e, <p, A p>_W = %.6e" % (bc, wAp, pAw, pAp))
     assert abs(wAp - pAw) <= 1e-12 * abs(wAp)
@@ -148,24 +146,24 @@ def test_exact_for_quadratic_u_linear_a_and_linear_c(bc):
     =: F, the residual adds it to four terms of that size with one rounding each, so |r| <= 8 * (eps / 2) * F = 4 eps F (measured: 0.0
     on these dyadic nodes)."""
     n3, s = (17, 17, 17), 0.75
-    x, y, z = CO._nodes(n3)
+    x, y, z = OC.nodes(n3)
     a, c, u = 1 + 2 * y, 1 + x, x * x + y * z
     f = 2 * a + 2 * z - s * (1 + x) * u
-    r = CA.residual(n3, UNIT, u, f, a, c, s, np.float64, bc)
+    r = OP.Op(n3, UNIT, np.float64, s, a, c, bc).residual(u, f)
     F = np.abs(f).max() + s * np.abs(c * u).max()
     bound = 4 * np.finfo(np.float64).eps * F
     print("exactness, bc = %d: max |residual| = %.3e, bound %.3e" % (bc, np.abs(r).max(), bound))
-    assert (bc == 0) == (NR.face_unknowns(n3, bc).sum() == 0)
+    assert (bc == 0) == (OP.face_unknowns(n3, bc).sum() == 0)
     assert np.abs(r).max() <= bound
 
 
 def _table_case(name):
     big, semi = (33, 33, 33), (65, 33, 17)
-    return {"smooth": (big, "full", CO.smooth_coefficient(big), CA.smooth_capacity(big), 100.0),
-            "block100": (big, "full", np.ones(O.shape(big)), CA.block_capacity(big, 100, 1), 100.0),
-            "block100_a10": (big, "full", CO.jump_coefficient(big, 10), CA.block_capacity(big, 100, 1), 100.0),
-            "block_1_0": (big, "full", np.ones(O.shape(big)), CA.block_capacity(big, 1, 0), 1e4),
-            "semi": (semi, "semi", CO.smooth_coefficient(semi), CA.smooth_capacity(semi), 100.0)}[name]
+    return {"smooth": (big, "full", OC.smooth_coefficient(big), OC.smooth_capacity(big), 100.0),
+            "block100": (big, "full", np.ones(O.shape(big)), OC.block_capacity(big, 100, 1), 100.0),
+            "block100_a10": (big, "full", OC.jump_coefficient(big, 10), OC.block_capacity(big, 100, 1), 100.0),
+            "block_1_0": (big, "full", np.ones(O.shape(big)), OC.block_capacity(big, 1, 0), 1e4),
+            "semi": (semi, "semi", OC.smooth_coefficient(semi), OC.smooth_capacity(semi), 100.0)}[name]
 
 
 @pytest.mark.parametrize("name", ["smooth", "block100", "block100_a10", "block_1_0", "semi"])
@@ -173,7 +171,7 @@ def test_restated_vcycle_converges(name):
     """plain V(2,2) from a random interior f (seed 5) and a zero guess: the residual falls below 1e-10 of its start within 60
     cycles (the issue's scratch restatement: 8, 15, 13, 20 and 7 cycles; the count is printed, the bound is the issue's)"""
     n3, coarsening, a, c, s = _table_case(name)
-    H = CA.Hierarchy(n3, UNIT, a, c, s, 0, np.float64, coarsening)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, s, a, c), coarsening)
     f = np.zeros(O.shape(n3))
     f[1:-1, 1:-1, 1:-1] = np.random.default_rng(5).uniform(-1, 1, tuple(k - 2 for k in O.shape(n3)))
     H.f[0] = f
@@ -188,14 +186,14 @@ def test_backward_euler_in_a_closed_box_keeps_the_heat_content(jump):
     of c u_t = div(a grad u) with kappa dt = 1e-2 solved to 1e-10: the relative drift of sum(w c u) stays below 1e-9, the bound of
     the wall test (dividing by c instead would conserve sum(w u) of another equation)"""
     n3 = (17, 17, 17)
-    c = CA.block_capacity(n3, 100, 1) if jump else CA.smooth_capacity(n3)
-    H = CA.Hierarchy(n3, UNIT, CO.smooth_coefficient(n3), c, 0.0, 63)
-    H.v[0] = NR.gaussian(n3)
-    W = NR.weights(n3, 63)
+    c = OC.block_capacity(n3, 100, 1) if jump else OC.smooth_capacity(n3)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.0, OC.smooth_coefficient(n3), c, 63))
+    H.v[0] = OC.gaussian(n3)
+    W = OP.weights(n3, 63)
     heat0 = math.fsum((W * c * H.v[0]).ravel())
     cycles, worst, conv = H.backward_euler(5, 1e-2, 1.0, 2, 2, 1e-10, 60)
     assert conv, (cycles, worst)
     drift = abs(math.fsum((W * c * H.v[0]).ravel()) - heat0) / abs(heat0)
-    moved = float(np.abs(H.v[0] - NR.gaussian(n3)).max())
+    moved = float(np.abs(H.v[0] - OC.gaussian(n3)).max())
     print("jump %d: %d cycles, worst relative residual %.3e, drift of sum(w c u) %.3e, u moved by %.3e" % (jump, cycles, worst, drift, moved))
     assert moved > 1e-3 and drift < 1e-9, (moved, drift)

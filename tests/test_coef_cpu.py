@@ -1,5 +1,5 @@
 """The variable-coefficient operator div(a grad u) - s u = f without a GPU: the restatement of its arithmetic
-(tests/coef_restated.py) is exact where the discretisation is, symmetric and negative definite, anchored to the pinned
+(tests/op_restated.py) is exact where the discretisation is, symmetric and negative definite, anchored to the pinned
 constant-coefficient operators at a = 1, and its cycle is a solver; the library exports the new entries, rejects NULL arguments and
 reports the size of the struct the Python mirror restates."""
 import ctypes as C
@@ -8,10 +8,10 @@ import math
 import numpy as np
 import pytest
 
-import coef_restated as CO
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-import shift_restated as SH
 from pde_multigrid_amd.multigrid import _grid3_struct
 from solve_restated import boundary_mask, problem
 
@@ -24,9 +24,9 @@ def test_exact_for_linear_a_times_quadratic_u():
     """a = 1 + x + 2y, u = x^2 + y z, f = div(a grad u) = 2(1 + x + 2y) + 2x + 2z on 17^3: the arithmetic-mean faces are exact for
     a linear a, the differences for a quadratic u (measured: a residual of 0.0 or a few ulps of |f|; the bound is the issue's)"""
     n3 = (17, 17, 17)
-    x, y, z = CO._nodes(n3)
+    x, y, z = OC.nodes(n3)
     a, u, f = 1 + x + 2 * y, x * x + y * z, 2 * (1 + x + 2 * y) + 2 * x + 2 * z
-    r = CO.residual(n3, UNIT, u, f, a, 0.0, np.float64)
+    r = OP.Op(n3, UNIT, np.float64, 0.0, a).residual(u, f)
     print("exactness: max |residual| = %.3e" % np.abs(r).max())
     assert np.abs(r).max() <= 1e-10
 
@@ -38,7 +38,7 @@ def test_operator_is_symmetric_and_negative_definite():
     p, w = g.uniform(-1, 1, O.shape(n3)), g.uniform(-1, 1, O.shape(n3))
     p[boundary_mask(n3)] = 0
     w[boundary_mask(n3)] = 0
-    Ap, Aw = CO.apply_A(n3, RG, p, a, s, np.float64), CO.apply_A(n3, RG, w, a, s, np.float64)
+    Ap, Aw = OP.Op(n3, RG, np.float64, s, a).apply_A(p), OP.Op(n3, RG, np.float64, s, a).apply_A(w)
     wAp, pAw, pAp = float((w * Ap).sum()), float((p * Aw).sum()), float((p * Ap).sum())
     print("symmetry: <w, A p> = %.15e, <p, A w> = %.15e, <p, A p> = %.6e" % (wAp, pAw, pAp))
     assert abs(wAp - pAw) <= 1e-12 * abs(wAp)
@@ -57,7 +57,7 @@ ANCHOR_GRIDS = [((21, 13, 29), RG), ((17, 17, 17), UNIT)]
 @pytest.mark.parametrize("s", [0, 100])
 @pytest.mark.parametrize("grid", [0, 1])
 def test_unit_coefficient_is_the_pinned_operator_in_value(grid, s, dtype):
-    """a = 1: relax (two sweeps) and residual agree with shift_restated's in value -- other associations, so not in bits.  The
+    """a = 1: relax (two sweeps) and residual agree with the shifted operator's in value -- other associations, so not in bits.  The
     differences seen on the CPU, in units of eps * max |want| (relax, residual), are ANCHOR_SEEN -- between 0.5 and 1.5 for the
     two sweeps, between 0.79 and 1.14 for the residual; the bound is 8 times them."""
     n3, rng = ANCHOR_GRIDS[grid]
@@ -66,8 +66,8 @@ def test_unit_coefficient_is_the_pinned_operator_in_value(grid, s, dtype):
     one = np.ones(O.shape(n3), dtype)
     eps = float(np.finfo(dtype).eps)
     seen = ANCHOR_SEEN[(np.dtype(dtype).name, grid, s)]
-    pairs = [("relax", CO.relax(n3, rng, v, f, one, s, 2, dtype), SH.relax(n3, rng, v, f, s, 2, dtype)),
-             ("residual", CO.residual(n3, rng, v, f, one, s, dtype), SH.residual(n3, rng, v, f, s, dtype))]
+    pairs = [("relax", OP.Op(n3, rng, dtype, s, one).relax(v, f, 2), OP.Op(n3, rng, dtype, s).relax(v, f, 2)),
+             ("residual", OP.Op(n3, rng, dtype, s, one).residual(v, f), OP.Op(n3, rng, dtype, s).residual(v, f))]
     for (what, got, want), bound in zip(pairs, seen):
         got, want = got.astype(np.float64), want.astype(np.float64)
         units = np.abs(got - want).max() / (eps * np.abs(want).max())
@@ -80,12 +80,12 @@ def test_restated_cycle_converges_with_a_smooth_coefficient(s):
     """fp64 V(2,2) on 33^3, unit cube, random interior f, a = 1 + 0.5 sin(2 pi x) cos(pi y) + 0.25 z: relative residual below 1e-8
     after 8 cycles (the issue's prototype: 8.2e-10 and 9.5e-11; the bound is the shift test's)"""
     n3 = (33, 33, 33)
-    H = CO.Hierarchy(n3, UNIT, CO.smooth_coefficient(n3), s)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, s, OC.smooth_coefficient(n3)))
     H.f[0] = problem(n3)
-    r0 = math.sqrt(SH.fsum_sq(H.residual(0)))
+    r0 = math.sqrt(OP.fsum_sq(H.residual(0)))
     for _ in range(8):
         H.vcycle(0, 2, 2)
-    rel = math.sqrt(SH.fsum_sq(H.residual(0))) / r0
+    rel = math.sqrt(OP.fsum_sq(H.residual(0))) / r0
     print("smooth coefficient, shift %g: relative residual %.3e after 8 V(2,2)" % (s, rel))
     assert rel < 1e-8, rel
 
@@ -94,11 +94,11 @@ def test_restated_fcg_solves_a_jump_of_ten():
     """a = 10 inside the centred cube of edge 1/2, 1 outside, s = 0: flexible CG + V(2,2) to 1e-10 in at most 20 iterations (the
     issue's prototype: 12), and the restricted coefficients never fall below the smallest fine one (positive weights)"""
     n3 = (33, 33, 33)
-    a, f = CO.jump_coefficient(n3, 10), problem(n3)
-    H = CO.Hierarchy(n3, UNIT, a, 0.0)
+    a, f = OC.jump_coefficient(n3, 10), problem(n3)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.0, a))
     for l, al in enumerate(H.a):
         assert al.min() >= 1.0, (l, al.min())
-    _, k, hist, conv = CO.fcg_restated(n3, UNIT, a, 0.0, np.zeros_like(f), f, CO.m_cycle(n3, UNIT, a, 0.0, 2, 2), 1e-10, 50)
+    _, k, hist, conv = OP.fcg(OP.Op(n3, UNIT, np.float64, 0.0, a), np.zeros_like(f), f, tol=1e-10, maxit=50)[:4]
     print("jump 10: %d iterations, last relative residual %.3e" % (k, hist[-1]))
     assert conv and k <= 20, k
 

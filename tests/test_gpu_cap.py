@@ -2,7 +2,7 @@
 (csrc/mgx_cap3d.hip), the hierarchy that holds a capacity array per level (MultiGrid3D(capacity=c), set_capacity) and the solves and
 implicit heat steps on it.
 
-Every kernel is checked bit for bit against the numpy restatement of its arithmetic (tests/cap_restated.py), with poisoned pads and
+Every kernel is checked bit for bit against the numpy restatement of its arithmetic (tests/op_restated.py), with poisoned pads and
 with both row counts of the colour pass; with c == 1 against the _coef entry on the same inputs; the capacity of every level against
 the restated restriction chain; the cycles against the restated cycle, every level, eager and replayed from a graph."""
 import ctypes as C
@@ -11,13 +11,10 @@ import math
 import numpy as np
 import pytest
 
-import cap_restated as CA
-import coef_restated as CO
-import neumann_krylov_restated as NK
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-import shift_restated as SH
 from conftest import bits_equal
 from odd_shapes import pads_unchanged, run_poisoned
 from pde_multigrid_amd.multigrid import _ct, _ip, _rp, grid_spacing, xs_unpack
@@ -61,7 +58,7 @@ def _coef(n3, dtype, seed=100):
 
 
 def _cap(n3, dtype, seed=200):
-    return CA.random_capacity(n3, dtype, seed)
+    return OC.random_capacity(n3, dtype, seed)
 
 
 def _fn(name, dtype):
@@ -112,8 +109,8 @@ def test_relax_cap(ctx, n3, bc, s, dtype):
     assert (c == 0).any() and c.max() > 1
     try:
         for sweeps in (1, 3):
-            want = CA.relax(n3, RG, v, f, a, c, s, sweeps, dtype, bc)
-            assert bits_equal(want[~NR.unknown_mask(n3, bc)], v[~NR.unknown_mask(n3, bc)])
+            want = OP.Op(n3, RG, dtype, s, a, c, bc).relax(v, f, sweeps)
+            assert bits_equal(want[~OP.unknown_mask(n3, bc)], v[~OP.unknown_mask(n3, bc)])
             for knob in (2, 4):
                 ctx.set_param("relax3d.rows", knob)
                 rows = knob
@@ -141,7 +138,7 @@ def test_relax_cap_from_zero(ctx, n3, s, dtype):
     f[1:-1:2, 1:-1, 1:-1] = 0  # zero right-hand sides too: the signs of the zeros the first pass stores
     fn, ct = _fn("relax_cap_from_zero", dtype)
     for sweeps in (1, 2):
-        want = CA.relax(n3, RG, np.zeros_like(v), f, a, c, s, sweeps, dtype)
+        want = OP.Op(n3, RG, dtype, s, a, c).relax(np.zeros_like(v), f, sweeps)
         for rim_is_zero in (0, 1):
             v0 = v.copy()
             if rim_is_zero:  # the caller vouches for a zero boundary; the interior is stale
@@ -158,8 +155,8 @@ def test_relax_cap_from_zero(ctx, n3, s, dtype):
 @pytest.mark.parametrize("n3,bc,s", CASES)
 def test_residual_cap(ctx, n3, bc, s, dtype):
     v, f, a, c, r0 = _rand(n3, dtype, 5), _rand(n3, dtype, 6), _coef(n3, dtype), _cap(n3, dtype), _rand(n3, dtype, 7)
-    want = CA.residual(n3, RG, v, f, a, c, s, dtype, bc)
-    want_ss = SH.fsum_sq(want)
+    want = OP.Op(n3, RG, dtype, s, a, c, bc).residual(v, f)
+    want_ss = OP.fsum_sq(want)
     w = Work(ctx, n3, dtype)
     try:
         for name, tail in _forms("residual_cap", bc):
@@ -190,9 +187,9 @@ def test_residual_cap(ctx, n3, bc, s, dtype):
 @pytest.mark.parametrize("n3,bc,s", CASES)
 def test_apply_cap_dot(ctx, n3, bc, s, dtype):
     p, a, c, q0 = _rand(n3, dtype, 8), _coef(n3, dtype), _cap(n3, dtype), _rand(n3, dtype, 9)
-    unk = NR.unknown_mask(n3, bc)
-    want = CA.apply_A(n3, RG, p, a, c, s, dtype, bc)
-    want_pq = NK.wdot(NR.weights(n3, bc), p, want)
+    unk = OP.unknown_mask(n3, bc)
+    want = OP.Op(n3, RG, dtype, s, a, c, bc).apply_A(p)
+    want_pq = OP.wdot(OP.weights(n3, bc), p, want)
     w = Work(ctx, n3, dtype)
     try:
         for name, tail in _forms("apply_cap_dot", bc):
@@ -222,7 +219,7 @@ def test_cap_rhs(ctx, n3, bc, s, dtype):
     for name, tail in _forms("cap_rhs", bc):
         fn = _fn(name, dtype)[0]
         for src in (q, None):
-            want = CA.rhs(u, c, src, 0.3, s, dtype, bc, f=f0)
+            want = OP.Op(n3, UNIT, dtype, s, c=c, bc=bc).rhs(u, src, 0.3, f=f0)
             arrays = [u, c, f0] + ([q] if src is not None else [])
             ups, outs = run_poisoned(ctx, arrays, lambda x, cc, d, qq=None: fn(ctx._h, x, cc, qq, ct(0.3), ct(s), d, _ip(n3), *tail), dtype)
             assert bits_equal(xs_unpack(outs[2], n3[0]), want), (name, src is None)  # the Dirichlet entries of f as they were
@@ -299,7 +296,7 @@ def _mg(ctx, grid, bc, dtype, a, c, v=None, f=None, s=S_CYCLE):
 
 def _restated(grid, bc, dtype, a, c, v, f, s=S_CYCLE):
     n3, rng, how = GRIDS[grid]
-    H = CA.Hierarchy(n3, rng, a, c, s, bc, dtype, how)
+    H = OP.Hierarchy(OP.Op(n3, rng, dtype, s, a, c, bc), how)
     H.v[0], H.f[0] = v.copy(), f.copy()
     return H
 
@@ -401,11 +398,11 @@ def test_relax_residual_and_norm_through_the_hierarchy(ctx, bc, dtype):
     v, f, a, c = _rand(n3, dtype, 7), _rand(n3, dtype, 8), _coef(n3, dtype), _cap(n3, dtype)
     mg = _mg(ctx, 1, bc, dtype, a, c, v=v, f=f, s=s)
     mg.Relax(0, 3)
-    want = CA.relax(n3, rng, v, f, a, c, s, 3, dtype, bc)
+    want = OP.Op(n3, rng, dtype, s, a, c, bc).relax(v, f, 3)
     assert bits_equal(mg.download_v(0), want)
-    r = CA.residual(n3, rng, want, f, a, c, s, dtype, bc)
+    r = OP.Op(n3, rng, dtype, s, a, c, bc).residual(want, f)
     assert bits_equal(mg.CalculateResidual(0), r)
-    assert close(mg.ResidualNorm(0), math.sqrt(SH.fsum_sq(r)), 1e-12)
+    assert close(mg.ResidualNorm(0), math.sqrt(OP.fsum_sq(r)), 1e-12)
     mg.close()
 
 
@@ -419,7 +416,7 @@ def pcg_problem():
     f = _rand(n3, np.float64, 5)
     v0 = np.zeros_like(f)
     v0[boundary_mask(n3)] = _rand(n3, np.float64, 9)[boundary_mask(n3)]  # Dirichlet data where a face is no wall
-    return CO.smooth_coefficient(n3), CA.block_capacity(n3, 100, 1), f, v0
+    return OC.smooth_coefficient(n3), OC.block_capacity(n3, 100, 1), f, v0
 
 
 @pytest.mark.parametrize("krylov,bc", [(False, 0), (True, 0), ("weighted", 0), (False, 37), ("weighted", 37), ("weighted", 63)])
@@ -430,16 +427,16 @@ def test_pcg_matches_the_restatement(ctx, pcg_problem, krylov, bc):
     n3, s, tol = PCG_N, 100.0, (1e-10 if bc else 5e-11)
     a, c, f, v0 = pcg_problem
     if krylov:
-        _, want_k, hist, want_c, _ = CA.fcg(n3, UNIT, a, c, s, bc, v0, f, tol, 60)
+        _, want_k, hist, want_c, _ = OP.fcg(OP.Op(n3, UNIT, np.float64, s, a, c, bc), v0, f, tol=tol, maxit=60)[:5]
     else:
-        H = CA.Hierarchy(n3, UNIT, a, c, s, bc)
+        H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, s, a, c, bc))
         H.v[0], H.f[0] = v0.copy(), f.copy()
-        rr0, hist = SH.fsum_sq(H.residual(0)), []
+        rr0, hist = OP.fsum_sq(H.residual(0)), []
         while not hist or (hist[-1] >= tol and len(hist) < 60):
             H.vcycle(0, 2, 2)
-            hist.append(math.sqrt(SH.fsum_sq(H.residual(0)) / rr0))
+            hist.append(math.sqrt(OP.fsum_sq(H.residual(0)) / rr0))
         want_k, want_c = len(hist), hist[-1] < tol
-    assert want_c and NK.decisive(hist, tol), hist[-2:]
+    assert want_c and OC.decisive(hist, tol), hist[-2:]
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, shift=s, coefficient=a, neumann=_faces(bc), capacity=c)
     mg.upload_v(0, v0)
     mg.upload_f(0, f)
@@ -447,8 +444,9 @@ def test_pcg_matches_the_restatement(ctx, pcg_problem, krylov, bc):
     x = mg.download_v(0)
     assert bits_equal(mg.download_f(0), f), "d_f[0] was not restored"
     mg.close()
-    unk = NR.unknown_mask(n3, bc)
-    true_rel = math.sqrt(SH.fsum_sq(CA.residual(n3, UNIT, x, f, a, c, s, np.float64, bc)) / SH.fsum_sq(CA.residual(n3, UNIT, v0, f, a, c, s, np.float64, bc)))
+    unk = OP.unknown_mask(n3, bc)
+    op = OP.Op(n3, UNIT, np.float64, s, a, c, bc)
+    true_rel = math.sqrt(OP.fsum_sq(op.residual(x, f)) / OP.fsum_sq(op.residual(v0, f)))
     print("PCG krylov=%s bc=%d: %d iterations (restated %d), rel %.3e, restated residual of the result %.3e" % (krylov, bc, k, want_k, rel, true_rel))
     assert k == want_k and conv
     assert rel < tol and true_rel < tol and close(rel, true_rel, 1e-6)
@@ -463,13 +461,13 @@ def test_backward_euler_in_a_closed_box_keeps_the_heat_content(ctx, krylov):
     """17^3, all six faces walls, smooth a, c jumping by 100, five steps of c u_t = div(a grad u) with kappa dt = 1e-2 to 1e-10: the
     first step's right-hand side is the restated one, and sum(w c u) drifts by less than 1e-9 (relative)"""
     n3 = (17, 17, 17)
-    a, c, u0 = CO.smooth_coefficient(n3), CA.block_capacity(n3, 100, 1), NR.gaussian(n3)
-    W = NR.weights(n3, 63)
+    a, c, u0 = OC.smooth_coefficient(n3), OC.block_capacity(n3, 100, 1), OC.gaussian(n3)
+    W = OP.weights(n3, 63)
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=a, neumann=[1] * 6, capacity=c)
     mg.upload_v(0, u0)
     its, worst, conv = mg.BackwardEuler(1, 1e-2, 1.0, tol=1e-10, krylov=krylov)
     assert conv and mg.shift == 100.0
-    assert bits_equal(mg.download_f(0), CA.rhs(u0, c, None, 1.0, 100.0, np.float64, 63, f=mg.download_f(0)))
+    assert bits_equal(mg.download_f(0), OP.Op(n3, UNIT, np.float64, 100.0, c=c, bc=63).rhs(u0, None, 1.0, f=mg.download_f(0)))
     its4, worst4, conv4 = mg.BackwardEuler(4, 1e-2, 1.0, tol=1e-10, krylov=krylov)
     u = mg.download_v(0)
     mg.close()

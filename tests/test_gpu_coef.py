@@ -1,7 +1,7 @@
 """GPU suite: the variable-coefficient operator div(a grad u) - s u = f (csrc/mgx_coef3d.hip), the hierarchy that cycles with it
 (MultiGrid3D(coefficient=a), set_coefficient) and the solves and implicit heat steps on it.
 
-The four kernels are checked bit for bit against the numpy restatement of their arithmetic (tests/coef_restated.py), with poisoned
+The four kernels are checked bit for bit against the numpy restatement of their arithmetic (tests/op_restated.py), with poisoned
 pads; the coefficient of every level against the restated restriction chain; the cycles against the restated cycle, every level,
 bit for bit, eagerly and through captured graphs; the solver against the restated iteration counts; the time stepping against a
 constant-coefficient hierarchy and against each step's own linear system."""
@@ -12,11 +12,11 @@ import math
 import numpy as np
 import pytest
 
-import coef_restated as CO
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
 import semi_restated as S
-import shift_restated as SH
 from conftest import bits_equal
 from odd_shapes import pads_unchanged, run_poisoned
 from pde_multigrid_amd.multigrid import _ct, _ip, _rp, grid_spacing, xs_unpack
@@ -91,7 +91,7 @@ def test_relax_coef(ctx, n3, sweeps, rg, s, dtype):
     fn, ct = _fn("relax_coef", dtype)
     ups, outs = run_poisoned(ctx, [v, f, a], lambda x, b, c: fn(ctx._h, x, b, c, _ip(n3), _h(n3, rng, dtype), ct(s), C.c_int(sweeps)), dtype)
     assert ctx.last_relax_kernel().startswith("relax_coef3d_xs_kernel"), ctx.last_relax_kernel()
-    want = CO.relax(n3, rng, v, f, a, s, sweeps, dtype)
+    want = OP.Op(n3, rng, dtype, s, a).relax(v, f, sweeps)
     got = xs_unpack(outs[0], n3[0])
     assert bits_equal(got, want), np.argwhere(got != want)[:5]  # the interior, and the boundary as it was
     assert pads_unchanged(ups[0], outs[0], n3[0]) and bits_equal(outs[1], ups[1]) and bits_equal(outs[2], ups[2])
@@ -108,7 +108,7 @@ def test_relax_coef_from_zero(ctx, n3, rg, s, dtype):
     f[1:-1:2, 1:-1, 1:-1] = 0  # zero right-hand sides too: the signs of the zeros the first pass stores
     fn, ct = _fn("relax_coef_from_zero", dtype)
     for sweeps in (1, 2):
-        want = CO.relax(n3, rng, np.zeros_like(v), f, a, s, sweeps, dtype)
+        want = OP.Op(n3, rng, dtype, s, a).relax(np.zeros_like(v), f, sweeps)
         for rim_is_zero in (0, 1):
             v0 = v.copy()
             if rim_is_zero:  # the caller vouches for a zero boundary; the interior is stale
@@ -130,8 +130,8 @@ def test_residual_coef(ctx, n3, rg, s, dtype):
     rng = RANGES[rg]
     v, f, a, r0 = _rand(n3, dtype, 5), _rand(n3, dtype, 6), _coef(n3, dtype), _rand(n3, dtype, 7)
     fn, ct = _fn("residual_coef", dtype)
-    want = CO.residual(n3, rng, v, f, a, s, dtype)
-    want_ss = SH.fsum_sq(want)
+    want = OP.Op(n3, rng, dtype, s, a).residual(v, f)
+    want_ss = OP.fsum_sq(want)
     w = Work(ctx, n3, dtype)
     try:
         sums = []
@@ -162,7 +162,7 @@ def test_apply_coef_dot(ctx, n3, rg, s, dtype):
     rng = RANGES[rg]
     p, a, q0 = _rand(n3, dtype, 8), _coef(n3, dtype), _rand(n3, dtype, 9)
     fn, ct = _fn("apply_coef_dot", dtype)
-    want = CO.apply_A(n3, rng, p, a, s, dtype)
+    want = OP.Op(n3, rng, dtype, s, a).apply_A(p)
     w = Work(ctx, n3, dtype)
     try:
         sums = []
@@ -191,7 +191,7 @@ def test_relax_rows_knob_lowers_the_coefficient_pass_only(ctx, n3, dtype):
     v, f, a = _rand(n3, dtype, 1), _rand(n3, dtype, 2), _coef(n3, dtype)
     coef, ct = _fn("relax_coef", dtype)
     shift, _ = _fn("relax_shift", dtype)
-    want, want_shift = CO.relax(n3, rng, v, f, a, s, 1, dtype), SH.relax(n3, rng, v, f, s, 1, dtype)
+    want, want_shift = OP.Op(n3, rng, dtype, s, a).relax(v, f, 1), OP.Op(n3, rng, dtype, s).relax(v, f, 1)
     ups, outs = run_poisoned(ctx, [v, f], lambda x, b: shift(ctx._h, x, b, _ip(n3), _h(n3, rng, dtype), ct(s), C.c_int(1)), dtype)
     default_shift = ctx.last_relax_kernel()
     assert default_shift.startswith("relax_shift3d_xs_kernel") and bits_equal(xs_unpack(outs[0], n3[0]), want_shift)
@@ -250,7 +250,7 @@ def _mg(ctx, grid, dtype, s, a, v=None, f=None):
 
 def _restated(grid, dtype, s, a, v, f):
     n3, rng, how = GRIDS[grid]
-    H = CO.Hierarchy(n3, rng, a, s, dtype, how)
+    H = OP.Hierarchy(OP.Op(n3, rng, dtype, s, a), how)
     H.v[0], H.f[0] = v.copy(), f.copy()
     return H
 
@@ -273,16 +273,16 @@ def test_set_coefficient_restricts_down_the_levels(ctx, grid, dtype):
     assert not mg.has_coefficient
     mg.set_coefficient(a)
     assert mg.has_coefficient
-    sizes, masks = S.plan(n3, rng) if how == "semi" else SH.full_plan(n3)
+    sizes, masks = S.plan(n3, rng) if how == "semi" else OP.full_plan(n3)
     assert mg.masks == masks
     ptrs = [mg.grid(l).d_a for l in range(mg.maxGrids)]
-    for l, want in enumerate(CO.coarse_coefficients(sizes, masks, a, dtype)):
+    for l, want in enumerate(OP.coarse_coefficients(sizes, masks, a, dtype)):
         assert bits_equal(mg.download_coefficient(l), want), l
         assert want.min() >= 0.5
     b = _coef(n3, dtype, 101)  # new values: the same arrays
     mg.set_coefficient(b)
     assert [mg.grid(l).d_a for l in range(mg.maxGrids)] == ptrs
-    for l, want in enumerate(CO.coarse_coefficients(sizes, masks, b, dtype)):
+    for l, want in enumerate(OP.coarse_coefficients(sizes, masks, b, dtype)):
         assert bits_equal(mg.download_coefficient(l), want), l
     mg.set_coefficient(None)
     assert not mg.has_coefficient and all(not mg.grid(l).d_a for l in range(mg.maxGrids))
@@ -396,17 +396,17 @@ def test_relax_residual_and_norm_through_the_hierarchy(ctx, dtype):
     v, f, a = _rand(n3, dtype, 7), _rand(n3, dtype, 8), _coef(n3, dtype)
     mg = _mg(ctx, 1, dtype, s, a, v=v, f=f)
     mg.Relax(0, 3)
-    want = CO.relax(n3, rng, v, f, a, s, 3, dtype)
+    want = OP.Op(n3, rng, dtype, s, a).relax(v, f, 3)
     assert bits_equal(mg.download_v(0), want)
-    r = CO.residual(n3, rng, want, f, a, s, dtype)
+    r = OP.Op(n3, rng, dtype, s, a).residual(want, f)
     assert bits_equal(mg.CalculateResidual(0), r)
-    assert close(mg.ResidualNorm(0), math.sqrt(SH.fsum_sq(r)), 1e-12)
+    assert close(mg.ResidualNorm(0), math.sqrt(OP.fsum_sq(r)), 1e-12)
     mg.close()
 
 
 # ---------------------------------------------------------------------------------------------------------- solves
 PCG_N = (33, 33, 33)
-COEFS = {"smooth": lambda: CO.smooth_coefficient(PCG_N), "jump10": lambda: CO.jump_coefficient(PCG_N, 10)}
+COEFS = {"smooth": lambda: OC.smooth_coefficient(PCG_N), "jump10": lambda: OC.jump_coefficient(PCG_N, 10)}
 
 
 @pytest.mark.parametrize("krylov", [True, False])
@@ -418,9 +418,9 @@ def test_pcg_matches_restatement(ctx, which, s, krylov):
     v0 = np.zeros_like(f)
     v0[boundary_mask(n3)] = _rand(n3, np.float64, 9)[boundary_mask(n3)]  # Dirichlet data
     if krylov:
-        want_x, want_k, _, want_c = CO.fcg_restated(n3, UNIT, a, s, v0, f, CO.m_cycle(n3, UNIT, a, s, 2, 2), tol, 100)
+        want_x, want_k, _, want_c = OP.fcg(OP.Op(n3, UNIT, np.float64, s, a), v0, f, tol=tol, maxit=100)[:4]
     else:
-        want_x, want_k, _, want_c = CO.cycles_to(n3, UNIT, a, s, v0, f, 2, 2, tol, 100)
+        want_x, want_k, _, want_c = OP.cycles_to(OP.Op(n3, UNIT, np.float64, s, a), v0, f, 2, 2, tol, 100)
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, shift=s, coefficient=a)
     mg.upload_v(0, v0)
     mg.upload_f(0, f)
@@ -428,8 +428,8 @@ def test_pcg_matches_restatement(ctx, which, s, krylov):
     x = mg.download_v(0)
     assert bits_equal(mg.download_f(0), f), "d_f[0] was not restored"
     mg.close()
-    r, r0 = CO.residual(n3, UNIT, x, f, a, s, np.float64), CO.residual(n3, UNIT, v0, f, a, s, np.float64)
-    true_rel = math.sqrt(SH.fsum_sq(r) / SH.fsum_sq(r0))
+    r, r0 = OP.Op(n3, UNIT, np.float64, s, a).residual(x, f), OP.Op(n3, UNIT, np.float64, s, a).residual(v0, f)
+    true_rel = math.sqrt(OP.fsum_sq(r) / OP.fsum_sq(r0))
     print("PCG %s s=%g krylov=%s: %d iterations (restated %d), rel %.3e, restated residual of the result %.3e"
           % (which, s, krylov, k, want_k, rel, true_rel))
     assert k == want_k and conv == want_c and conv
@@ -478,17 +478,17 @@ def test_backward_euler_with_a_constant_coefficient_is_kappa(ctx):
 def test_backward_euler_steps_solve_their_own_systems(ctx):
     n3, kappa, dt, tol = EULER_N, 0.7, 3e-3, 1e-10
     s = 1.0 / (kappa * dt)
-    a = CO.smooth_coefficient(n3)
+    a = OC.smooth_coefficient(n3)
     u = _rand(n3, np.float64, 20)
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=a)
     mg.upload_v(0, u)
     for step in range(5):
         its, worst, conv = mg.BackwardEuler(1, dt, kappa, tol=tol)
         new = mg.download_v(0)
-        f = SH.rhs(u, None, 1.0 / kappa, mg.shift, np.float64)
+        f = OP.Op(n3, UNIT, np.float64, mg.shift).rhs(u, None, 1.0 / kappa)
         assert bits_equal(interior(mg.download_f(0)), interior(f)), "d_f[0] is not the step's right-hand side"
-        rel = math.sqrt(SH.fsum_sq(CO.residual(n3, UNIT, new, f, a, mg.shift, np.float64)) /
-                        SH.fsum_sq(CO.residual(n3, UNIT, u, f, a, mg.shift, np.float64)))
+        rel = math.sqrt(OP.fsum_sq(OP.Op(n3, UNIT, np.float64, mg.shift, a).residual(new, f)) /
+                        OP.fsum_sq(OP.Op(n3, UNIT, np.float64, mg.shift, a).residual(u, f)))
         print("backward Euler, smooth coefficient, step %d: %d iterations, residual %.3e (restated %.3e)" % (step, its, worst, rel))
         assert conv and worst < tol and rel < tol
         assert bits_equal(new[boundary_mask(n3)], u[boundary_mask(n3)]), "the Dirichlet data changed"

@@ -1,7 +1,7 @@
 """Harmonic-mean face coefficients on the GPU: the mgx3dxs_*_hmean entries (csrc/mgx_hmean3d.hip, the face
 unknowns in csrc/mgx_wall3d.hip), the hierarchy's switch (MultiGrid3D(face_mean="harmonic"), set_face_mean) and the solves on it.
 
-Every kernel is checked bit for bit against the numpy restatement of its arithmetic (tests/hmean_restated.py), with poisoned pads,
+Every kernel is checked bit for bit against the numpy restatement of its arithmetic (tests/op_restated.py), with poisoned pads,
 with and without a capacity, with masks and walls; the cycles against the restated cycle; the layered slab against its analytic
 series-resistance profile, which the arithmetic faces miss by orders of magnitude.
 
@@ -14,18 +14,14 @@ import math
 import numpy as np
 import pytest
 
-import cap_restated as CA
-import coef_restated as CO
-import hmean_restated as HM
-import neumann_krylov_restated as NK
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-import shift_restated as SH
 from conftest import bits_equal
 from odd_shapes import pads_unchanged, run_poisoned
 from pde_multigrid_amd.multigrid import _ct, _ip, _rp, grid_spacing, xs_unpack
-from robin_restated import ZERO
+from op_restated import ZERO
 from solve_restated import boundary_mask, close
 
 pytestmark = pytest.mark.gpu
@@ -61,7 +57,7 @@ def _coef(n3, dtype, seed=100):
 
 
 def _cap(n3, dtype, use):
-    return CA.random_capacity(n3, dtype, 200) if use else None
+    return OC.random_capacity(n3, dtype, 200) if use else None
 
 
 def _fn(name, dtype):
@@ -117,10 +113,10 @@ def _check_relax_hmean(ctx, n3, bc, s, dtype, cap):
     """1 and 3 sweeps: the restatement's bits; f, a, c, the Dirichlet entries and the pads as they were; twice, the same bits"""
     v, f, a, c = _rand(n3, dtype, 1), _rand(n3, dtype, 2), _coef(n3, dtype), _cap(n3, dtype, cap)
     fn, ct = _fn("relax_hmean_wall", dtype)
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     for beta in BETAS[bc]:
         for sweeps in (1, 3):
-            want = HM.relax(n3, RG, v, f, a, s, sweeps, dtype, c, bc, beta)
+            want = OP.Op(n3, RG, dtype, s, a, c, bc, beta, "harmonic").relax(v, f, sweeps)
             assert bits_equal(want[~unk], v[~unk])
             got = []
             for rep in range(2):
@@ -134,7 +130,7 @@ def _check_relax_hmean(ctx, n3, bc, s, dtype, cap):
             assert bits_equal(got[0], got[1])
     assert bits_equal(want, P.ops3dxs.relax_hmean(ctx, v, f, a, n3, RG, s, 3, c=c, bc=bc if bc else None, beta=beta if bc else None))
     if not cap and not bc:  # the faces are not the arithmetic ones
-        assert not bits_equal(want, CO.relax(n3, RG, v, f, a, s, 3, dtype))
+        assert not bits_equal(want, OP.Op(n3, RG, dtype, s, a).relax(v, f, 3))
 
 
 def _check_relax_hmean_from_zero(ctx, n3, s, dtype, cap):
@@ -142,7 +138,7 @@ def _check_relax_hmean_from_zero(ctx, n3, s, dtype, cap):
     f[1:-1:2, 1:-1, 1:-1] = 0  # zero right-hand sides too: the signs of the zeros the first pass stores
     fn, ct = _fn("relax_hmean_from_zero", dtype)
     for sweeps in (1, 3):
-        want = HM.relax_from_zero(n3, RG, f, a, s, sweeps, dtype, c)
+        want = OP.Op(n3, RG, dtype, s, a, c, mean="harmonic").relax(np.zeros(O.shape(n3), dtype), f, sweeps)
         for rim_is_zero in (0, 1):
             v0 = v.copy()
             if rim_is_zero:  # the caller vouches for a zero boundary; the interior is stale
@@ -162,8 +158,8 @@ def _check_residual_hmean(ctx, n3, bc, s, dtype, cap):
     w = Work(ctx, n3, dtype)
     try:
         for beta in BETAS[bc]:
-            want = HM.residual(n3, RG, v, f, a, s, dtype, c, bc, beta)
-            want_ss = SH.fsum_sq(want)
+            want = OP.Op(n3, RG, dtype, s, a, c, bc, beta, "harmonic").residual(v, f)
+            want_ss = OP.fsum_sq(want)
             sums = []
             for rep in range(2):
                 ups, outs = _run(ctx, [v, f, a, c, r0], lambda x, b, aa, cc, d: fn(ctx._h, x, b, aa, cc, d, _ip(n3), _h(n3, dtype), ct(s), w.work, w.sum,
@@ -188,13 +184,13 @@ def _check_residual_hmean(ctx, n3, bc, s, dtype, cap):
 
 def _check_apply_hmean_dot(ctx, n3, bc, s, dtype, cap):
     p, a, c, q0 = _rand(n3, dtype, 8), _coef(n3, dtype), _cap(n3, dtype, cap), _rand(n3, dtype, 9)
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     fn, ct = _fn("apply_hmean_dot_wall", dtype)
     w = Work(ctx, n3, dtype)
     try:
         for beta in BETAS[bc]:
-            want = HM.apply_A(n3, RG, p, a, s, dtype, c, bc, beta)
-            want_pq = NK.wdot(NR.weights(n3, bc), p, want)
+            want = OP.Op(n3, RG, dtype, s, a, c, bc, beta, "harmonic").apply_A(p)
+            want_pq = OP.wdot(OP.weights(n3, bc), p, want)
             sums = []
             for rep in range(2):
                 ups, outs = _run(ctx, [p, a, c, q0], lambda x, aa, cc, b: fn(ctx._h, x, aa, cc, b, _ip(n3), _h(n3, dtype), ct(s), w.work, w.sum,
@@ -255,7 +251,7 @@ def _check_cycles_match_the_restated_hierarchy(ctx, grid, dtype):
     those of the arithmetic hierarchy (a goes down the levels as it always did)"""
     n3, rng, how = GRIDS[grid]
     v, f, a = _rand(n3, dtype, 1), _rand(n3, dtype, 2), _coef(n3, dtype)
-    H = HM.Hierarchy(n3, rng, a, S_CYCLE, dtype=dtype, coarsening=how)
+    H = OP.Hierarchy(OP.Op(n3, rng, dtype, S_CYCLE, a, mean="harmonic"), how)
     H.v[0], H.f[0] = v.copy(), f.copy()
     mg = _mg(ctx, grid, dtype, a, v, f)
     assert mg.face_mean == "harmonic" and mg.has_coefficient
@@ -281,8 +277,8 @@ def _check_cycles_match_the_restated_hierarchy(ctx, grid, dtype):
 def _check_cycles_with_walls_and_a_capacity_match_the_restated_hierarchy(ctx, dtype):
     n3, rng, _ = GRIDS[0]
     bc, beta, g = 0b100101, (1.5, 0, 0.25, 0, 0, 0), (0, 0, -0.5, 0, 0, 2.0)
-    v, f, a, c = _rand(n3, dtype, 1), _rand(n3, dtype, 2), _coef(n3, dtype), CA.random_capacity(n3, dtype, 200)
-    H = HM.Hierarchy(n3, rng, a, S_CYCLE, c, bc, beta, g, dtype)
+    v, f, a, c = _rand(n3, dtype, 1), _rand(n3, dtype, 2), _coef(n3, dtype), OC.random_capacity(n3, dtype, 200)
+    H = OP.Hierarchy(OP.Op(n3, rng, dtype, S_CYCLE, a, c, bc, beta, "harmonic"), g=g)
     H.v[0], H.f[0] = v.copy(), f.copy()
     H.add_wall_flux()
     mg = _mg(ctx, 0, dtype, a, v, f, neumann=[(bc >> k) & 1 for k in range(6)], capacity=c, robin=beta, wall_flux=g)
@@ -296,7 +292,7 @@ def _check_cycles_with_walls_and_a_capacity_match_the_restated_hierarchy(ctx, dt
     H.relax(0, 1)
     r = H.residual(0)
     assert bits_equal(mg.CalculateResidual(0), r)
-    assert close(mg.ResidualNorm(0), math.sqrt(SH.fsum_sq(r)), 1e-12)
+    assert close(mg.ResidualNorm(0), math.sqrt(OP.fsum_sq(r)), 1e-12)
     mg.close()
 
 
@@ -309,7 +305,7 @@ def _pcg_problem():
     f = _rand(n3, np.float64, 5)
     v0 = np.zeros_like(f)
     v0[boundary_mask(n3)] = _rand(n3, np.float64, 9)[boundary_mask(n3)]  # Dirichlet data where a face is no wall
-    return CO.jump_coefficient(n3, 1000.0), f, v0
+    return OC.jump_coefficient(n3, 1000.0), f, v0
 
 
 # (krylov, mask, the restatement's count on this problem from a CPU run, maxit with room above it)
@@ -322,9 +318,9 @@ def _check_pcg_on_the_jump_of_1000(ctx, krylov, bc, count, maxit):
     n3, tol = PCG_N, 1e-10
     a, f, v0 = _pcg_problem()
     if krylov:
-        _, want_k, hist, want_c, _ = HM.fcg(n3, UNIT, a, 0.0, v0, f, bc=bc, tol=tol, maxit=maxit)
+        _, want_k, hist, want_c, _ = OP.fcg(OP.Op(n3, UNIT, np.float64, 0.0, a, bc=bc, mean="harmonic"), v0, f, tol=tol, maxit=maxit)[:5]
     else:
-        H = HM.Hierarchy(n3, UNIT, a, 0.0, bc=bc)
+        H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.0, a, bc=bc, mean="harmonic"))
         H.v[0], H.f[0] = v0.copy(), f.copy()
         want_k, _, want_c = H.cycle_to(2, 2, tol, maxit)
     assert want_c and want_k == count, (want_k, count)
@@ -334,8 +330,9 @@ def _check_pcg_on_the_jump_of_1000(ctx, krylov, bc, count, maxit):
     k, rel, conv, _ = mg.PCG(2, 2, tol, maxit, krylov=krylov)
     x = mg.download_v(0)
     mg.close()
-    unk = NR.unknown_mask(n3, bc)
-    true_rel = math.sqrt(SH.fsum_sq(HM.residual(n3, UNIT, x, f, a, 0.0, np.float64, bc=bc)) / SH.fsum_sq(HM.residual(n3, UNIT, v0, f, a, 0.0, np.float64, bc=bc)))
+    unk = OP.unknown_mask(n3, bc)
+    op = OP.Op(n3, UNIT, np.float64, 0.0, a, bc=bc, mean="harmonic")
+    true_rel = math.sqrt(OP.fsum_sq(op.residual(x, f)) / OP.fsum_sq(op.residual(v0, f)))
     print("PCG krylov=%s bc=%d: %d iterations (restated %d), rel %.3e, restated residual of the result %.3e" % (krylov, bc, k, want_k, rel, true_rel))
     assert conv and abs(k - want_k) <= 1, (k, want_k)
     assert rel < tol and true_rel < tol and close(rel, true_rel, 1e-6)
@@ -350,10 +347,10 @@ def _check_backward_euler_with_a_jumping_capacity(ctx):
     restatement takes 25 cycles): the first step's right-hand side is the restated one, the result the restated steps' to 1e-9 --
     the bound test_gpu_cap.py holds its own backward Euler test to -- and bit for bit where the cycle counts agree"""
     n3 = PCG_N
-    a, c = CO.jump_coefficient(n3, 1000.0), CA.block_capacity(n3, 100, 1)
-    u0 = NR.gaussian(n3)
+    a, c = OC.jump_coefficient(n3, 1000.0), OC.block_capacity(n3, 100, 1)
+    u0 = OC.gaussian(n3)
     u0[boundary_mask(n3)] = 0
-    H = HM.Hierarchy(n3, UNIT, a, 0.0, c=c)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.0, a, c, mean="harmonic"))
     H.v[0] = u0.copy()
     want_its, want_worst, want_conv = H.backward_euler(2, 1e-2, 1.0, 2, 2, 1e-10, 100)
     assert want_conv and want_its == 25, want_its
@@ -361,7 +358,7 @@ def _check_backward_euler_with_a_jumping_capacity(ctx):
     mg.upload_v(0, u0)
     its, worst, conv = mg.BackwardEuler(1, 1e-2, 1.0, tol=1e-10, krylov=False)
     assert conv and mg.shift == 100.0
-    assert bits_equal(mg.download_f(0)[~boundary_mask(n3)], CA.rhs(u0, c, None, 1.0, 100.0, np.float64)[~boundary_mask(n3)])
+    assert bits_equal(mg.download_f(0)[~boundary_mask(n3)], OP.Op(n3, UNIT, np.float64, 100.0, c=c).rhs(u0, None, 1.0)[~boundary_mask(n3)])
     its2, worst2, conv2 = mg.BackwardEuler(1, 1e-2, 1.0, tol=1e-10, krylov=False)
     u = mg.download_v(0)
     mg.close()
@@ -383,8 +380,8 @@ def _check_the_layered_slab_matches_the_series_resistance_profile(ctx, jump):
     """9 x 9 x 17, a1 below the interface midway between planes 8 and 9, a1 * jump above; insulated x/y faces, u = 0 and 1 on the z
     faces, f = 0: PCG(krylov="weighted") to 1e-12 gives the analytic piecewise-linear profile with harmonic faces; with
     arithmetic faces the same call is off by orders of magnitude more (0.036 and 0.059 of the unit drop in the restatement)"""
-    n3, rng = HM.SLAB_N3, HM.SLAB_RNG
-    a, u, _ = HM.slab(jump)
+    n3, rng = OC.SLAB_N3, OC.SLAB_RNG
+    a, u, _ = OC.slab(jump)
     v0 = u.copy()
     v0[1:-1] = 0.0
     bound = 10 * SLAB_RESTATED_ERROR[jump]
@@ -402,23 +399,20 @@ def _check_the_layered_slab_matches_the_series_resistance_profile(ctx, jump):
 # ---------------------------------------------------------------------------------------------------------- switching
 def _check_switching_the_mean_between_replayed_cycles(ctx, dtype):
     """use_graph: cycle arithmetic, switch to harmonic, cycle, switch back, cycle -- every cycle has the bits of an eager hierarchy
-    taken through the same switches and of the restated hierarchy of that mean, and the arithmetic cycle is coef_restated's"""
+    taken through the same switches and of the restated hierarchy of that mean"""
     n3, rng, how = GRIDS[0]
     v, f, a = _rand(n3, dtype, 1), _rand(n3, dtype, 2), _coef(n3, dtype)
     mg, eager = _mg(ctx, 0, dtype, a, v, f, mean="arithmetic"), _mg(ctx, 0, dtype, a, v, f, mean="arithmetic")
     mg.use_graph = True
-    H = HM.Hierarchy(n3, rng, a, S_CYCLE, dtype=dtype, mean="arithmetic")
-    K = CO.Hierarchy(n3, rng, a, S_CYCLE, dtype)
-    for X in (H, K):
-        X.v[0], X.f[0] = v.copy(), f.copy()
-    K.vcycle(0, 2, 2)
+    H = OP.Hierarchy(OP.Op(n3, rng, dtype, S_CYCLE, a))
+    H.v[0], H.f[0] = v.copy(), f.copy()
     for step, mean in enumerate(("arithmetic", "arithmetic", "harmonic", "harmonic", "arithmetic")):
         if mean != mg.face_mean:
             assert mg._mg.contents.graph_exec[0], "nothing was captured before the switch"
             mg.set_face_mean(mean)
             eager.set_face_mean(mean)
             assert not mg._mg.contents.graph_exec[0], "the switch kept a captured graph"
-        H.mean = mean
+        H.replace(mean=mean)
         assert mg.face_mean == eager.face_mean == mean
         mg.VCycle(0, 2, 2)
         eager.VCycle(0, 2, 2)
@@ -426,8 +420,6 @@ def _check_switching_the_mean_between_replayed_cycles(ctx, dtype):
         assert ("hmean" in ctx.last_relax_kernel()) == (mean == "harmonic"), ctx.last_relax_kernel()
         for l in range(mg.maxGrids):
             assert bits_equal(mg.download_v(l), eager.download_v(l)) and bits_equal(mg.download_v(l), H.v[l]), (step, mean, l)
-        if step == 0:
-            assert bits_equal(mg.download_v(0), K.v[0])
     mg.close()
     eager.close()
 

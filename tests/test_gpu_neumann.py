@@ -1,7 +1,7 @@
 """GPU suite: homogeneous Neumann faces (csrc/mgx_rim3d.hip), the hierarchy that cycles with a face mask
 (MultiGrid3D(neumann=...)) and the plain-cycling solve and implicit heat steps on it.
 
-The eight _bc kernel entries are checked bit for bit against the numpy restatement (tests/neumann_restated.py), with poisoned
+The eight _bc kernel entries are checked bit for bit against the numpy restatement (tests/op_restated.py), with poisoned
 pads, on rows longer than a wave, rows that end inside a tile and three-point axes (both mirrors of an axis are then the same
 point); mask 0 against the existing entries too.  The cycles against the restated cycle, every level, bit for bit, eagerly and
 through captured graphs, with the mask changed and cleared in between; the solver against the restated cycle counts; the time
@@ -13,12 +13,12 @@ import math
 import numpy as np
 import pytest
 
-import coef_restated as CO
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
 from conftest import bits_equal
-from neumann_restated import VCYCLE_CASES, gaussian, vcycle_case
+from op_cases import VCYCLE_CASES, gaussian, vcycle_case
 from odd_shapes import pads_unchanged, run_poisoned
 from pde_multigrid_amd.multigrid import _ct, _ip, _rp, grid_spacing, xs_unpack
 from solve_restated import close
@@ -92,7 +92,7 @@ def test_relax_bc(ctx, n3, coef, dtype):
     a = _rand(n3, dtype, 3, 0.5, 2.0) if coef else None
     fn, ct = _fn("relax_coef_bc" if coef else "relax_shift_bc", dtype)
     for bc in MASKS:
-        unk = NR.unknown_mask(n3, bc)
+        unk = OP.unknown_mask(n3, bc)
         for s in shifts(bc):
             for sweeps in (1, 3):
                 if coef:
@@ -102,7 +102,7 @@ def test_relax_bc(ctx, n3, coef, dtype):
                     ups, outs = run_poisoned(ctx, [v, f], lambda x, b: fn(ctx._h, x, b, _ip(n3), _h(n3, rng, dtype), ct(s), C.c_int(sweeps),
                                                                           C.c_int(bc)), dtype)
                 got = xs_unpack(outs[0], n3[0])
-                want = NR.relax(n3, rng, v, f, a, s, sweeps, bc, dtype)
+                want = OP.Op(n3, rng, dtype, s, a, bc=bc).relax(v, f, sweeps)
                 assert bits_equal(got, want), (bc, s, sweeps, np.argwhere(got != want)[:5])
                 assert bits_equal(got[~unk], v[~unk]), "a Dirichlet entry of v was written"
                 assert pads_unchanged(ups[0], outs[0], n3[0]) and all(bits_equal(o, u) for o, u in zip(outs[1:], ups[1:])), (bc, s, sweeps)
@@ -132,8 +132,8 @@ def test_residual_bc(ctx, n3, coef, dtype):
     try:
         for bc in MASKS:
             for s in shifts(bc):
-                want = NR.residual(n3, rng, v, f, a, s, bc, dtype)
-                want_ss = NR.fsum_sq(want)
+                want = OP.Op(n3, rng, dtype, s, a, bc=bc).residual(v, f)
+                want_ss = OP.fsum_sq(want)
                 sums = []
                 for rep in range(2):
                     ups, outs = run(ins + [r0], True, True, s, bc)
@@ -175,15 +175,15 @@ def test_transfers_bc(ctx, n3, dtype):
         for bc in MASKS:
             ups, outs = run_poisoned(ctx, [fine, coarse], lambda a, b: rfn(ctx._h, a, _ip(fn3), b, _ip(cn3), C.c_int(bc)), dtype)
             got = xs_unpack(outs[1], cn3[0])
-            assert bits_equal(got, NR.restrict(fn3, fine, bc, dtype)), ("restrict", fn3, bc)
+            assert bits_equal(got, OP.restrict(fn3, fine, bc, dtype)), ("restrict", fn3, bc)
             assert bits_equal(outs[0], ups[0]) and pads_unchanged(ups[1], outs[1], cn3[0])
             if bc == 0:
                 assert bits_equal(got, P.ops3dxs.restrict(ctx, fine, fn3))
             for add, kfn in ((False, ifn), (True, cfn)):
                 ups, outs = run_poisoned(ctx, [fine, coarse], lambda a, b: kfn(ctx._h, a, _ip(fn3), b, _ip(cn3), C.c_int(bc)), dtype)
                 got = xs_unpack(outs[0], fn3[0])
-                assert bits_equal(got, NR.interpolate(fn3, fine, coarse, bc, dtype, add=add)), ("interpolate", add, fn3, bc)
-                unk = NR.unknown_mask(fn3, bc)
+                assert bits_equal(got, OP.interpolate(fn3, fine, coarse, bc, dtype, add=add)), ("interpolate", add, fn3, bc)
+                unk = OP.unknown_mask(fn3, bc)
                 assert bits_equal(got[~unk], fine[~unk]), "a Dirichlet entry was written"
                 assert bits_equal(outs[1], ups[1]) and pads_unchanged(ups[0], outs[0], fn3[0])
                 if bc == 0:
@@ -200,10 +200,10 @@ def test_shift_rhs_bc(ctx, n3, dtype):
         for s in (0.75, 1e4):
             ups, outs = run_poisoned(ctx, [u, q, f0], lambda a, b, c: fn(ctx._h, a, b, ct(0.3), ct(s), c, _ip(n3), C.c_int(bc)), dtype)
             got = xs_unpack(outs[2], n3[0])
-            assert bits_equal(got, NR.rhs(u, q, 0.3, s, bc, dtype, f=f0)), (bc, s)  # the Dirichlet entries of f as they were
+            assert bits_equal(got, OP.Op(n3, UNIT, dtype, s, bc=bc).rhs(u, q, 0.3, f=f0)), (bc, s)  # the Dirichlet entries of f as they were
             assert bits_equal(outs[0], ups[0]) and bits_equal(outs[1], ups[1]) and pads_unchanged(ups[2], outs[2], n3[0])
             ups, outs = run_poisoned(ctx, [u, f0], lambda a, c: fn(ctx._h, a, None, ct(0.3), ct(s), c, _ip(n3), C.c_int(bc)), dtype)
-            assert bits_equal(xs_unpack(outs[1], n3[0]), NR.rhs(u, None, 0.3, s, bc, dtype, f=f0)), (bc, s)
+            assert bits_equal(xs_unpack(outs[1], n3[0]), OP.Op(n3, UNIT, dtype, s, bc=bc).rhs(u, None, 0.3, f=f0)), (bc, s)
             if bc == 0:
                 assert bits_equal(got, P.ops3dxs.shift_rhs(ctx, u, q, 0.3, s, n3, f=f0))
 
@@ -217,7 +217,7 @@ def test_set_rim_bc(ctx, n3, dtype):
         for value in (0.0, -2.5):
             ups, outs = run_poisoned(ctx, [v], lambda a: fn(ctx._h, a, _ip(n3), ct(value), C.c_int(bc)), dtype)
             want = v.copy()
-            want[NR.face_unknowns(n3, bc)] = value  # the interior and the Dirichlet entries as they were
+            want[OP.face_unknowns(n3, bc)] = value  # the interior and the Dirichlet entries as they were
             assert bits_equal(xs_unpack(outs[0], n3[0]), want), (bc, value)
             assert pads_unchanged(ups[0], outs[0], n3[0])
             assert bits_equal(P.ops3dxs.set_rim_bc(ctx, v, n3, value, bc), want)
@@ -263,7 +263,7 @@ FACES = lambda bc: [bool((bc >> k) & 1) for k in range(6)]
 
 def _mg(ctx, grid, dtype, bc, s, coef, v=None, f=None):
     n3, rng = GRIDS[grid]
-    mg = P.MultiGrid3D(ctx, n3, rng, dtype, residual_mode=P.CORRECT, shift=s, coefficient=CO.smooth_coefficient(n3, dtype) if coef else None,
+    mg = P.MultiGrid3D(ctx, n3, rng, dtype, residual_mode=P.CORRECT, shift=s, coefficient=OC.smooth_coefficient(n3, dtype) if coef else None,
                        neumann=FACES(bc))
     if v is not None:
         mg.upload_v(0, v)
@@ -274,7 +274,7 @@ def _mg(ctx, grid, dtype, bc, s, coef, v=None, f=None):
 
 def _restated(grid, dtype, bc, s, coef, v, f):
     n3, rng = GRIDS[grid]
-    H = NR.Hierarchy(n3, rng, CO.smooth_coefficient(n3, dtype) if coef else None, s, bc, dtype)
+    H = OP.Hierarchy(OP.Op(n3, rng, dtype, s, OC.smooth_coefficient(n3, dtype) if coef else None, bc=bc))
     H.v[0], H.f[0] = v.copy(), f.copy()
     return H
 
@@ -437,11 +437,11 @@ def test_relax_residual_and_norm_through_the_hierarchy(ctx, dtype):
     v, f = _rand(n3, dtype, 7), _rand(n3, dtype, 8)
     mg = _mg(ctx, 1, dtype, bc, s, False, v=v, f=f)
     mg.Relax(0, 3)
-    want = NR.relax(n3, rng, v, f, None, s, 3, bc, dtype)
+    want = OP.Op(n3, rng, dtype, s, bc=bc).relax(v, f, 3)
     assert bits_equal(mg.download_v(0), want)
-    r = NR.residual(n3, rng, want, f, None, s, bc, dtype)
+    r = OP.Op(n3, rng, dtype, s, bc=bc).residual(want, f)
     assert bits_equal(mg.CalculateResidual(0), r)
-    assert close(mg.ResidualNorm(0), math.sqrt(NR.fsum_sq(r)), 1e-12)  # all unknowns, unweighted
+    assert close(mg.ResidualNorm(0), math.sqrt(OP.fsum_sq(r)), 1e-12)  # all unknowns, unweighted
     mg.close()
 
 
@@ -451,7 +451,7 @@ def test_plain_cycling_counts_match_the_restatement(ctx, bc, s, coef):
     H = vcycle_case(bc, s, coef)
     n3, v0, f = H.sizes[0], H.v[0].copy(), H.f[0].copy()
     want_k, want_rel, want_c = H.cycle_to(2, 2, tol, 100)
-    a = CO.smooth_coefficient(n3) if coef else None
+    a = OC.smooth_coefficient(n3) if coef else None
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, shift=s, coefficient=a, neumann=FACES(bc))
     mg.upload_v(0, v0)
     mg.upload_f(0, f)
@@ -461,7 +461,7 @@ def test_plain_cycling_counts_match_the_restatement(ctx, bc, s, coef):
     mg.close()
     print("bc %d s %g coef %d: %d cycles (restated %d), rel %.3e (restated %.3e)" % (bc, s, coef, k, want_k, rel, want_rel))
     assert (k, conv) == (want_k, want_c) and conv and rel < tol and close(rel, want_rel, 1e-6)
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     assert bits_equal(x[~unk], v0[~unk]), "the boundary data were changed"
     assert bits_equal(x, H.v[0])
     x2, k2, rel2, conv2 = P.solve3d_pcg(ctx, v0, f, UNIT, tol=tol, krylov=False, shift=s, coefficient=a, neumann=FACES(bc))
@@ -475,8 +475,8 @@ def test_backward_euler_in_a_closed_box_keeps_the_heat_content(ctx, kdt):
     five steps solved to 1e-10: the relative drift of sum(w u) stays below 1e-9"""
     n3 = (17, 17, 17)
     u0 = gaussian(n3)
-    W = NR.weights(n3, 63)
-    mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=CO.smooth_coefficient(n3), neumann=[1] * 6)
+    W = OP.weights(n3, 63)
+    mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=OC.smooth_coefficient(n3), neumann=[1] * 6)
     mg.upload_v(0, u0)
     its, worst, conv = mg.BackwardEuler(5, kdt, 1.0, tol=1e-10, maxit=50, krylov=False)
     u = mg.download_v(0)
@@ -486,7 +486,7 @@ def test_backward_euler_in_a_closed_box_keeps_the_heat_content(ctx, kdt):
     print("kappa dt %g: %d cycles, worst relative residual %.3e, relative drift of the heat content %.3e" % (kdt, its, worst, drift))
     assert conv and worst < 1e-10
     assert drift < 1e-9, drift
-    H = NR.Hierarchy(n3, UNIT, CO.smooth_coefficient(n3), 0.0, 63)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.0, OC.smooth_coefficient(n3), bc=63))
     H.v[0] = u0.copy()
     want_its, _, _ = H.backward_euler(5, kdt, 1.0, 2, 2, 1e-10, 50)
     assert its == want_its and bits_equal(u, H.v[0])
@@ -503,13 +503,13 @@ def test_backward_euler_step_against_its_own_linear_system(ctx):
     u, rhs_dev = mg.download_v(0), mg.download_f(0)
     assert mg.shift == s
     mg.close()
-    f = NR.rhs(u0, q, 1.0 / kappa, s, bc, np.float64, f=f0)
+    f = OP.Op(n3, UNIT, np.float64, s, bc=bc).rhs(u0, q, 1.0 / kappa, f=f0)
     assert bits_equal(rhs_dev, f), "d_f[0] is not the step's right-hand side on the unknowns and what it was elsewhere"
-    res = lambda x: NR.fsum_sq(NR.residual(n3, rng, x, f, None, s, bc, np.float64))
+    res = lambda x: OP.fsum_sq(OP.Op(n3, rng, np.float64, s, bc=bc).residual(x, f))
     rel = math.sqrt(res(u) / res(u0))
     print("one step, bc %d: %d cycles, residual %.3e (restated %.3e)" % (bc, its, worst, rel))
     assert conv and worst < tol and rel < tol and close(worst, rel, 1e-6)
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     assert bits_equal(u[~unk], u0[~unk]), "the Dirichlet data changed"
 
 
@@ -554,7 +554,7 @@ def test_refusals_leave_the_hierarchy_usable(ctx):
     mg.shift = 0.75
     mg.upload_v(0, v)
     mg.VCycle(0, 2, 2)  # still usable
-    H = NR.Hierarchy(n3, UNIT, None, 0.75, 63)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.75, bc=63))
     H.v[0], H.f[0] = v.copy(), f.copy()
     H.vcycle(0, 2, 2)
     assert bits_equal(mg.download_v(0), H.v[0])

@@ -4,7 +4,7 @@ The vector entries for all unknowns (mgx3dxs_*_bc of csrc/mgx_rim3d.hip: laplace
 cg_direction, project) are checked on test_gpu_neumann.py's shapes and masks: the arrays bit for bit against numpy with poisoned
 pads, Dirichlet entries and read-only arguments unchanged, the sums against math.fsum to 1e-13 of the sum of the absolute terms
 and equal on two runs with NaN guards behind the work array, mask 0 against the existing entries.  The solves against the
-restatement (tests/neumann_krylov_restated.py): iteration counts, residuals, what a solve leaves behind, graphs against eager
+restatement (tests/op_restated.py): iteration counts, residuals, what a solve leaves behind, graphs against eager
 runs, the closed box without a shift."""
 import ctypes as C
 import math
@@ -12,14 +12,12 @@ import math
 import numpy as np
 import pytest
 
-import coef_restated as CO
-import neumann_krylov_restated as KR
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
 from conftest import bits_equal
-from neumann_krylov_restated import CASES, TOL, UNIT
-from neumann_restated import gaussian
+from op_cases import CASES, TOL, UNIT, gaussian
 from odd_shapes import pads_unchanged, run_poisoned
 from pde_multigrid_amd.multigrid import _ct, _ip, _rp, grid_spacing, xs_unpack
 
@@ -104,10 +102,10 @@ def test_apply_dot_bc(ctx, n3, coef, dtype):
     w = Work(ctx, n3, dtype)
     try:
         for bc in MASKS:
-            unk, W = NR.unknown_mask(n3, bc), NR.weights(n3, bc)
+            unk, W = OP.unknown_mask(n3, bc), OP.weights(n3, bc)
             for s in (0.0, 0.75):
                 want = q0.copy()
-                want[unk] = NR.apply_A(n3, rng, p, a, s, bc, dtype)[unk]  # the Dirichlet entries of q are not written
+                want[unk] = OP.Op(n3, rng, dtype, s, a, bc=bc).apply_A(p)[unk]  # the Dirichlet entries of q are not written
                 sums = []
                 for rep in range(2):
                     ups, outs = run_poisoned(ctx, ins + [q0], lambda *d: fn(ctx._h, *d, _ip(n3), _h(n3, rng, dtype), ct(s), w.work, w.sum,
@@ -135,7 +133,7 @@ def test_cg_update_bc(ctx, n3, dtype):
     w = Work(ctx, n3, dtype, (alpha, 0.0))
     try:
         for bc in MASKS:
-            unk = NR.unknown_mask(n3, bc)
+            unk = OP.unknown_mask(n3, bc)
             wx, wr = x.copy(), r.copy()
             wx[unk] = (x + al * p)[unk]
             wr[unk] = (r - al * q)[unk]
@@ -167,7 +165,7 @@ def test_dot2_bc(ctx, n3, dtype):
     a64, b64, c64 = (t.astype(np.float64) for t in (a, b, c))
     try:
         for bc in MASKS:
-            W = NR.weights(n3, bc)
+            W = OP.weights(n3, bc)
             for two in (True, False):
                 sums = []
                 for rep in range(2):
@@ -197,7 +195,7 @@ def test_cg_direction_bc(ctx, n3, dtype):
     forms = [(False, True, False), (True, True, True), (True, False, False), (True, True, False), (False, True, True)]
     try:
         for bc in MASKS:
-            unk = NR.unknown_mask(n3, bc)
+            unk = OP.unknown_mask(n3, bc)
             for fx, fz, fb in forms:
                 wx, wp = x.copy(), p.copy()
                 if fx:
@@ -224,8 +222,8 @@ def test_project_bc(ctx, n3, dtype):
     w = Work(ctx, n3, dtype)
     try:
         for bc in MASKS:
-            unk, W = NR.unknown_mask(n3, bc), NR.weights(n3, bc)
-            sw = KR.sum_weights(n3, bc)
+            unk, W = OP.unknown_mask(n3, bc), OP.weights(n3, bc)
+            sw = OP.sum_weights(n3, bc)
             means = []
             for rep in range(2):
                 ups, outs = run_poisoned(ctx, [a], lambda ad: fn(ctx._h, ad, _ip(n3), w.work, w.sum, C.c_int(bc)), dtype)
@@ -261,8 +259,8 @@ def test_entries_reject_bad_masks_and_sizes(ctx, dtype):
             call()
         assert e.value.status == P.MGX_ERR_SIZE
     q, pq = ops.laplace_dot_shift_bc(ctx, a, n3, RG, 1.0, 37)  # the wrappers themselves
-    want = NR.apply_A(n3, RG, a, None, 1.0, 37, dtype)
-    want[~NR.unknown_mask(n3, 37)] = 0.0  # the Dirichlet entries of the wrapper's zero-filled q, unwritten
+    want = OP.Op(n3, RG, dtype, 1.0, bc=37).apply_A(a)
+    want[~OP.unknown_mask(n3, 37)] = 0.0  # the Dirichlet entries of the wrapper's zero-filled q, unwritten
     assert bits_equal(q, want)
     got, mean = ops.project_bc(ctx, a, n3, 63)
     assert bits_equal(got, a - dtype(mean))
@@ -270,7 +268,7 @@ def test_entries_reject_bad_masks_and_sizes(ctx, dtype):
 
 # ---------------------------------------------------------------------------------------------------------- solves
 def _mg(ctx, n3, bc, s, kind, v0, f, dtype=np.float64):
-    mg = P.MultiGrid3D(ctx, n3, UNIT, dtype, residual_mode=P.CORRECT, shift=s, coefficient=KR.coefficient(n3, kind, dtype), neumann=FACES(bc))
+    mg = P.MultiGrid3D(ctx, n3, UNIT, dtype, residual_mode=P.CORRECT, shift=s, coefficient=OC.coefficient(n3, kind, dtype), neumann=FACES(bc))
     mg.upload_v(0, v0)
     mg.upload_f(0, f)
     return mg
@@ -278,9 +276,9 @@ def _mg(ctx, n3, bc, s, kind, v0, f, dtype=np.float64):
 
 def _true_rel(n3, bc, s, kind, x, v0, f, removed=0.0, dtype=np.float64):
     """the restated true relative residual of x against f - removed"""
-    a = KR.coefficient(n3, kind, dtype)
+    a = OC.coefficient(n3, kind, dtype)
     fp = (f - dtype(removed)).astype(dtype) if removed else f
-    res = lambda y: KR.fsum_sq(NR.residual(n3, UNIT, y, fp, a, s, bc, dtype))
+    res = lambda y: OP.fsum_sq(OP.Op(n3, UNIT, dtype, s, a, bc=bc).residual(y, fp))
     return math.sqrt(res(x) / res(v0))
 
 
@@ -292,8 +290,8 @@ def test_table_cases_match_the_restated_solver(ctx, case, size):
     a factor 1.5 from tol on both sides of the deciding iteration (within 2 where it does not: a count may then flip)"""
     bc, s, kind = CASES[case][:3]
     n3 = (size,) * 3
-    v0, f = KR.table_start(case, n3)
-    x_r, k_r, hist_r, conv_r, rel_r, removed_r = KR.solved(case, size)
+    v0, f = OC.table_start(case, n3)
+    x_r, k_r, hist_r, conv_r, rel_r, removed_r = OC.solved(case, size)
     mg = _mg(ctx, n3, bc, s, kind, v0, f)
     k, rel, conv, hist = mg.PCG(2, 2, TOL, 60, krylov="weighted")
     x, removed = mg.download_v(0), mg.pcg_removed_mean
@@ -301,13 +299,13 @@ def test_table_cases_match_the_restated_solver(ctx, case, size):
     mg.close()
     want = _true_rel(n3, bc, s, kind, x, v0, f, removed)
     print("case %r at %d^3: %d iterations (restated %d, decisive %s), rel %.3e (restated of x %.3e)" % (CASES[case][:3], size, k, k_r,
-                                                                                                          KR.decisive(hist_r), rel, want))
+                                                                                                          OC.decisive(hist_r), rel, want))
     assert conv and conv_r and rel < TOL and want < TOL and abs(rel - want) <= 1e-6 * want
-    if KR.decisive(hist_r):
+    if OC.decisive(hist_r):
         assert k == k_r == CASES[case][3 + (size == 33)]
     else:
         assert abs(k - k_r) <= 2
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     assert bits_equal(x[~unk], v0[~unk]), "the Dirichlet data were changed"
     if not (bc == 63 and s == 0):
         assert removed == 0.0
@@ -317,8 +315,8 @@ def test_table_cases_match_the_restated_solver(ctx, case, size):
 def test_jump_1000_converges_where_plain_cycling_does_not(ctx, case):
     bc, s, kind = CASES[case][:3]
     n3 = (33, 33, 33)
-    v0, f = KR.start(n3)
-    k_r, conv_r = KR.solved(case, 33)[1], KR.solved(case, 33)[3]
+    v0, f = OC.start(n3)
+    k_r, conv_r = OC.solved(case, 33)[1], OC.solved(case, 33)[3]
     mg = _mg(ctx, n3, bc, s, kind, v0, f)
     k, rel, conv, _ = mg.PCG(2, 2, TOL, 60, krylov="weighted")
     mg.upload_v(0, v0)
@@ -331,8 +329,8 @@ def test_jump_1000_converges_where_plain_cycling_does_not(ctx, case):
 
 def test_fp32_solve_in_the_closed_box(ctx):
     n3, bc, s, tol, dt = (17, 17, 17), 63, 100.0, 1e-4, np.float32
-    v0, f = KR.start(n3, dt)
-    x_r, k_r, hist_r, conv_r, rel_r, _ = KR.wfcg(n3, UNIT, None, s, bc, v0, f, tol=tol, dtype=dt)
+    v0, f = OC.start(n3, dt)
+    x_r, k_r, hist_r, conv_r, rel_r, _ = OP.fcg(OP.Op(n3, UNIT, dt, s, bc=bc), v0, f, tol=tol)
     mg = _mg(ctx, n3, bc, s, None, v0, f, dt)
     k, rel, conv, _ = mg.PCG(2, 2, tol, 60, krylov=2)
     x = mg.download_v(0)
@@ -347,7 +345,7 @@ def test_fp32_solve_in_the_closed_box(ctx):
 def test_graph_replay_gives_the_eager_bits(ctx, case):
     bc, s, kind = CASES[case][:3]
     n3 = (17, 17, 17)
-    v0, f = KR.start(n3)
+    v0, f = OC.start(n3)
     mg = _mg(ctx, n3, bc, s, kind, v0, f)
     k0, rel0, conv0, hist0 = mg.PCG(2, 2, TOL, 60, krylov="weighted")
     x0 = mg.download_v(0)
@@ -372,7 +370,7 @@ def test_weighted_without_a_mask_is_krylov_1(ctx, s, kind, dtype):
     v0, f = _rand(n3, dtype, 1), _rand(n3, dtype, 2)
     out = []
     for krylov in (True, "weighted"):
-        mg = P.MultiGrid3D(ctx, n3, RG, dtype, residual_mode=P.CORRECT, shift=s, coefficient=KR.coefficient(n3, kind, dtype))
+        mg = P.MultiGrid3D(ctx, n3, RG, dtype, residual_mode=P.CORRECT, shift=s, coefficient=OC.coefficient(n3, kind, dtype))
         mg.upload_v(0, v0)
         mg.upload_f(0, f)
         k, rel, conv, hist = mg.PCG(2, 2, tol, 50, krylov=krylov)
@@ -386,7 +384,7 @@ def test_mask_cleared_after_a_masked_solve(ctx):
     """p and q hold values on the face unknowns during a solve with a mask and krylov = 1 reads p's boundary as zero Dirichlet
     data: after the mask is cleared it gives the bits of a hierarchy that never had one"""
     n3, tol = (17, 17, 17), 1e-10
-    v0, f = KR.start(n3)
+    v0, f = OC.start(n3)
     mg = _mg(ctx, n3, 63, 0.0, None, v0, f)
     k, rel, conv, _ = mg.PCG(2, 2, tol, 60, krylov="weighted")  # the singular solve: the projections too
     assert conv and mg.pcg_removed_mean != 0.0
@@ -411,7 +409,7 @@ def test_mask_cleared_after_a_masked_solve(ctx):
 
 def test_krylov_1_with_a_mask_names_krylov_2(ctx):
     n3 = (17, 17, 17)
-    v0, f = KR.start(n3)
+    v0, f = OC.start(n3)
     mg = _mg(ctx, n3, 17, 0.0, None, v0, f)
     for call in (lambda: mg.PCG(2, 2, 1e-8, 5, krylov=True), lambda: mg.BackwardEuler(1, 1e-2, 1.0, krylov=True)):
         with pytest.raises(P.MgxError) as e:
@@ -430,8 +428,8 @@ def test_backward_euler_in_a_closed_box_keeps_the_heat_content(ctx, kdt):
     data, five steps solved to 1e-10: the relative drift of sum(w u) stays below 1e-9"""
     n3 = (17, 17, 17)
     u0 = gaussian(n3)
-    W = NR.weights(n3, 63)
-    mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=CO.smooth_coefficient(n3), neumann=[1] * 6)
+    W = OP.weights(n3, 63)
+    mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=OC.smooth_coefficient(n3), neumann=[1] * 6)
     mg.upload_v(0, u0)
     its, worst, conv = mg.BackwardEuler(5, kdt, 1.0, tol=1e-10, maxit=50, krylov="weighted")
     u = mg.download_v(0)
@@ -454,13 +452,13 @@ def test_backward_euler_step_against_its_own_linear_system(ctx):
     u, rhs_dev = mg.download_v(0), mg.download_f(0)
     assert mg.shift == s
     mg.close()
-    f = NR.rhs(u0, q, 1.0 / kappa, s, bc, np.float64, f=f0)
+    f = OP.Op(n3, UNIT, np.float64, s, bc=bc).rhs(u0, q, 1.0 / kappa, f=f0)
     assert bits_equal(rhs_dev, f), "d_f[0] is not the step's right-hand side on the unknowns and what it was elsewhere"
-    res = lambda x: NR.fsum_sq(NR.residual(n3, UNIT, x, f, None, s, bc, np.float64))
+    res = lambda x: OP.fsum_sq(OP.Op(n3, UNIT, np.float64, s, bc=bc).residual(x, f))
     rel = math.sqrt(res(u) / res(u0))
     print("one step, bc %d: %d iterations, residual %.3e (restated %.3e)" % (bc, its, worst, rel))
     assert conv and worst < tol and rel < tol and abs(worst - rel) <= 1e-6 * rel
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     assert bits_equal(u[~unk], u0[~unk]), "the Dirichlet data changed"
 
 
@@ -468,12 +466,12 @@ def test_backward_euler_step_against_its_own_linear_system(ctx):
 def test_solve3d_pcg_equals_the_hierarchy_call(ctx, case):
     bc, s, kind = CASES[case][:3]
     n3 = (17, 17, 17)
-    v0, f = KR.start(n3)
+    v0, f = OC.start(n3)
     mg = _mg(ctx, n3, bc, s, kind, v0, f)
     k, rel, conv, _ = mg.PCG(2, 2, TOL, 60, krylov="weighted")
     x = mg.download_v(0)
     mg.close()
-    x2, k2, rel2, conv2 = P.solve3d_pcg(ctx, v0, f, UNIT, tol=TOL, maxit=60, krylov="weighted", shift=s, coefficient=KR.coefficient(n3, kind),
+    x2, k2, rel2, conv2 = P.solve3d_pcg(ctx, v0, f, UNIT, tol=TOL, maxit=60, krylov="weighted", shift=s, coefficient=OC.coefficient(n3, kind),
                                         neumann=FACES(bc))
     assert conv and (k2, rel2, conv2) == (k, rel, conv) and bits_equal(x2, x)
 
@@ -487,23 +485,23 @@ def test_singular_solve(ctx, case, size):
     operator as before, and cycles with a shift like any other"""
     bc, s, kind = CASES[case][:3]
     n3 = (size,) * 3
-    v0, f = KR.start(n3)
-    x_r, k_r, hist_r, conv_r, rel_r, removed_r = KR.solved(case, size)
-    W = NR.weights(n3, 63)
+    v0, f = OC.start(n3)
+    x_r, k_r, hist_r, conv_r, rel_r, removed_r = OC.solved(case, size)
+    W = OP.weights(n3, 63)
     mg = _mg(ctx, n3, bc, s, kind, np.zeros_like(v0), f)
     k, rel, conv, _ = mg.PCG(2, 2, TOL, 60, krylov="weighted")
     x0, removed = mg.download_v(0), mg.pcg_removed_mean
-    assert conv and rel < TOL and abs(KR.wmean(W, x0)) <= 1e-12 * np.abs(x0).max()
+    assert conv and rel < TOL and abs(OP.wmean(W, x0)) <= 1e-12 * np.abs(x0).max()
     mg.upload_v(0, v0)
     k_rand, rel_rand, conv_rand, _ = mg.PCG(2, 2, TOL, 60, krylov="weighted")
     x = mg.download_v(0)
     assert conv_rand and rel_rand < TOL and mg.pcg_removed_mean == removed
-    print("case %r at %d^3: %d iterations (restated %d, decisive %s), removed mean %.17g" % (CASES[case][:3], size, k, k_r, KR.decisive(hist_r),
+    print("case %r at %d^3: %d iterations (restated %d, decisive %s), removed mean %.17g" % (CASES[case][:3], size, k, k_r, OC.decisive(hist_r),
                                                                                              removed))
-    assert k == k_r == CASES[case][3 + (size == 33)] if KR.decisive(hist_r) else abs(k - k_r) <= 2
-    want = math.fsum((W * f).ravel()) / KR.sum_weights(n3, 63)
+    assert k == k_r == CASES[case][3 + (size == 33)] if OC.decisive(hist_r) else abs(k - k_r) <= 2
+    want = math.fsum((W * f).ravel()) / OP.sum_weights(n3, 63)
     assert removed_r == want and abs(removed - want) <= 1e-12 * abs(want)
-    assert abs(KR.wmean(W, x) - KR.wmean(W, v0)) <= 1e-12 * np.abs(x).max()
+    assert abs(OP.wmean(W, x) - OP.wmean(W, v0)) <= 1e-12 * np.abs(x).max()
     assert mg._mg.contents.bc_reserved == 0
     for call in (lambda: mg.VCycle(0, 2, 2), lambda: mg.Relax(0, 1), lambda: mg.ResidualNorm(0), lambda: mg.PCG(2, 2, TOL, 5, krylov=False),
                  lambda: mg.PCG(2, 2, TOL, 5, krylov=True)):
@@ -517,7 +515,7 @@ def test_singular_solve(ctx, case, size):
     mg.upload_v(0, v0)
     mg.VCycle(0, 2, 2)
     assert mg.PCG(2, 2, TOL, 60, krylov="weighted")[2] and mg.pcg_removed_mean == 0.0  # written as 0 by every other solve
-    H = NR.Hierarchy(n3, UNIT, KR.coefficient(n3, kind), 0.75, 63)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.75, OC.coefficient(n3, kind), bc=63))
     H.v[0], H.f[0] = v0.copy(), f.copy()
     H.vcycle(0, 2, 2)
     mg.upload_v(0, v0)

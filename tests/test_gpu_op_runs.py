@@ -8,7 +8,7 @@ and on every shape small enough for a test it picks the shortest one: 1 plane fo
 read), 2 coarse planes for the transfers.  "relax3d.zchunk" and "residual_restrict3d.pzchunk" set the run lengths here, so that
 the carried values, runs that do not divide the planes and runs longer than the grid are all exercised; one test uses grids long enough along z for the host's own rule to choose runs of 4 and of 2 planes.
 
-Everything is compared bit for bit with the numpy restatements (shift_restated, coef_restated, neumann_restated,
+Everything is compared bit for bit with the numpy restatements (op_restated,
 semi_restated), computed once per case and shared by all run lengths: the run length never changes a result.  All arrays are
 random, the coefficient included, so that they vary along z."""
 import copy
@@ -20,12 +20,11 @@ import sys
 import numpy as np
 import pytest
 
-import coef_restated as CO
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
 import semi_restated as S
-import shift_restated as SH
 from conftest import bits_equal
 from odd_shapes import pads_unchanged, run_poisoned
 from pde_multigrid_amd.multigrid import _ct, _ip, _rp, grid_spacing, xs_unpack
@@ -156,7 +155,7 @@ def test_relax_shift_runs(ctx, num_cus, n3, dtype):
     rim = boundary_mask(n3)
     for s in (0.0, 0.75):
         for sweeps in (1, 2):
-            want = SH.relax(n3, RG, v, f, s, sweeps, dtype)
+            want = OP.Op(n3, RG, dtype, s).relax(v, f, sweeps)
             _check_relax(ctx, "relax_shift", "relax_shift3d_xs_kernel", dtype, n3, [v, f], s, sweeps, (), want, rim, 4, num_cus, (s, sweeps))
 
 
@@ -170,7 +169,7 @@ def test_relax_coef_runs(ctx, num_cus, n3, rows, dtype):
         k.set("relax3d.rows", rows)
         for s in (0.0, 0.75):
             for sweeps in (1, 2):
-                want = CO.relax(n3, RG, v, f, a, s, sweeps, dtype)
+                want = OP.Op(n3, RG, dtype, s, a).relax(v, f, sweeps)
                 _check_relax(ctx, "relax_coef", "relax_coef3d_xs_kernel", dtype, n3, [v, f, a], s, sweeps, (), want, rim, rows, num_cus,
                              (rows, s, sweeps))
 
@@ -188,7 +187,7 @@ def test_relax_from_zero_runs(ctx, num_cus, n3, coef, dtype):
     rim = boundary_mask(n3)
     for s in (0.0, 0.75):
         zero = np.zeros_like(v)
-        want = CO.relax(n3, RG, zero, f, a, s, 2, dtype) if coef else SH.relax(n3, RG, zero, f, s, 2, dtype)
+        want = OP.Op(n3, RG, dtype, s, a).relax(zero, f, 2) if coef else OP.Op(n3, RG, dtype, s).relax(zero, f, 2)
         for rim_is_zero in (0, 1):
             v0 = v.copy()
             if rim_is_zero:  # the caller vouches for a zero boundary, which then stays as it is; the interior is stale
@@ -207,10 +206,10 @@ def test_relax_bc_runs(ctx, num_cus, n3, coef, dtype):
     a = _coef(n3, dtype, 3) if coef else None
     entry, kernel = ("relax_coef_bc", "relax_coef3d_xs_kernel") if coef else ("relax_shift_bc", "relax_shift3d_xs_kernel")
     for bc, shifts in ((37, (0.0, 0.75)), (63, (0.75,))):  # a closed box without a shift is singular
-        unk = NR.unknown_mask(n3, bc)
+        unk = OP.unknown_mask(n3, bc)
         for s in shifts:
             for sweeps in (1, 2):
-                want = NR.relax(n3, RG, v, f, a, s, sweeps, bc, dtype)
+                want = OP.Op(n3, RG, dtype, s, a, bc=bc).relax(v, f, sweeps)
                 _check_relax(ctx, entry, kernel, dtype, n3, [v, f] + ([a] if coef else []), s, sweeps, (bc,), want, ~unk, 4, num_cus,
                              (bc, s, sweeps))
 
@@ -249,15 +248,15 @@ def test_the_hosts_rule_chooses_multi_plane_runs(ctx, num_cus, entry, rows, zchu
     v, f = _rand(n3, dtype, 1), _rand(n3, dtype, 2)
     s, extra, a = 0.75, (), None
     if entry == "relax_shift":
-        kernel, want, keep = "relax_shift3d_xs_kernel", SH.relax(n3, RG, v, f, s, 1, dtype), boundary_mask(n3)
+        kernel, want, keep = "relax_shift3d_xs_kernel", OP.Op(n3, RG, dtype, s).relax(v, f, 1), boundary_mask(n3)
     else:
         a = _coef(n3, dtype)
         kernel = "relax_coef3d_xs_kernel"
         if entry == "relax_coef":
-            want, keep = CO.relax(n3, RG, v, f, a, s, 1, dtype), boundary_mask(n3)
+            want, keep = OP.Op(n3, RG, dtype, s, a).relax(v, f, 1), boundary_mask(n3)
         else:
             extra = (63,)
-            want, keep = NR.relax(n3, RG, v, f, a, s, 1, 63, dtype), ~NR.unknown_mask(n3, 63)
+            want, keep = OP.Op(n3, RG, dtype, s, a, bc=63).relax(v, f, 1), ~OP.unknown_mask(n3, 63)
     with knobs(ctx) as k:
         k.set("relax3d.rows", rows)
         ups, outs = _relax_call(ctx, entry, dtype, n3, [v, f] + ([] if a is None else [a]), s, 1, extra)
@@ -279,16 +278,16 @@ FACES = [bool((CYCLE_BC >> k) & 1) for k in range(6)]
 def _restated(op, grid, dtype):
     n3, rng, how = CYCLE_GRIDS[grid]
     if op == "shift":
-        return SH.Hierarchy(n3, rng, CYCLE_S, dtype, how)
+        return OP.Hierarchy(OP.Op(n3, rng, dtype, CYCLE_S), how)
     if op == "coef":
-        return CO.Hierarchy(n3, rng, CO.smooth_coefficient(n3, dtype), CYCLE_S, dtype, how)
-    return NR.Hierarchy(n3, rng, CO.smooth_coefficient(n3, dtype), CYCLE_S, CYCLE_BC, dtype)
+        return OP.Hierarchy(OP.Op(n3, rng, dtype, CYCLE_S, OC.smooth_coefficient(n3, dtype)), how)
+    return OP.Hierarchy(OP.Op(n3, rng, dtype, CYCLE_S, OC.smooth_coefficient(n3, dtype), bc=CYCLE_BC))
 
 
 def _mg(ctx, op, grid, dtype, v, f):
     n3, rng, how = CYCLE_GRIDS[grid]
     mg = P.MultiGrid3D(ctx, n3, rng, dtype, residual_mode=P.CORRECT, coarsening=how, shift=CYCLE_S,
-                       coefficient=None if op == "shift" else CO.smooth_coefficient(n3, dtype), neumann=FACES if op == "neumann" else None)
+                       coefficient=None if op == "shift" else OC.smooth_coefficient(n3, dtype), neumann=FACES if op == "neumann" else None)
     mg.upload_v(0, v)
     mg.upload_f(0, f)
     return mg
@@ -394,7 +393,7 @@ def test_residual_restrict_shift_runs(ctx, n3, mask, dtype):
     v, f = _rand(n3, dtype, 13), _rand(n3, dtype, 14)
     fn, ct = _fn("residual_restrict_shift", dtype)
     for s in (0.0, 0.75):
-        want = SH.restrict_residual(n3, SH.residual(n3, rng, v, f, s, dtype), mask, dtype)
+        want = OP.restrict(n3, OP.Op(n3, rng, dtype, s).residual(v, f), 0, dtype, mask)
         _check_transfer(ctx, lambda a, b, c, keep: fn(ctx._h, a, b, _ip(n3), _h(n3, rng, dtype), ct(s), c, _ip(cn), C.c_int(keep)), dtype, n3, cn,
                         v, f, want, s)
 

@@ -2,7 +2,7 @@
 hierarchy that carries the walls (MultiGrid3D(robin=, wall_flux=), set_wall, add_wall_flux) and the solves and implicit heat steps
 on it.  DESIGN.md 18.
 
-Every kernel is checked bit for bit against the numpy restatement of its arithmetic (tests/robin_restated.py) with poisoned pads,
+Every kernel is checked bit for bit against the numpy restatement of its arithmetic (tests/op_restated.py) with poisoned pads,
 with all betas zero against the _bc entry on the same inputs too; the cycles against the restated cycle, every level, eager and
 replayed from a graph; the solves against the restated iteration counts."""
 import ctypes as C
@@ -11,14 +11,10 @@ import math
 import numpy as np
 import pytest
 
-import cap_restated as CA
-import coef_restated as CO
-import neumann_krylov_restated as NK
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-import robin_restated as RR
-import shift_restated as SH
 from conftest import bits_equal
 from odd_shapes import pads_unchanged, run_poisoned
 from pde_multigrid_amd.multigrid import _ct, _ip, _rp, grid_spacing, xs_unpack
@@ -55,7 +51,7 @@ def _coef(n3, dtype, seed=100):
 
 
 def _cap(n3, dtype, seed=200):
-    c = CA.random_capacity(n3, dtype, seed)
+    c = OC.random_capacity(n3, dtype, seed)
     c[-1, 0, :] = 0  # zeros on face unknowns too
     return c
 
@@ -75,7 +71,7 @@ def _faces(bc):
 
 def _beta_sets(bc):
     """all zero; a mixed set that leaves some flagged faces at 0 (where the mask has more than one); 1e6 on every flagged face"""
-    return [RR.ZERO, RR.mixed_betas(bc), tuple(1e6 * b for b in _faces(bc))]
+    return [OP.ZERO, OC.mixed_betas(bc), tuple(1e6 * b for b in _faces(bc))]
 
 
 def _operands(kind, n3, dtype):
@@ -128,14 +124,14 @@ def _relax_wall(ctx, n3, bc, dtype):
     """1 and 3 sweeps of every operator, every beta set and shift: the restatement's bits (all betas zero: the _bc entry's too); f,
     a, c, the Dirichlet entries of v and the pads as they were"""
     v, f = _rand(n3, dtype, 1), _rand(n3, dtype, 2)
-    dirichlet = ~NR.unknown_mask(n3, bc)
+    dirichlet = ~OP.unknown_mask(n3, bc)
     for kind in KINDS:
         a, c = _operands(kind, n3, dtype)
         ops = [x for x in (a, c) if x is not None]
         for bi, beta in enumerate(_beta_sets(bc)):
             for s in SHIFTS:
                 for sweeps in (1, 3):
-                    want = RR.relax(n3, RG, v, f, a, c, s, sweeps, bc, beta, dtype)
+                    want = OP.Op(n3, RG, dtype, s, a, c, bc, beta).relax(v, f, sweeps)
                     fn, ct = _fn(_entry("relax", kind, "wall"), dtype)
                     ups, outs = run_poisoned(ctx, [v, f] + ops, lambda x, b, *ac: fn(ctx._h, x, b, *ac, _ip(n3), _h(n3, dtype), ct(s),
                                                                                      C.c_int(sweeps), C.c_int(bc), _rp(beta, ct)), dtype)
@@ -149,11 +145,11 @@ def _relax_wall(ctx, n3, bc, dtype):
                                                                                        C.c_int(sweeps), C.c_int(bc)), dtype)
                         assert bits_equal(outb[0], outs[0]), (kind, s, sweeps)
                 if bi and not np.isinf(want).any():
-                    assert not bits_equal(want, RR.relax(n3, RG, v, f, a, c, s, 3, bc, RR.ZERO, dtype)), "the wall changed nothing"
+                    assert not bits_equal(want, OP.Op(n3, RG, dtype, s, a, c, bc).relax(v, f, 3)), "the wall changed nothing"
     # the Python wrapper, on a call of its own: the capacity operator, the mixed betas, three sweeps
     a, c = _operands("cap", n3, dtype)
-    beta = RR.mixed_betas(bc)
-    assert bits_equal(P.ops3dxs.relax_wall(ctx, v, f, a, c, n3, RG, 0.75, 3, bc, beta), RR.relax(n3, RG, v, f, a, c, 0.75, 3, bc, beta, dtype))
+    beta = OC.mixed_betas(bc)
+    assert bits_equal(P.ops3dxs.relax_wall(ctx, v, f, a, c, n3, RG, 0.75, 3, bc, beta), OP.Op(n3, RG, dtype, 0.75, a, c, bc, beta).relax(v, f, 3))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -176,8 +172,8 @@ def _residual_wall(ctx, n3, bc, dtype):
             keep = range(0, 2 + len(ops))
             for bi, beta in enumerate(_beta_sets(bc)):
                 for s in SHIFTS:
-                    want = RR.residual(n3, RG, v, f, a, c, s, bc, beta, dtype)
-                    want_ss = SH.fsum_sq(want)
+                    want = OP.Op(n3, RG, dtype, s, a, c, bc, beta).residual(v, f)
+                    want_ss = OP.fsum_sq(want)
                     fn, ct = _fn(_entry("residual", kind, "wall"), dtype)
                     tail = (C.c_int(bc), _rp(beta, ct))
                     sums = []
@@ -204,10 +200,10 @@ def _residual_wall(ctx, n3, bc, dtype):
         w.close()
     # the Python wrapper, on a call of its own: the capacity operator, the mixed betas
     a, c = _operands("cap", n3, dtype)
-    beta = RR.mixed_betas(bc)
-    want = RR.residual(n3, RG, v, f, a, c, 0.75, bc, beta, dtype)
+    beta = OC.mixed_betas(bc)
+    want = OP.Op(n3, RG, dtype, 0.75, a, c, bc, beta).residual(v, f)
     r, ss = P.ops3dxs.residual_wall(ctx, v, f, a, c, n3, RG, 0.75, bc, beta)
-    assert bits_equal(r, want) and close(ss, SH.fsum_sq(want), 1e-13)
+    assert bits_equal(r, want) and close(ss, OP.fsum_sq(want), 1e-13)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -222,8 +218,8 @@ def test_apply_dot_wall(ctx, shapes, dtype):
 def _apply_dot_wall(ctx, n3, bc, dtype):
     """q = A p at the unknowns and <p, q>_W"""
     p, q0 = _rand(n3, dtype, 8), _rand(n3, dtype, 9)
-    unk = NR.unknown_mask(n3, bc)
-    W = NR.weights(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
+    W = OP.weights(n3, bc)
     w = Work(ctx, n3, dtype)
     try:
         for kind in KINDS:
@@ -231,8 +227,8 @@ def _apply_dot_wall(ctx, n3, bc, dtype):
             ops = [x for x in (a, c) if x is not None]
             for bi, beta in enumerate(_beta_sets(bc)):
                 for s in SHIFTS:
-                    want = RR.apply_A(n3, RG, p, a, c, s, bc, beta, dtype)
-                    want_pq = NK.wdot(W, p, want)
+                    want = OP.Op(n3, RG, dtype, s, a, c, bc, beta).apply_A(p)
+                    want_pq = OP.wdot(W, p, want)
                     fn, ct = _fn(_entry("dot", kind, "wall"), dtype)
                     sums = []
                     for rep in range(2):
@@ -254,10 +250,10 @@ def _apply_dot_wall(ctx, n3, bc, dtype):
         w.close()
     # the Python wrapper, on a call of its own: the capacity operator, the mixed betas
     a, c = _operands("cap", n3, dtype)
-    beta = RR.mixed_betas(bc)
-    want = RR.apply_A(n3, RG, p, a, c, 0.75, bc, beta, dtype)
+    beta = OC.mixed_betas(bc)
+    want = OP.Op(n3, RG, dtype, 0.75, a, c, bc, beta).apply_A(p)
     q, pq = P.ops3dxs.apply_dot_wall(ctx, p, a, c, n3, RG, 0.75, bc, beta)
-    assert bits_equal(q[unk], want[unk]) and close(pq, NK.wdot(W, p, want), 1e-13)
+    assert bits_equal(q[unk], want[unk]) and close(pq, OP.wdot(W, p, want), 1e-13)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -273,18 +269,18 @@ def _wall_rhs(ctx, n3, bc, dtype):
     """f -= 2 g / h at the face unknowns of the faces with a flux, nothing else of f; all zeros: f as it was"""
     f0 = _rand(n3, dtype, 12)
     fn, ct = _fn("wall_rhs", dtype)
-    fluxes = [RR.ZERO, tuple(-x for x in RR.mixed_betas(bc)), tuple((-1) ** k * 1e6 * b for k, b in enumerate(_faces(bc)))]
+    fluxes = [OP.ZERO, tuple(-x for x in OC.mixed_betas(bc)), tuple((-1) ** k * 1e6 * b for k, b in enumerate(_faces(bc)))]
     for g in fluxes:
-        want = RR.add_flux(n3, RG, f0, g, bc, dtype)
+        want = OP.Op(n3, RG, dtype, 0.0, bc=bc).add_flux(f0, g)
         ups, outs = run_poisoned(ctx, [f0], lambda x: fn(ctx._h, x, _ip(n3), _h(n3, dtype), _rp(g, ct), C.c_int(bc)), dtype)
         got = xs_unpack(outs[0], n3[0])
         assert bits_equal(got, want), (g, np.argwhere(got != want)[:5])
         assert pads_unchanged(ups[0], outs[0], n3[0])
         changed = got != f0
-        assert (changed <= NR.face_unknowns(n3, bc)).all() and changed.any() == any(g), g
+        assert (changed <= OP.face_unknowns(n3, bc)).all() and changed.any() == any(g), g
     # the Python wrapper, on a call of its own
     g = fluxes[1]
-    assert bits_equal(P.ops3dxs.wall_rhs(ctx, f0, n3, RG, g, bc), RR.add_flux(n3, RG, f0, g, bc, dtype))
+    assert bits_equal(P.ops3dxs.wall_rhs(ctx, f0, n3, RG, g, bc), OP.Op(n3, RG, dtype, 0.0, bc=bc).add_flux(f0, g))
 
 
 # ---------------------------------------------------------------------------------------------------------- hierarchy
@@ -301,7 +297,7 @@ CLEARED = [h for h in HIER if h[3]] + [(0, 63, "shift", 0.75), (1, 63, "coef", 0
 
 def _problem(grid, kind, dtype):
     n3 = GRIDS[grid][0]
-    a = None if kind == "shift" else CO.smooth_coefficient(n3, dtype)
+    a = None if kind == "shift" else OC.smooth_coefficient(n3, dtype)
     c = _cap(n3, dtype) if kind == "cap" else None
     return _rand(n3, dtype, 1), _rand(n3, dtype, 2), a, c
 
@@ -319,7 +315,7 @@ def _mg(ctx, grid, bc, dtype, a, c, s, beta, g=None, v=None, f=None):
 
 def _restated(grid, bc, dtype, a, c, s, beta, g, v, f):
     n3, rng = GRIDS[grid]
-    H = RR.Hierarchy(n3, rng, a, c, s, bc, beta, g or RR.ZERO, dtype)
+    H = OP.Hierarchy(OP.Op(n3, rng, dtype, s, a, c, bc, beta), g=g or OP.ZERO)
     H.v[0], H.f[0] = v.copy(), f.copy()
     return H
 
@@ -343,10 +339,10 @@ def _cycles_eager_and_replayed_match_the_restated_cycle(ctx, grid, bc, kind, s, 
     """two V(2,2) eagerly, then three through use_graph (a capture and two runs, the last a replay): the restated hierarchy after
     every cycle, every level"""
     v, f, a, c = _problem(grid, kind, dtype)
-    beta = RR.mixed_betas(bc)
+    beta = OC.mixed_betas(bc)
     H = _restated(grid, bc, dtype, a, c, s, beta, None, v, f)
     mg = _mg(ctx, grid, bc, dtype, a, c, s, beta, v=v, f=f)
-    assert mg.wall == (tuple(float(_ct(dtype)[1](b).value) for b in beta), RR.ZERO)
+    assert mg.wall == (tuple(float(_ct(dtype)[1](b).value) for b in beta), OP.ZERO)
     execs = []
     for k in range(5):
         mg.use_graph = k >= 2
@@ -356,7 +352,7 @@ def _cycles_eager_and_replayed_match_the_restated_cycle(ctx, grid, bc, kind, s, 
         execs.append(mg._mg.contents.graph_exec[0])
     assert not execs[1] and execs[4] and execs[4] == execs[3], "the last cycle was captured again instead of replayed"
     r = H.residual(0)
-    assert bits_equal(mg.CalculateResidual(0), r) and close(mg.ResidualNorm(0), math.sqrt(SH.fsum_sq(r)), 1e-12)
+    assert bits_equal(mg.CalculateResidual(0), r) and close(mg.ResidualNorm(0), math.sqrt(OP.fsum_sq(r)), 1e-12)
     mg.close()
 
 
@@ -369,7 +365,7 @@ def test_fmg_with_a_flux_matches_the_restated_cycle(ctx, dtype):
 def _fmg_with_a_flux_matches_the_restated_cycle(ctx, grid, bc, kind, s, dtype):
     """add_wall_flux, then FMG(1,2,2): f of level 0 included"""
     v, f, a, c = _problem(grid, kind, dtype)
-    beta, g = RR.mixed_betas(bc), tuple((0.5 - 0.3 * k) if (bc >> k) & 1 else 0.0 for k in range(6))
+    beta, g = OC.mixed_betas(bc), tuple((0.5 - 0.3 * k) if (bc >> k) & 1 else 0.0 for k in range(6))
     H = _restated(grid, bc, dtype, a, c, s, beta, g, v, f)
     H.add_wall_flux()
     assert not bits_equal(H.f[0], f)
@@ -393,7 +389,7 @@ def _walls_set_between_cycles_and_cleared(ctx, grid, bc, kind, s, dtype):
     """through use_graph: set_wall drops the captured graph and the next cycle runs with the new betas; with zeros the hierarchy
     gives the bits of one that never had a wall"""
     v, f, a, c = _problem(grid, kind, dtype)
-    b1, b2 = RR.mixed_betas(bc), tuple(2.5 * b for b in _faces(bc))
+    b1, b2 = OC.mixed_betas(bc), tuple(2.5 * b for b in _faces(bc))
     mg = _mg(ctx, grid, bc, dtype, a, c, s, b1, v=v, f=f)
     mg.use_graph = True
     mg.VCycle(0, 2, 2)
@@ -406,7 +402,7 @@ def _walls_set_between_cycles_and_cleared(ctx, grid, bc, kind, s, dtype):
     H.vcycle(0, 2, 2)
     _same_levels(mg, H, "replaced")
     mg.set_wall(None, None)
-    assert not mg._mg.contents.wall and not mg._mg.contents.graph_exec[0] and mg.wall == (RR.ZERO, RR.ZERO)
+    assert not mg._mg.contents.wall and not mg._mg.contents.graph_exec[0] and mg.wall == (OP.ZERO, OP.ZERO)
     mg.upload_v(0, v)
     mg.VCycle(0, 2, 2)
     never = _mg(ctx, grid, bc, dtype, a, c, s, None, v=v, f=f)
@@ -436,16 +432,16 @@ def pcg_restated(case):
     n3 = PCG_N
     g = np.random.default_rng(5)
     f, v0 = g.uniform(-1, 1, O.shape(n3)), g.uniform(-1, 1, O.shape(n3))
-    a = CO.smooth_coefficient(n3) if coef else None
+    a = OC.smooth_coefficient(n3) if coef else None
     if krylov:
-        _, k, hist, conv, _ = RR.wfcg(n3, UNIT, a, None, s, bc, beta, v0, f, tol, 60)
+        _, k, hist, conv, _ = OP.fcg(OP.Op(n3, UNIT, np.float64, s, a, bc=bc, beta=beta), v0, f, tol=tol, maxit=60)[:5]
     else:
-        H = RR.Hierarchy(n3, UNIT, a, None, s, bc, beta)
+        H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, s, a, bc=bc, beta=beta))
         H.v[0], H.f[0] = v0.copy(), f.copy()
-        rr0, hist = SH.fsum_sq(H.residual(0)), []
+        rr0, hist = OP.fsum_sq(H.residual(0)), []
         while not hist or (hist[-1] >= tol and len(hist) < 60):
             H.vcycle(0, 2, 2)
-            hist.append(math.sqrt(SH.fsum_sq(H.residual(0)) / rr0))
+            hist.append(math.sqrt(OP.fsum_sq(H.residual(0)) / rr0))
         k, conv = len(hist), hist[-1] < tol
     return k, conv, list(hist), a, v0, f
 
@@ -459,7 +455,7 @@ def _pcg_matches_the_restatement(ctx, case):
     bc, s, coef, beta, krylov, tol = PCG_CASES[case]
     n3 = PCG_N
     want_k, want_c, hist, a, v0, f = pcg_restated(case)
-    assert want_c and NK.decisive(hist, tol), hist[-2:]
+    assert want_c and OC.decisive(hist, tol), hist[-2:]
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, shift=s, coefficient=a, neumann=_faces(bc), robin=beta)
     mg.upload_v(0, v0)
     mg.upload_f(0, f)
@@ -468,8 +464,8 @@ def _pcg_matches_the_restatement(ctx, case):
     assert bits_equal(mg.download_f(0), f), "d_f[0] was not restored"
     assert mg.pcg_removed_mean == 0.0 and mg._mg.contents.bc_reserved == 0
     mg.close()
-    unk = NR.unknown_mask(n3, bc)
-    res = lambda u: SH.fsum_sq(RR.residual(n3, UNIT, u, f, a, None, s, bc, beta, np.float64))
+    unk = OP.unknown_mask(n3, bc)
+    res = lambda u: OP.fsum_sq(OP.Op(n3, UNIT, np.float64, s, a, bc=bc, beta=beta).residual(u, f))
     true_rel = math.sqrt(res(x) / res(v0))
     print("PCG case %d: %d iterations (restated %d), rel %.3e, restated residual of the result %.3e" % (case, k, want_k, rel, true_rel))
     assert k == want_k and conv
@@ -486,7 +482,7 @@ def test_the_constant_state_is_the_solution(ctx):
     n3, beta = (17, 17, 17), (1.0, 0.5, 0.25, 2.0, 0.25, 4.0)
     g = tuple(7 * b for b in beta)
     zero = np.zeros(O.shape(n3))
-    for coef in (None, CO.smooth_coefficient(n3)):
+    for coef in (None, OC.smooth_coefficient(n3)):
         u, k, rel, conv = P.solve3d_pcg(ctx, zero, zero, UNIT, tol=1e-10, krylov="weighted", coefficient=coef, neumann=[1] * 6, robin=beta,
                                         wall_flux=g)
         err = float(np.abs(u - 7).max())
@@ -511,18 +507,18 @@ def _one_backward_euler_step(ctx, cap, krylov):
     """the step's right-hand side is the restated one, flux included, and u' solves (A - s c - d) u' = rhs to the tolerance"""
     n3, dt, kappa = (17, 17, 17), 1e-2, 2.0
     beta, g = (2.0, 0.0, 0.5, 0.0, 0.0, 1.0), (0.0, 1.5, 0.0, 0.0, -0.5, 1.0)
-    a, c, u0, q = CO.smooth_coefficient(n3), (CA.smooth_capacity(n3) if cap else None), NR.gaussian(n3), _rand(n3, np.float64, 3)
+    a, c, u0, q = OC.smooth_coefficient(n3), (OC.smooth_capacity(n3) if cap else None), OC.gaussian(n3), _rand(n3, np.float64, 3)
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=a, neumann=[1] * 6, capacity=c, robin=beta, wall_flux=g)
     mg.upload_v(0, u0)
     its, worst, conv = mg.BackwardEuler(1, dt, kappa, source=q, tol=1e-10, krylov=krylov)
     s = 1.0 / (kappa * dt)
     assert conv and worst < 1e-10 and mg.shift == s
-    rhs = CA.rhs(u0, c, q, 1.0 / kappa, s, np.float64, 63) if cap else NR.rhs(u0, q, 1.0 / kappa, s, 63, np.float64)
-    rhs = RR.add_flux(n3, UNIT, rhs, g, 63, np.float64)
+    rhs = OP.Op(n3, UNIT, np.float64, s, c=c, bc=63).rhs(u0, q, 1.0 / kappa) if cap else OP.Op(n3, UNIT, np.float64, s, bc=63).rhs(u0, q, 1.0 / kappa)
+    rhs = OP.Op(n3, UNIT, np.float64, 0.0, bc=63).add_flux(rhs, g)
     assert bits_equal(mg.download_f(0), rhs)
     u = mg.download_v(0)
     mg.close()
-    res = lambda x: SH.fsum_sq(RR.residual(n3, UNIT, x, rhs, a, c, s, 63, beta, np.float64))
+    res = lambda x: OP.fsum_sq(OP.Op(n3, UNIT, np.float64, s, a, c, 63, beta).residual(x, rhs))
     rel = math.sqrt(res(u) / res(u0))
     print("one step, cap=%s krylov=%s: %d iterations, rel %.3e (restated %.3e)" % (cap, krylov, its, worst, rel))
     assert rel < 1e-10 and np.abs(u - u0).max() > 1e-3
@@ -535,21 +531,21 @@ def test_heat_balance_in_a_closed_box(ctx):
 
 def _heat_balance_in_a_closed_box(ctx, krylov):
     """five steps of test_robin_cpu's closed 17^3 box with a capacity: per step the change of sum_W(c u) is kappa dt times the
-    weighted sum of the wall terms of the new u, to ten times the bound the restatement meets on the CPU (robin_restated.heat_bound)"""
-    k = RR.HEAT_CASE
+    weighted sum of the wall terms of the new u, to ten times the bound the restatement meets on the CPU (op_cases.heat_bound)"""
+    k = OC.HEAT_CASE
     n3 = k["n3"]
-    c = CA.smooth_capacity(n3)
-    mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=CO.smooth_coefficient(n3), neumann=[1] * 6, capacity=c, robin=k["beta"],
+    c = OC.smooth_capacity(n3)
+    mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, coefficient=OC.smooth_coefficient(n3), neumann=[1] * 6, capacity=c, robin=k["beta"],
                        wall_flux=k["g"])
-    us = [NR.gaussian(n3)]
+    us = [OC.gaussian(n3)]
     mg.upload_v(0, us[0])
     for _ in range(k["steps"]):
         its, worst, conv = mg.BackwardEuler(1, k["dt"], k["kappa"], tol=1e-10, krylov=krylov)
         assert conv and worst < 1e-10
         us.append(mg.download_v(0))
     mg.close()
-    worst, heat = RR.heat_balance(n3, c, us, k["beta"], k["g"], k["dt"], k["kappa"])
-    bound = 10 * RR.heat_bound(n3, CO.smooth_coefficient(n3), c, us, k["beta"], k["g"], k["dt"], k["kappa"], 1e-10)
+    worst, heat = OC.heat_balance(n3, c, us, k["beta"], k["g"], k["dt"], k["kappa"])
+    bound = 10 * OC.heat_bound(n3, OC.smooth_coefficient(n3), c, us, k["beta"], k["g"], k["dt"], k["kappa"], 1e-10)
     print("closed box, krylov=%s: worst relative imbalance of a step %.3e (bound %.1e), heat %.6e -> %.6e" % (krylov, worst, bound,
                                                                                                              heat[0], heat[-1]))
     assert abs(heat[-1] - heat[0]) > 1e-4 * abs(heat[0])
@@ -569,7 +565,7 @@ def test_refusals_leave_the_hierarchy_usable(ctx):
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, shift=0.75, neumann=_faces(bc), robin=beta)
     mg.upload_v(0, v)
     mg.upload_f(0, f)
-    H = RR.Hierarchy(n3, UNIT, None, None, 0.75, bc, beta)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.75, bc=bc, beta=beta))
     H.v[0], H.f[0] = v.copy(), f.copy()
     for call, words in [(lambda: mg.set_wall((-1, 0, 0, 0, 0, 0), None), ("beta",)),
                         (lambda: mg.set_wall((float("nan"), 0, 0, 0, 0, 0), None), ("beta",)),
@@ -581,7 +577,7 @@ def test_refusals_leave_the_hierarchy_usable(ctx):
                         (lambda: mg.PCG(2, 2, 1e-8, 5, precond="f32"), ("wall",)),
                         (lambda: mg.BackwardEuler(1, 1e-2, 1.0, krylov=True), ("krylov",))]:
         _refused(call, *words)
-        assert mg.wall == (tuple(float(b) for b in beta), RR.ZERO) and mg.neumann == tuple(bool(b) for b in _faces(bc))
+        assert mg.wall == (tuple(float(b) for b in beta), OP.ZERO) and mg.neumann == tuple(bool(b) for b in _faces(bc))
     with pytest.raises(ValueError):
         mg.set_wall((1, 2, 3), None)
     mg.VCycle(0, 2, 2)
@@ -620,7 +616,7 @@ def test_wall_data_too_large_for_the_precision_are_refused(ctx, dtype):
     mg = P.MultiGrid3D(ctx, (17, 17, 17), UNIT, dtype, residual_mode=P.CORRECT, shift=0.75, neumann=[1, 0, 0, 0, 0, 0], robin=(2, 0, 0, 0, 0, 0))
     _refused(lambda: mg.set_wall((big, 0, 0, 0, 0, 0), None), "beta", "not finite in this precision")
     _refused(lambda: mg.set_wall(None, (-big, 0, 0, 0, 0, 0)), "g[", "not finite in this precision")
-    assert mg.wall == ((2.0, 0, 0, 0, 0, 0), RR.ZERO)
+    assert mg.wall == ((2.0, 0, 0, 0, 0, 0), OP.ZERO)
     mg.set_wall((big / 64, 0, 0, 0, 0, 0), None)  # 2 beta / h with h = 1/16 on level 0 is finite, on every coarser level too
     mg.VCycle(0, 1, 1)
     assert np.isfinite(mg.download_v(0)).all()

@@ -1,7 +1,7 @@
 """GPU suite: the shifted operator (Laplacian - s) u = f (csrc/mgx_shift3d.hip), the hierarchy that cycles with it
 (MultiGrid3D(shift=s)) and the implicit heat steps built on both (MultiGrid3D.BackwardEuler).
 
-The six kernels are checked bit for bit against the numpy restatement of their arithmetic (tests/shift_restated.py), with poisoned
+The six kernels are checked bit for bit against the numpy restatement of their arithmetic (tests/op_restated.py), with poisoned
 pads; the cycles against the restated cycle, every level, bit for bit, eagerly and through captured graphs; the solver against the
 restated iteration counts; the time stepping against the discrete eigenvalue of its initial state."""
 import ctypes as C
@@ -13,7 +13,7 @@ import pytest
 import oracle as O
 import pde_multigrid_amd as P
 import semi_restated as S
-import shift_restated as SH
+import op_restated as OP
 from conftest import bits_equal
 from odd_shapes import pads_unchanged, run_poisoned
 from pde_multigrid_amd.multigrid import _ct, _ip, _rp, grid_spacing, xs_unpack
@@ -80,7 +80,7 @@ def test_relax_shift(ctx, n3, sweeps, s, dtype):
     fn, ct = _fn("relax_shift", dtype)
     ups, outs = run_poisoned(ctx, [v, f], lambda a, b: fn(ctx._h, a, b, _ip(n3), _h(n3, RG, dtype), ct(s), C.c_int(sweeps)), dtype)
     assert ctx.last_relax_kernel().startswith("relax_shift3d_xs_kernel"), ctx.last_relax_kernel()
-    want = SH.relax(n3, RG, v, f, s, sweeps, dtype)
+    want = OP.Op(n3, RG, dtype, s).relax(v, f, sweeps)
     got = xs_unpack(outs[0], n3[0])
     assert bits_equal(got, want), np.argwhere(got != want)[:5]  # the interior, and the boundary as it was
     assert pads_unchanged(ups[0], outs[0], n3[0]) and bits_equal(outs[1], ups[1])
@@ -96,7 +96,7 @@ def test_relax_shift_from_zero(ctx, n3, s, dtype):
     f[1:-1:2, 1:-1, 1:-1] = 0  # zero right-hand sides too: the signs of the zeros the first pass stores
     fn, ct = _fn("relax_shift_from_zero", dtype)
     for sweeps in (1, 2):
-        want = SH.relax(n3, RG, np.zeros_like(v), f, s, sweeps, dtype)
+        want = OP.Op(n3, RG, dtype, s).relax(np.zeros_like(v), f, sweeps)
         for rim_is_zero in (0, 1):
             v0 = v.copy()
             if rim_is_zero:  # the caller vouches for a zero boundary; the interior is stale
@@ -116,8 +116,8 @@ def test_residual_shift(ctx, n3, rg, s, dtype):
     rng = RG if rg == "aniso" else UNIT
     v, f, r0 = _rand(n3, dtype, 5), _rand(n3, dtype, 6), _rand(n3, dtype, 7)
     fn, ct = _fn("residual_shift", dtype)
-    want = SH.residual(n3, rng, v, f, s, dtype)
-    want_ss = SH.fsum_sq(want)
+    want = OP.Op(n3, rng, dtype, s).residual(v, f)
+    want_ss = OP.fsum_sq(want)
     w = Work(ctx, n3, dtype)
     try:
         sums = []
@@ -146,7 +146,7 @@ def test_laplace_dot_shift(ctx, n3, rg, s, dtype):
     p, q0 = _rand(n3, dtype, 8), _rand(n3, dtype, 9)
     fn, ct = _fn("laplace_dot_shift", dtype)
     rfn, _ = _fn("residual_shift", dtype)
-    want = SH.apply_A(n3, rng, p, s, dtype)
+    want = OP.Op(n3, rng, dtype, s).apply_A(p)
     w = Work(ctx, n3, dtype)
     try:
         sums = []
@@ -176,11 +176,11 @@ def test_shift_rhs(ctx, n3, s, dtype):
     rim = boundary_mask(n3)
     ups, outs = run_poisoned(ctx, [u, q, f0], lambda a, b, c: fn(ctx._h, a, b, ct(0.3), ct(s), c, _ip(n3)), dtype)
     got = xs_unpack(outs[2], n3[0])
-    assert bits_equal(interior(got), interior(SH.rhs(u, q, 0.3, s, dtype))) and bits_equal(got[rim], f0[rim])
+    assert bits_equal(interior(got), interior(OP.Op(n3, UNIT, dtype, s).rhs(u, q, 0.3))) and bits_equal(got[rim], f0[rim])
     assert bits_equal(outs[0], ups[0]) and bits_equal(outs[1], ups[1]) and pads_unchanged(ups[2], outs[2], n3[0])
     ups, outs = run_poisoned(ctx, [u, f0], lambda a, c: fn(ctx._h, a, None, ct(0.3), ct(s), c, _ip(n3)), dtype)
     got = xs_unpack(outs[1], n3[0])
-    assert bits_equal(interior(got), interior(SH.rhs(u, None, 0.3, s, dtype))) and bits_equal(got[rim], f0[rim])
+    assert bits_equal(interior(got), interior(OP.Op(n3, UNIT, dtype, s).rhs(u, None, 0.3))) and bits_equal(got[rim], f0[rim])
     assert bits_equal(outs[0], ups[0]) and pads_unchanged(ups[1], outs[1], n3[0])
 
 
@@ -194,7 +194,7 @@ def test_residual_restrict_shift(ctx, n3, rg, mask, s, dtype):
     cn = S.coarse_size(n3, mask)
     v, f, c0 = _rand(n3, dtype, 13), _rand(n3, dtype, 14), _rand(cn, dtype, 15)
     fn, ct = _fn("residual_restrict_shift", dtype)
-    want = SH.restrict_residual(n3, SH.residual(n3, rng, v, f, s, dtype), mask, dtype)
+    want = OP.restrict(n3, OP.Op(n3, rng, dtype, s).residual(v, f), 0, dtype, mask)
     rim = boundary_mask(cn)
     assert not want[rim].any()
     for keep in (0, 1):
@@ -245,7 +245,7 @@ def _mg(ctx, grid, dtype, s=SHIFT, v=None, f=None):
 
 def _restated(grid, dtype, s, v, f):
     n3, rng, how = GRIDS[grid]
-    H = SH.Hierarchy(n3, rng, s, dtype, how)
+    H = OP.Hierarchy(OP.Op(n3, rng, dtype, s), how)
     H.v[0], H.f[0] = v.copy(), f.copy()
     return H
 
@@ -335,11 +335,11 @@ def test_relax_residual_and_norm_through_the_hierarchy(ctx, dtype):
     v, f = _rand(n3, dtype, 7), _rand(n3, dtype, 8)
     mg = _mg(ctx, 1, dtype, v=v, f=f)
     mg.Relax(0, 3)
-    want = SH.relax(n3, rng, v, f, SHIFT, 3, dtype)
+    want = OP.Op(n3, rng, dtype, SHIFT).relax(v, f, 3)
     assert bits_equal(mg.download_v(0), want)
-    r = SH.residual(n3, rng, want, f, SHIFT, dtype)
+    r = OP.Op(n3, rng, dtype, SHIFT).residual(want, f)
     assert bits_equal(mg.CalculateResidual(0), r)
-    assert close(mg.ResidualNorm(0), math.sqrt(SH.fsum_sq(r)), 1e-12)
+    assert close(mg.ResidualNorm(0), math.sqrt(OP.fsum_sq(r)), 1e-12)
     mg.shift = 0.0  # and back on the unshifted operators
     mg.upload_v(0, v)
     mg.Relax(0, 3)
@@ -354,9 +354,9 @@ def test_pcg_matches_restatement(ctx, krylov):
     v0 = np.zeros_like(f)
     v0[boundary_mask(n3)] = _rand(n3, np.float64, 9)[boundary_mask(n3)]  # Dirichlet data
     if krylov:
-        want_x, want_k, _, want_c = SH.fcg_restated(n3, UNIT, s, v0, f, SH.m_cycle(n3, UNIT, s, 2, 2), tol, 100)
+        want_x, want_k, _, want_c = OP.fcg(OP.Op(n3, UNIT, np.float64, s), v0, f, tol=tol, maxit=100)[:4]
     else:
-        want_x, want_k, _, want_c = SH.cycles_to(n3, UNIT, s, v0, f, 2, 2, tol, 100)
+        want_x, want_k, _, want_c = OP.cycles_to(OP.Op(n3, UNIT, np.float64, s), v0, f, 2, 2, tol, 100)
     mg = P.MultiGrid3D(ctx, n3, UNIT, residual_mode=P.CORRECT, shift=s)
     mg.upload_v(0, v0)
     mg.upload_f(0, f)
@@ -364,8 +364,8 @@ def test_pcg_matches_restatement(ctx, krylov):
     x = mg.download_v(0)
     assert bits_equal(mg.download_f(0), f), "d_f[0] was not restored"
     mg.close()
-    r, r0 = SH.residual(n3, UNIT, x, f, s, np.float64), SH.residual(n3, UNIT, v0, f, s, np.float64)
-    true_rel = math.sqrt(SH.fsum_sq(r) / SH.fsum_sq(r0))
+    r, r0 = OP.Op(n3, UNIT, np.float64, s).residual(x, f), OP.Op(n3, UNIT, np.float64, s).residual(v0, f)
+    true_rel = math.sqrt(OP.fsum_sq(r) / OP.fsum_sq(r0))
     print("shifted PCG krylov=%s: %d iterations (restated %d), rel %.3e, restated residual of the result %.3e" % (krylov, k, want_k, rel, true_rel))
     assert k == want_k and conv == want_c and conv
     assert rel < tol and true_rel < tol and close(rel, true_rel, 1e-6)
@@ -454,9 +454,9 @@ def test_backward_euler_step_with_a_source(ctx):
     u = mg.download_v(0)
     rhs_dev = mg.download_f(0)
     mg.close()
-    f = SH.rhs(u0, q, 1.0 / kappa, s, np.float64)
+    f = OP.Op(n3, UNIT, np.float64, s).rhs(u0, q, 1.0 / kappa)
     assert bits_equal(interior(rhs_dev), interior(f)), "d_f[0] is not the step's right-hand side"
-    rel = math.sqrt(SH.fsum_sq(SH.residual(n3, UNIT, u, f, s, np.float64)) / SH.fsum_sq(SH.residual(n3, UNIT, u0, f, s, np.float64)))
+    rel = math.sqrt(OP.fsum_sq(OP.Op(n3, UNIT, np.float64, s).residual(u, f)) / OP.fsum_sq(OP.Op(n3, UNIT, np.float64, s).residual(u0, f)))
     print("backward Euler with a source: %d iterations, residual %.3e (restated %.3e)" % (its, worst, rel))
     assert conv and worst < tol and rel < tol
     assert bits_equal(u[boundary_mask(n3)], u0[boundary_mask(n3)]), "the Dirichlet data changed"

@@ -1,4 +1,4 @@
-"""Harmonic-mean face coefficients without a GPU: the restatement of the arithmetic (tests/hmean_restated.py) is
+"""Harmonic-mean face coefficients without a GPU: the restatement of the arithmetic (tests/op_restated.py) is
 exact for a layered medium whose interface lies midway between two node planes, where the arithmetic mean is wrong by the order
 of the flux itself; its matrix is symmetric bit for bit; with a constant power-of-two coefficient it has the bits of the
 arithmetic restatement; and the library exports the new entries, rejects NULL arguments and bad masks before it touches the
@@ -9,12 +9,10 @@ import math
 import numpy as np
 import pytest
 
-import coef_restated as CO
-import hmean_restated as HM
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-import robin_restated as RB
 from conftest import bits_equal
 from pde_multigrid_amd.multigrid import _grid3_struct
 
@@ -38,18 +36,17 @@ SLAB_MULTIPLE = 16
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("jump", [10, 1000])
 def test_the_harmonic_restatement_is_exact_for_a_layered_medium(jump, dtype):
-    n3, rng = HM.SLAB_N3, HM.SLAB_RNG
-    a, u, q = HM.slab(jump, dtype)
+    n3, rng = OC.SLAB_N3, OC.SLAB_RNG
+    a, u, q = OC.slab(jump, dtype)
     h = (rng[5] - rng[4]) / (n3[2] - 1)
     f = np.zeros(O.shape(n3), dtype)
-    r = HM.residual(n3, rng, u, f, a, 0.0, dtype)
+    r = OP.Op(n3, rng, dtype, 0.0, a, mean="harmonic").residual(u, f)
     bound = SLAB_MULTIPLE * np.finfo(dtype).eps * float(a.max()) * float(np.abs(u).max()) / h ** 2
     worst = float(np.abs(r).max())
     print("jump %g %s: harmonic residual %.3e (bound %.3e)" % (jump, np.dtype(dtype).name, worst, bound))
     assert worst <= bound, (worst, bound)
     # the arithmetic faces put the interface on node plane K: the same field leaves a residual of the order of the flux itself
-    ra = HM.residual(n3, rng, u, f, a, 0.0, dtype, mean="arithmetic")
-    assert bits_equal(ra, CO.residual(n3, rng, u, f, a, 0.0, dtype))
+    ra = OP.Op(n3, rng, dtype, 0.0, a).residual(u, f)
     flux = abs(q)  # max |a grad u|: the same in both layers
     print("jump %g %s: arithmetic residual %.3e against flux / h = %.3e" % (jump, np.dtype(dtype).name, float(np.abs(ra).max()), flux / h))
     assert float(np.abs(ra).max()) > 1e-2 * flux / h
@@ -62,17 +59,17 @@ def test_the_restated_solve_of_the_slab_is_the_analytic_profile(jump):
     iterations, 4.6e-11 for 1000 in 60 -- the cycle is a weak preconditioner across a sheet the coarse levels smear); the
     arithmetic operator's solution is off by 0.036 and 0.059 of the unit drop: the test_gpu_hmean.py slab test holds ten times
     the harmonic figures"""
-    n3, rng = HM.SLAB_N3, HM.SLAB_RNG
-    a, u, _ = HM.slab(jump)
+    n3, rng = OC.SLAB_N3, OC.SLAB_RNG
+    a, u, _ = OC.slab(jump)
     v0 = u.copy()
     v0[1:-1] = 0.0  # the Dirichlet planes z-low and z-high keep the data; every other point is an unknown
     f = np.zeros(O.shape(n3))
-    x, it, _, conv, rel = HM.fcg(n3, rng, a, 0.0, v0, f, bc=15, tol=1e-12, maxit=100)
+    x, it, _, conv, rel = OP.fcg(OP.Op(n3, rng, np.float64, 0.0, a, bc=15, mean="harmonic"), v0, f, tol=1e-12, maxit=100)[:5]
     assert conv and rel < 1e-12, (it, rel)
     err = float(np.abs(x - u).max())
     print("jump %g: harmonic CG %d iterations, error %.3e" % (jump, it, err))
     assert err < 1e-12 * jump
-    xa, _, _, conva, _ = HM.fcg(n3, rng, a, 0.0, v0, f, bc=15, tol=1e-12, maxit=100, mean="arithmetic")
+    xa, _, _, conva, _ = OP.fcg(OP.Op(n3, rng, np.float64, 0.0, a, bc=15), v0, f, tol=1e-12, maxit=100)[:5]
     assert conva and float(np.abs(xa - u).max()) > 1e-2
 
 
@@ -84,12 +81,12 @@ def _matrix(n3, rng, a, s, dtype, c, bc, beta):
     for j in range(vol):
         e = np.zeros(vol, dtype)
         e[j] = 1
-        A[:, j] = HM.apply_A(n3, rng, e.reshape(O.shape(n3)), a, s, dtype, c, bc, beta).ravel()
+        A[:, j] = OP.Op(n3, rng, dtype, s, a, c, bc, beta, "harmonic").apply_A(e.reshape(O.shape(n3))).ravel()
     return A
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-@pytest.mark.parametrize("bc,beta", [(0, RB.ZERO), (63, RB.ZERO), (0b101010, (0, 1.5, 0, 0.25, 0, 3.0))])
+@pytest.mark.parametrize("bc,beta", [(0, OP.ZERO), (63, OP.ZERO), (0b101010, (0, 1.5, 0, 0.25, 0, 3.0))])
 def test_apply_A_is_symmetric_bit_for_bit(bc, beta, dtype):
     """<x, A y> == <y, A x> through math.fsum for x = e_i, y = e_j: an entry of the matrix is one face coefficient times q*, and a
     face has the same bits seen from either node (the inner product of the mask weighs by powers of two, exactly).  For general
@@ -100,8 +97,8 @@ def test_apply_A_is_symmetric_bit_for_bit(bc, beta, dtype):
     a[1:3, 2:5, 1:4] *= dtype(1000)
     c = g.uniform(0, 2, O.shape(n3)).astype(dtype)
     A = _matrix(n3, RG, a, 3.0, dtype, c, bc, beta)
-    unk = NR.unknown_mask(n3, bc).ravel()
-    W = NR.weights(n3, bc).ravel()
+    unk = OP.unknown_mask(n3, bc).ravel()
+    W = OP.weights(n3, bc).ravel()
     WA = (W[:, None] * A.astype(np.float64))[np.ix_(unk, unk)]
     assert np.count_nonzero(WA) > 3 * unk.sum()  # (the matrix was formed)
     for i, j in zip(*np.nonzero(WA)):  # <e_i, A e_j>_W and <e_j, A e_i>_W
@@ -117,10 +114,10 @@ def test_general_vectors_agree_to_rounding():
     x, y = g.uniform(-1, 1, O.shape(n3)), g.uniform(-1, 1, O.shape(n3))
     for v in (x, y):
         v[0], v[-1], v[:, 0], v[:, -1], v[:, :, 0], v[:, :, -1] = 0, 0, 0, 0, 0, 0
-    xAy = math.fsum((x * HM.apply_A(n3, RG, y, a, 2.0, np.float64)).ravel())
-    yAx = math.fsum((y * HM.apply_A(n3, RG, x, a, 2.0, np.float64)).ravel())
+    xAy = math.fsum((x * OP.Op(n3, RG, np.float64, 2.0, a, mean="harmonic").apply_A(y)).ravel())
+    yAx = math.fsum((y * OP.Op(n3, RG, np.float64, 2.0, a, mean="harmonic").apply_A(x)).ravel())
     assert abs(xAy - yAx) <= 1e-12 * abs(xAy)
-    assert math.fsum((x * HM.apply_A(n3, RG, x, a, 2.0, np.float64)).ravel()) < 0  # negative definite
+    assert math.fsum((x * OP.Op(n3, RG, np.float64, 2.0, a, mean="harmonic").apply_A(x)).ravel()) < 0  # negative definite
 
 
 # ------------------------------------------------------------------------------------------ the bits of the arithmetic operator
@@ -134,16 +131,15 @@ def test_a_constant_power_of_two_gives_the_bits_of_the_arithmetic_restatement(k,
     a = np.full(O.shape(n3), 2.0 ** k, dtype)
     c = g.uniform(0, 2, O.shape(n3)).astype(dtype)
     v, f = g.uniform(-1, 1, O.shape(n3)).astype(dtype), g.uniform(-1, 1, O.shape(n3)).astype(dtype)
-    for cc, bc, beta in ((None, 0, RB.ZERO), (c, 0, RB.ZERO), (c, 0b010101, (2.0, 0, 0.5, 0, 0, 0))):
-        kw = dict(c=cc, bc=bc, beta=beta)
-        assert bits_equal(HM.relax(n3, RG, v, f, a, 3.0, 2, dtype, **kw), HM.relax(n3, RG, v, f, a, 3.0, 2, dtype, mean="arithmetic", **kw))
-        assert bits_equal(HM.residual(n3, RG, v, f, a, 3.0, dtype, **kw), HM.residual(n3, RG, v, f, a, 3.0, dtype, mean="arithmetic", **kw))
-        assert bits_equal(HM.apply_A(n3, RG, v, a, 3.0, dtype, **kw), HM.apply_A(n3, RG, v, a, 3.0, dtype, mean="arithmetic", **kw))
-    assert bits_equal(HM.relax(n3, RG, v, f, a, 3.0, 2, dtype, mean="arithmetic"), CO.relax(n3, RG, v, f, a, 3.0, 2, dtype))
+    for cc, bc, beta in ((None, 0, OP.ZERO), (c, 0, OP.ZERO), (c, 0b010101, (2.0, 0, 0.5, 0, 0, 0))):
+        hm, ar = (OP.Op(n3, RG, dtype, 3.0, a, cc, bc, beta, mean) for mean in ("harmonic", "arithmetic"))
+        assert bits_equal(hm.relax(v, f, 2), ar.relax(v, f, 2))
+        assert bits_equal(hm.residual(v, f), ar.residual(v, f))
+        assert bits_equal(hm.apply_A(v), ar.apply_A(v))
     outs = []
     for mean in ("harmonic", "arithmetic"):
         for coarsening in ("full", "semi"):
-            H = HM.Hierarchy(n3, RG, a, 3.0, dtype=dtype, coarsening=coarsening, mean=mean)
+            H = OP.Hierarchy(OP.Op(n3, RG, dtype, 3.0, a, mean=mean), coarsening)
             H.v[0], H.f[0] = v.copy(), f.copy()
             H.vcycle(0, 2, 2)
             H.fmg(0, 1, 1, 1)
@@ -151,20 +147,7 @@ def test_a_constant_power_of_two_gives_the_bits_of_the_arithmetic_restatement(k,
     assert bits_equal(outs[0], outs[2]) and bits_equal(outs[1], outs[3])
     a2 = a.copy()
     a2[::2] *= dtype(2)  # two powers of two: the means differ
-    assert not bits_equal(HM.residual(n3, RG, v, f, a2, 3.0, dtype), HM.residual(n3, RG, v, f, a2, 3.0, dtype, mean="arithmetic"))
-
-
-def test_the_arithmetic_mode_of_the_restated_hierarchy_is_coef_restated():
-    n3 = (17, 17, 17)
-    g = np.random.default_rng(8)
-    a = CO.jump_coefficient(n3, 1000.0)
-    v, f = g.uniform(-1, 1, O.shape(n3)), g.uniform(-1, 1, O.shape(n3))
-    H, K = HM.Hierarchy(n3, UNIT, a, 2.0, mean="arithmetic"), CO.Hierarchy(n3, UNIT, a, 2.0)
-    for X in (H, K):
-        X.v[0], X.f[0] = v.copy(), f.copy()
-        X.vcycle(0, 2, 2)
-    assert bits_equal(H.v[0], K.v[0])
-    assert CO._faces.__module__ == "coef_restated"  # the swap is undone
+    assert not bits_equal(OP.Op(n3, RG, dtype, 3.0, a2, mean="harmonic").residual(v, f), OP.Op(n3, RG, dtype, 3.0, a2).residual(v, f))
 
 
 def test_restated_cg_solves_the_jump():
@@ -172,9 +155,9 @@ def test_restated_cg_solves_the_jump():
     either mean -- the transfers do not see the coefficient; DESIGN.md 19 has the counts at 33^3)"""
     n3 = (17, 17, 17)
     g = np.random.default_rng(9)
-    a = CO.jump_coefficient(n3, 1000.0)
+    a = OC.jump_coefficient(n3, 1000.0)
     f = g.uniform(-1, 1, O.shape(n3))
-    _, it, hist, conv, rel = HM.fcg(n3, UNIT, a, 0.0, np.zeros(O.shape(n3)), f, tol=1e-10, maxit=40)
+    _, it, hist, conv, rel = OP.fcg(OP.Op(n3, UNIT, np.float64, 0.0, a, mean="harmonic"), np.zeros(O.shape(n3)), f, tol=1e-10, maxit=40)[:5]
     print("harmonic CG on the jump of 1000 at 17^3: %d iterations to %.2e" % (it, rel))
     assert conv and rel < 1e-10
 

@@ -1,5 +1,5 @@
 """Homogeneous Neumann faces without a GPU: the library exports the new entries, rejects NULL arguments and masks outside 0 .. 63
-and reports the size of the struct the Python mirror restates; the restatement of the arithmetic (tests/neumann_restated.py) is
+and reports the size of the struct the Python mirror restates; the restatement of the arithmetic (tests/op_restated.py) is
 exact where the discretisation is, symmetric under the trapezoid weights and negative definite, second order, its cycle is a solver
 and its implicit steps in a closed box keep the heat content."""
 import ctypes as C
@@ -8,12 +8,11 @@ import math
 import numpy as np
 import pytest
 
-import coef_restated as CO
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-import shift_restated as SH
-from neumann_restated import VCYCLE_CASES, gaussian, vcycle_case
+from op_cases import VCYCLE_CASES, gaussian, vcycle_case
 from pde_multigrid_amd.multigrid import _grid3_struct
 
 UNIT = [0, 1, 0, 1, 0, 1]
@@ -72,28 +71,12 @@ def test_hierarchy_mirror_has_the_library_size(sfx, ct):
 # ------------------------------------------------------------------------------------------ the restated arithmetic
 def test_unknowns_and_weights():
     n3 = (5, 7, 9)
-    assert NR.unknown_mask(n3, 0).sum() == 3 * 5 * 7 and NR.unknown_mask(n3, 63).all()
-    m = NR.unknown_mask(n3, 1)  # x-low: the open face only, its edges are Dirichlet
+    assert OP.unknown_mask(n3, 0).sum() == 3 * 5 * 7 and OP.unknown_mask(n3, 63).all()
+    m = OP.unknown_mask(n3, 1)  # x-low: the open face only, its edges are Dirichlet
     assert m[1:-1, 1:-1, 0].all() and not m[0, :, 0].any() and not m[:, 0, 0].any() and not m[:, :, -1].any()
-    w = NR.weights(n3, 63)
+    w = OP.weights(n3, 63)
     assert w[0, 0, 0] == 0.125 and w[0, 0, 3] == 0.25 and w[0, 3, 3] == 0.5 and w[4, 3, 2] == 1.0
     assert math.isclose(w.sum(), 4 * 6 * 8)  # the trapezoid rule of 1 over the box, in cells
-
-
-@pytest.mark.parametrize("dtype", [np.float32, np.float64])
-def test_mask_zero_is_the_pinned_restatement_in_bits(dtype):
-    """without a face the padded evaluation keeps the interior only: the bits of shift_restated / coef_restated and the oracle"""
-    n3, rng, s = (21, 13, 9), [-1, 1, 0, 2, 0.5, 3], 0.75
-    g = np.random.default_rng(2)
-    v, f = (g.uniform(-1, 1, O.shape(n3)).astype(dtype) for _ in range(2))
-    a = g.uniform(0.5, 2, O.shape(n3)).astype(dtype)
-    same = lambda x, y: x.dtype == y.dtype and x.tobytes() == y.tobytes()
-    assert same(NR.relax(n3, rng, v, f, None, s, 2, 0, dtype), SH.relax(n3, rng, v, f, s, 2, dtype))
-    assert same(NR.relax(n3, rng, v, f, a, s, 2, 0, dtype), CO.relax(n3, rng, v, f, a, s, 2, dtype))
-    assert same(NR.residual(n3, rng, v, f, None, s, 0, dtype), SH.residual(n3, rng, v, f, s, dtype))
-    assert same(NR.residual(n3, rng, v, f, a, s, 0, dtype), CO.residual(n3, rng, v, f, a, s, dtype))
-    assert same(NR.rhs(v, f, 0.3, s, 0, dtype), SH.rhs(v, f, 0.3, s, dtype))
-    assert same(NR.restrict(n3, v, 0, dtype), O.restrict3d(n3, v, dtype=dtype))
 
 
 @pytest.mark.parametrize("case", [1, 17])
@@ -102,15 +85,15 @@ def test_exact_for_quadratic_u_with_linear_a(case):
     x = 0, u_z = 0 at z = 0), f = 2a + 2 a y + 2 z^2.  The mirrored differences and the arithmetic-mean faces are exact for them:
     the restated residual is exactly 0.0 at every unknown."""
     n3 = (17, 17, 17)
-    x, y, z = CO._nodes(n3)
+    x, y, z = OC.nodes(n3)
     a = 1 + 2 * y
     if case == 1:
         u, f = x * x + y * z, 2 * a + 2 * z
     else:
         u, f = x * x + y * z * z, 2 * a + 2 * a * y + 2 * z * z
-    r = NR.residual(n3, UNIT, u, f, a, 0.0, case, np.float64)
-    print("exactness, bc = %d: max |residual| = %.3e over %d unknowns" % (case, np.abs(r).max(), NR.unknown_mask(n3, case).sum()))
-    assert NR.face_unknowns(n3, case).sum() > 0
+    r = OP.Op(n3, UNIT, np.float64, 0.0, a, bc=case).residual(u, f)
+    print("exactness, bc = %d: max |residual| = %.3e over %d unknowns" % (case, np.abs(r).max(), OP.unknown_mask(n3, case).sum()))
+    assert OP.face_unknowns(n3, case).sum() > 0
     assert np.abs(r).max() == 0.0
 
 
@@ -121,11 +104,11 @@ def test_weighted_operator_is_symmetric_and_negative_definite(bc, coef):
     g = np.random.default_rng(5)
     a = g.uniform(0.5, 2, O.shape(n3)) if coef else None
     p, w = g.uniform(-1, 1, O.shape(n3)), g.uniform(-1, 1, O.shape(n3))
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     p[~unk] = 0
     w[~unk] = 0
-    W = NR.weights(n3, bc)
-    Ap, Aw = NR.apply_A(n3, UNIT, p, a, s, bc, np.float64), NR.apply_A(n3, UNIT, w, a, s, bc, np.float64)
+    W = OP.weights(n3, bc)
+    Ap, Aw = OP.Op(n3, UNIT, np.float64, s, a, bc=bc).apply_A(p), OP.Op(n3, UNIT, np.float64, s, a, bc=bc).apply_A(w)
     wAp, pAw, pAp = float((W * w * Ap).sum()), float((W * p * Aw).sum()), float((W * p * Ap).sum())
     print("bc %d coef %d: <w, A p>_W = %.15e, <p, A w>_W = %.15e, <p, A p>_W = %.6e" % (bc, coef, wAp, pAw, pAp))
     assert abs(wAp - pAw) <= 1e-12 * abs(wAp)
@@ -138,9 +121,9 @@ def test_second_order_in_a_closed_box():
     s, errs = 100.0, []
     for k in (9, 17, 33):
         n3 = (k, k, k)
-        x, y, z = CO._nodes(n3)
+        x, y, z = OC.nodes(n3)
         u = np.cos(np.pi * x) * np.cos(np.pi * y) * np.cos(np.pi * z)
-        H = NR.Hierarchy(n3, UNIT, None, s, 63)
+        H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, s, bc=63))
         H.f[0] = -(3 * np.pi ** 2 + s) * u
         cycles, rel, conv = H.cycle_to(2, 2, 1e-10, 50)
         assert conv, (k, cycles, rel)
@@ -155,7 +138,7 @@ def test_restated_cycle_converges(bc, s, coef):
     """fp64 V(2,2) on 33^3 from random v and f: the weighted residual falls below 1e-9 of its start in eight cycles (measured:
     4.3e-11 to 6.2e-11 on the first three cases, 8.3e-12 and 9.8e-12 on the last two)"""
     H = vcycle_case(bc, s, coef)
-    W = NR.weights(H.sizes[0], bc)
+    W = OP.weights(H.sizes[0], bc)
     wnorm = lambda r: math.sqrt(math.fsum((W * r * r).ravel()))
     r0 = wnorm(H.residual(0))
     for _ in range(8):
@@ -170,9 +153,9 @@ def test_backward_euler_in_a_closed_box_keeps_the_heat_content(kdt):
     """17^3, bc = 63, the smooth coefficient, Gaussian initial data, five restated steps with kappa dt = kdt solved to 1e-10: the
     relative drift of sum(w u) stays below 1e-9 (measured: 4.2e-14 and 0.0)"""
     n3 = (17, 17, 17)
-    H = NR.Hierarchy(n3, UNIT, CO.smooth_coefficient(n3), 0.0, 63)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.0, OC.smooth_coefficient(n3), bc=63))
     H.v[0] = gaussian(n3)
-    W = NR.weights(n3, 63)
+    W = OP.weights(n3, 63)
     heat0 = math.fsum((W * H.v[0]).ravel())
     cycles, worst, conv = H.backward_euler(5, kdt, 1.0, 2, 2, 1e-10, 50)
     assert conv, (cycles, worst)

@@ -1,6 +1,6 @@
 """Flexible CG on hierarchies with Neumann faces without a GPU: the library exports the vector entries for all unknowns and rejects
 NULL arguments and masks outside 0 .. 63 before it uses an argument, the struct mirror keeps the library's size; the restated
-solver (tests/neumann_krylov_restated.py) takes the iteration counts of DESIGN.md 16's table, converges where plain cycling does
+solver (tests/op_restated.py) takes the iteration counts of DESIGN.md 16's table, converges where plain cycling does
 not, and solves the closed box without a shift in the projected sense, to second order."""
 import ctypes as C
 import math
@@ -8,12 +8,11 @@ import math
 import numpy as np
 import pytest
 
-import coef_restated as CO
-import neumann_krylov_restated as KR
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-from neumann_krylov_restated import CASES, EXACT_17, TOL, UNIT
+from op_cases import CASES, EXACT_17, TOL, UNIT
 from pde_multigrid_amd.multigrid import _grid3_struct, krylov_mode
 
 ENTRIES = ("laplace_dot_shift_bc", "apply_coef_dot_bc", "cg_update_bc", "dot2_bc", "cg_direction_bc", "project_bc")
@@ -85,39 +84,39 @@ def test_krylov_argument_mapping():
 # ------------------------------------------------------------------------------------------ the restated solver
 def test_sum_of_weights_is_separable():
     for n3, bc in [((5, 7, 9), 63), ((5, 7, 9), 37), ((17, 3, 5), 2), ((3, 3, 3), 0)]:
-        assert KR.sum_weights(n3, bc) == float(NR.weights(n3, bc).sum())
+        assert OP.sum_weights(n3, bc) == float(OP.weights(n3, bc).sum())
 
 
 def test_operator_is_symmetric_in_the_weighted_product_only():
     n3, bc = (9, 9, 9), 37
     g = np.random.default_rng(3)
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     p, w = (np.where(unk, g.uniform(-1, 1, O.shape(n3)), 0.0) for _ in range(2))
-    a = CO.smooth_coefficient(n3)
-    W = NR.weights(n3, bc)
-    Ap, Aw = NR.apply_A(n3, UNIT, p, a, 0.5, bc, np.float64), NR.apply_A(n3, UNIT, w, a, 0.5, bc, np.float64)
+    a = OC.smooth_coefficient(n3)
+    W = OP.weights(n3, bc)
+    Ap, Aw = OP.Op(n3, UNIT, np.float64, 0.5, a, bc=bc).apply_A(p), OP.Op(n3, UNIT, np.float64, 0.5, a, bc=bc).apply_A(w)
     scale = math.fsum(np.abs(W * w * Ap).ravel())
-    assert abs(KR.wdot(W, w, Ap) - KR.wdot(W, p, Aw)) < 1e-13 * scale
+    assert abs(OP.wdot(W, w, Ap) - OP.wdot(W, p, Aw)) < 1e-13 * scale
     assert abs(math.fsum((w * Ap).ravel()) - math.fsum((p * Aw).ravel())) > 1e-6 * scale
 
 
 @pytest.mark.parametrize("case", EXACT_17)
 def test_iteration_counts_at_17(case):
     """the counts of the table's 17^3 row for mask 62, (63, 100, jump 100), (37, 0, smooth) and the closed box without a shift with
-    no coefficient and with the smooth one: 7, 9, 7, 7, 8.  The rows of the closed box without a shift start from the zero guess (KR.table_start)."""
-    x, k, hist, conv, rel, _ = KR.solved(case, 17)
+    no coefficient and with the smooth one: 7, 9, 7, 7, 8.  The rows of the closed box without a shift start from the zero guess (op_cases.table_start)."""
+    x, k, hist, conv, rel, _ = OC.solved(case, 17)
     print("case %r: %d iterations, history end %s, true residual %.3e" % (CASES[case][:3], k, hist[-3:], rel))
     assert conv and rel < TOL and k == CASES[case][3]
 
 
 def test_jump_1000_in_the_closed_box_converges_where_plain_cycling_does_not():
     bc, s, jump = CASES[3][:3]
-    x, k, hist, conv, rel, _ = KR.solved(3, 17)
+    x, k, hist, conv, rel, _ = OC.solved(3, 17)
     print("weighted CG: %d iterations, true residual %.3e" % (k, rel))
     assert conv and rel < TOL and k <= 40
     n3 = (17, 17, 17)
-    H = NR.Hierarchy(n3, UNIT, CO.jump_coefficient(n3, jump), s, bc)
-    H.v[0], H.f[0] = KR.start(n3)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, s, OC.jump_coefficient(n3, jump), bc=bc))
+    H.v[0], H.f[0] = OC.start(n3)
     cycles, rel_plain, conv_plain = H.cycle_to(2, 2, TOL, 60)
     print("plain cycling: %d cycles, residual %.3e" % (cycles, rel_plain))
     assert not conv_plain and cycles == 60
@@ -127,13 +126,13 @@ def test_jump_1000_in_the_closed_box_converges_where_plain_cycling_does_not():
 def test_singular_solve_keeps_the_mean_of_the_guess_and_reports_the_removed_mean(case):
     """from the random guess, whose weighted mean is not zero"""
     n3 = (17, 17, 17)
-    x, k, hist, conv, rel, removed = KR.solved(case, 17, random_guess=True)
-    v0, f = KR.start(n3)
-    W = NR.weights(n3, 63)
+    x, k, hist, conv, rel, removed = OC.solved(case, 17, random_guess=True)
+    v0, f = OC.start(n3)
+    W = OP.weights(n3, 63)
     assert conv and rel < TOL
-    assert abs(KR.wmean(W, v0)) > 1e-3
-    assert abs(KR.wmean(W, x) - KR.wmean(W, v0)) <= 1e-12 * np.abs(x).max()
-    assert removed == math.fsum((W * f).ravel()) / KR.sum_weights(n3, 63)
+    assert abs(OP.wmean(W, v0)) > 1e-3
+    assert abs(OP.wmean(W, x) - OP.wmean(W, v0)) <= 1e-12 * np.abs(x).max()
+    assert removed == math.fsum((W * f).ravel()) / OP.sum_weights(n3, 63)
 
 
 def test_singular_solve_is_second_order():
@@ -142,12 +141,12 @@ def test_singular_solve_is_second_order():
     errs = []
     for size in (9, 17, 33):
         n3 = (size,) * 3
-        xx, yy, zz = CO._nodes(n3)
+        xx, yy, zz = OC.nodes(n3)
         u = np.cos(np.pi * xx) * np.cos(np.pi * yy) * np.cos(np.pi * zz)
-        x, k, hist, conv, rel, removed = KR.wfcg(n3, UNIT, None, 0.0, 63, np.zeros(O.shape(n3)), -3 * np.pi ** 2 * u)
+        x, k, hist, conv, rel, removed = OP.fcg(OP.Op(n3, UNIT, np.float64, 0.0, bc=63), np.zeros(O.shape(n3)), -3 * np.pi ** 2 * u)
         assert conv
-        W = NR.weights(n3, 63)
-        errs.append(np.abs((x - KR.wmean(W, x)) - (u - KR.wmean(W, u))).max())
+        W = OP.weights(n3, 63)
+        errs.append(np.abs((x - OP.wmean(W, x)) - (u - OP.wmean(W, u))).max())
     ratios = [errs[0] / errs[1], errs[1] / errs[2]]
     print("max errors %s, ratios %s" % (errs, ratios))
     assert all(3.5 <= r <= 4.5 for r in ratios), ratios

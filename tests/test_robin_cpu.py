@@ -1,6 +1,6 @@
 """Convective (Robin) and prescribed-flux walls without a GPU: the library exports the new entries, rejects NULL arguments and bad
 wall data before it touches the device and keeps the sizes and offsets of both struct mirrors; the restatement of the arithmetic
-(tests/robin_restated.py) has the bits of neumann_restated / cap_restated with all betas zero, is symmetric under the trapezoid
+(tests/op_restated.py) is symmetric under the trapezoid
 weights and negative definite, second-order accurate, exact on the constant state, and its cycle is a solver."""
 import ctypes as C
 import math
@@ -8,12 +8,10 @@ import math
 import numpy as np
 import pytest
 
-import cap_restated as CA
-import coef_restated as CO
-import neumann_restated as NR
+import op_cases as OC
+import op_restated as OP
 import oracle as O
 import pde_multigrid_amd as P
-import robin_restated as RR
 from pde_multigrid_amd.multigrid import _grid3_struct
 
 UNIT = [0, 1, 0, 1, 0, 1]
@@ -100,38 +98,16 @@ def test_both_mirrors_still_have_the_library_sizes(sfx, ct):
 
 
 # ------------------------------------------------------------------------------------------ the restated arithmetic
-def _same(x, y):
-    return x.dtype == y.dtype and x.tobytes() == y.tobytes()
-
-
-@pytest.mark.parametrize("dtype", [np.float32, np.float64])
-@pytest.mark.parametrize("s", [0.0, 0.75])
-def test_zero_betas_are_the_neumann_operators_in_bits(s, dtype):
-    n3 = (21, 13, 9)
-    g = np.random.default_rng(2)
-    v, f = (g.uniform(-1, 1, O.shape(n3)).astype(dtype) for _ in range(2))
-    a = g.uniform(0.5, 2, O.shape(n3)).astype(dtype)
-    c = CA.random_capacity(n3, dtype, 3)
-    for bc in (1, 37, 63) if s else (1, 37):
-        for aa in (None, a):
-            assert _same(RR.relax(n3, RG, v, f, aa, None, s, 2, bc, RR.ZERO, dtype), NR.relax(n3, RG, v, f, aa, s, 2, bc, dtype)), bc
-            assert _same(RR.residual(n3, RG, v, f, aa, None, s, bc, RR.ZERO, dtype), NR.residual(n3, RG, v, f, aa, s, bc, dtype)), bc
-            assert _same(RR.apply_A(n3, RG, v, aa, None, s, bc, RR.ZERO, dtype), NR.apply_A(n3, RG, v, aa, s, bc, dtype)), bc
-        assert _same(RR.relax(n3, RG, v, f, a, c, s, 2, bc, RR.ZERO, dtype), CA.relax(n3, RG, v, f, a, c, s, 2, dtype, bc)), bc
-        assert _same(RR.residual(n3, RG, v, f, a, c, s, bc, RR.ZERO, dtype), CA.residual(n3, RG, v, f, a, c, s, dtype, bc)), bc
-        assert _same(RR.add_flux(n3, RG, f, RR.ZERO, bc, dtype), f), bc
-
-
 def test_a_wall_changes_the_points_with_a_diagonal_and_no_others():
     """mask 37 with a beta on x-low only: the residual differs from the insulated one exactly at the unknowns of that face, by
     d u_P up to rounding"""
     n3, bc, beta = (9, 7, 5), 37, (3.0, 0, 0, 0, 0, 0)
     g = np.random.default_rng(4)
     v, f = g.uniform(-1, 1, O.shape(n3)), g.uniform(-1, 1, O.shape(n3))
-    r0 = NR.residual(n3, RG, v, f, None, 0.75, bc, np.float64)
-    r1 = RR.residual(n3, RG, v, f, None, None, 0.75, bc, beta, np.float64)
-    d = RR.diagonal(n3, RG, beta, bc, np.float64)
-    unk = NR.unknown_mask(n3, bc)
+    r0 = OP.Op(n3, RG, np.float64, 0.75, bc=bc).residual(v, f)
+    r1 = OP.Op(n3, RG, np.float64, 0.75, bc=bc, beta=beta).residual(v, f)
+    d = OP.Op(n3, RG, np.float64, 0.0, bc=bc, beta=beta).diagonal()
+    unk = OP.unknown_mask(n3, bc)
     assert ((r0 != r1) <= ((d != 0) & unk)).all() and (r0 != r1).sum() > 0
     assert d[:, :, 0].min() == 2 * 3.0 / (2.0 / 8) and (d[:, :, 1:] == 0).all()
     assert np.abs((r1 - r0)[unk] - (d * v)[unk]).max() < 1e-12 * 30
@@ -142,20 +118,20 @@ def test_a_wall_changes_the_points_with_a_diagonal_and_no_others():
 def test_weighted_operator_is_symmetric_and_negative_definite(bc, s, beta, cap):
     n3 = (9, 9, 9)
     g = np.random.default_rng(5)
-    a = CO.smooth_coefficient(n3)
-    c = CA.random_capacity(n3, np.float64, 6) if cap else None
+    a = OC.smooth_coefficient(n3)
+    c = OC.random_capacity(n3, np.float64, 6) if cap else None
     p, w = g.uniform(-1, 1, O.shape(n3)), g.uniform(-1, 1, O.shape(n3))
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     p[~unk] = 0
     w[~unk] = 0
-    W = NR.weights(n3, bc)
-    Ap, Aw = (RR.apply_A(n3, UNIT, x, a, c, s, bc, beta, np.float64) for x in (p, w))
+    W = OP.weights(n3, bc)
+    Ap, Aw = (OP.Op(n3, UNIT, np.float64, s, a, c, bc, beta).apply_A(x) for x in (p, w))
     wAp, pAw, pAp = float((W * w * Ap).sum()), float((W * p * Aw).sum()), float((W * p * Ap).sum())
     print("bc %d: <w, A p>_W = %.15e, <p, A w>_W = %.15e, <p, A p>_W = %.6e" % (bc, wAp, pAw, pAp))
     assert abs(wAp - pAw) <= 1e-12 * abs(wAp)
     assert pAp < 0
     one = unk.astype(np.float64)  # the constant is no null vector any more: a wall loses heat
-    assert float((W * one * RR.apply_A(n3, UNIT, one, a, c, s, bc, beta, np.float64)).sum()) < 0
+    assert float((W * one * OP.Op(n3, UNIT, np.float64, s, a, c, bc, beta).apply_A(one)).sum()) < 0
 
 
 def _accuracy_case(n):
@@ -163,13 +139,13 @@ def _accuracy_case(n):
     along each face and is folded into f with the documented formula, f -= 2 g(P) / h.  Returns the maximum error of the
     solution of the discrete system at the unknowns."""
     n3, s, bc, beta = (n,) * 3, 2.0, 62, (0, 2, 0.5, 0, 3, 1)
-    x, y, z = CO._nodes(n3)
+    x, y, z = OC.nodes(n3)
     e = np.exp(x + y / 2)
     u, a = e * np.cos(z), 1 + x / 2 + y * z / 4
     grad = (u, u / 2, -e * np.sin(z))
     f = a * (u + u / 4 - u) + 0.5 * grad[0] + (z / 4) * grad[1] + (y / 4) * grad[2] - s * u
     h = 1.0 / (n - 1)
-    unk = NR.unknown_mask(n3, bc)
+    unk = OP.unknown_mask(n3, bc)
     for k in range(6):
         if not (bc >> k) & 1:
             continue
@@ -179,7 +155,7 @@ def _accuracy_case(n):
         idx = tuple(idx)
         gP = (1 if high else -1) * a[idx] * grad[axis][idx] + beta[k] * u[idx]
         f[idx] = np.where(unk[idx], f[idx] - 2 * gP / h, f[idx])
-    H = RR.Hierarchy(n3, UNIT, a, None, s, bc, beta)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, s, a, bc=bc, beta=beta))
     H.v[0] = np.where(unk, 0.0, u)
     H.f[0] = f
     cycles, rel, conv = H.cycle_to(2, 2, 1e-11, 40)
@@ -194,42 +170,28 @@ def test_second_order():
     assert 3.5 <= err[0] / err[1] <= 4.5 and 3.5 <= err[1] / err[2] <= 4.5, err
 
 
-@pytest.mark.parametrize("bc,s,coef", [(37, 0.0, True), (63, 0.75, False)])
-def test_the_weighted_cg_is_neumann_krylov_restated_s_with_zero_betas(bc, s, coef):
-    """robin_restated writes the flexible CG loop out (neumann_krylov_restated.wfcg takes no cycle): with all betas zero on a regular
-    system the two give the same iterate, count and history, bit for bit"""
-    import neumann_krylov_restated as NK
-    n3 = (17, 17, 17)
-    a = CO.smooth_coefficient(n3) if coef else None
-    v0, f = NK.start(n3)
-    x1, k1, h1, c1, rel1 = RR._wfcg(n3, UNIT, a, None, s, bc, RR.ZERO, v0, f, 1e-10, 60, 2, 2, np.float64)
-    x2, k2, h2, c2, rel2, removed = NK.wfcg(n3, UNIT, a, s, bc, v0, f, tol=1e-10, maxit=60)
-    assert c1 and c2 and k1 == k2 and removed == 0.0
-    assert _same(x1, x2) and _same(np.asarray(h1), np.asarray(h2)) and rel1 == rel2
-
-
 @pytest.mark.parametrize("coef", [False, True])
 def test_the_constant_state_has_a_residual_of_exactly_zero(coef):
     """mask 63, s = 0, f = 0, g_k = beta_k * 7: u = 7 balances every wall, and the residual is exactly 0 (the betas are dyadic and
     the spacings powers of two, so that 2 (7 beta) / h and 7 (2 beta / h) are the same number)"""
     n3, beta = (17, 9, 5), (1.0, 0.5, 0.0, 2.0, 0.25, 4.0)
     g = tuple(b * 7 for b in beta)
-    H = RR.Hierarchy(n3, UNIT, CO.smooth_coefficient(n3) if coef else None, None, 0.0, 63, beta, g)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, 0.0, OC.smooth_coefficient(n3) if coef else None, bc=63, beta=beta), g=g)
     H.v[0][:] = 7.0
     H.add_wall_flux()
     r = H.residual(0)
     assert (H.f[0] != 0).any() and not r.any(), np.abs(r).max()
 
 
-@pytest.mark.parametrize("case", range(len(RR.VCYCLE_CASES)))
+@pytest.mark.parametrize("case", range(len(OC.WALL_VCYCLE_CASES)))
 def test_restated_vcycle_converges_within_the_recorded_count(case):
     """V(2,2) from a random start at 33^3: below 1e-9 of the initial residual within the count recorded in DESIGN.md 18 (to 1e-10)
     plus two"""
-    recorded = RR.VCYCLE_CASES[case][4]
-    H = RR.vcycle_case(case)
+    recorded = OC.WALL_VCYCLE_CASES[case][4]
+    H = OC.vcycle_case(*OC.WALL_VCYCLE_CASES[case][:4])
     cycles, rel, conv = H.cycle_to(2, 2, 1e-10, 40)
-    print("case %d %r: %d cycles to 1e-10 (relative residual %.3e)" % (case, RR.VCYCLE_CASES[case][:4], cycles, rel))
-    H = RR.vcycle_case(case)
+    print("case %d %r: %d cycles to 1e-10 (relative residual %.3e)" % (case, OC.WALL_VCYCLE_CASES[case][:4], cycles, rel))
+    H = OC.vcycle_case(*OC.WALL_VCYCLE_CASES[case][:4])
     k9, rel9, conv9 = H.cycle_to(2, 2, 1e-9, recorded + 2)
     assert conv and cycles == recorded, (cycles, recorded)
     assert conv9 and k9 <= recorded + 2, (k9, rel9)
@@ -238,6 +200,6 @@ def test_restated_vcycle_converges_within_the_recorded_count(case):
 def test_restated_heat_balance_in_a_closed_box():
     """five backward Euler steps in a closed 17^3 box with a capacity and walls that lose and feed heat: per step
     sum_W(c u') - sum_W(c u) = kappa dt sum_W(2 (g - beta u') / h), up to the solves' tolerance"""
-    worst, _, bound = RR.heat_balance_restated()
+    worst, _, bound = OC.heat_balance_restated()
     print("worst relative imbalance of a step %.3e (bound %.3e)" % (worst, bound))
     assert worst <= bound

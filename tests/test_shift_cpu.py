@@ -1,4 +1,4 @@
-"""The shifted operator (Laplacian - s) u = f without a GPU: the restatement of its arithmetic (tests/shift_restated.py) is
+"""The shifted operator (Laplacian - s) u = f without a GPU: the restatement of its arithmetic (tests/op_restated.py) is
 anchored to the oracle at s = 0, the restated cycle is a solver for every shift, and the library exports the new entries,
 rejects NULL arguments and reports the size of the struct the Python mirror restates."""
 import ctypes as C
@@ -9,7 +9,7 @@ import pytest
 
 import oracle as O
 import pde_multigrid_amd as P
-import shift_restated as SH
+import op_restated as OP
 from conftest import bits_equal
 from pde_multigrid_amd.multigrid import _grid3_struct
 from solve_restated import problem
@@ -24,9 +24,9 @@ KERNELS = ("relax_shift", "relax_shift_from_zero", "residual_shift", "residual_r
 def test_restatement_at_zero_shift_is_the_oracle(n3, rng, dtype):
     r = np.random.default_rng(3)
     v, f = r.uniform(-1, 1, O.shape(n3)).astype(dtype), r.uniform(-1, 1, O.shape(n3)).astype(dtype)
-    assert bits_equal(SH.relax(n3, rng, v, f, 0.0, 2, dtype), O.relax3d(n3, rng, v, f, 2, dtype=dtype))
+    assert bits_equal(OP.Op(n3, rng, dtype, 0.0).relax(v, f, 2), O.relax3d(n3, rng, v, f, 2, dtype=dtype))
     # the residual's values: r + 0*c may turn a -0.0 into +0.0, nothing else
-    assert np.array_equal(SH.residual(n3, rng, v, f, 0.0, dtype), O.residual3d(n3, rng, v, f, O.CORRECT, dtype=dtype))
+    assert np.array_equal(OP.Op(n3, rng, dtype, 0.0).residual(v, f), O.residual3d(n3, rng, v, f, O.CORRECT, dtype=dtype))
 
 
 @pytest.mark.parametrize("s", [0.0, 1.0, 100.0, 1e4])
@@ -34,12 +34,12 @@ def test_restated_cycle_converges(s):
     """fp64 V(2,2) on 33^3, unit cube, random interior f: relative residual below 1e-8 after 8 cycles (measured with this
     restatement: 8.2e-10, 7.7e-10, 6.8e-11, 1e-16; the bound is the issue's)"""
     n3 = (33, 33, 33)
-    H = SH.Hierarchy(n3, UNIT, s)
+    H = OP.Hierarchy(OP.Op(n3, UNIT, np.float64, s))
     H.f[0] = problem(n3)
-    r0 = math.sqrt(SH.fsum_sq(H.residual(0)))
+    r0 = math.sqrt(OP.fsum_sq(H.residual(0)))
     for _ in range(8):
         H.vcycle(0, 2, 2)
-    rel = math.sqrt(SH.fsum_sq(H.residual(0))) / r0
+    rel = math.sqrt(OP.fsum_sq(H.residual(0))) / r0
     print("shift %g: relative residual %.3e after 8 V(2,2)" % (s, rel))
     assert rel < 1e-8, rel
 
@@ -50,8 +50,8 @@ def test_operator_is_minus_residual_and_rhs():
     p, q = r.uniform(-1, 1, O.shape(n3)), r.uniform(-1, 1, O.shape(n3))
     lap = -O.residual3d(n3, RG, p, np.zeros_like(p), O.CORRECT, dtype=np.float64)
     want = lap[1:-1, 1:-1, 1:-1] - 0.75 * p[1:-1, 1:-1, 1:-1]
-    assert np.allclose(SH.apply_A(n3, RG, p, 0.75, np.float64)[1:-1, 1:-1, 1:-1], want, rtol=1e-13, atol=1e-13)
-    f = SH.rhs(p, q, 0.5, 3.0, np.float64)
+    assert np.allclose(OP.Op(n3, RG, np.float64, 0.75).apply_A(p)[1:-1, 1:-1, 1:-1], want, rtol=1e-13, atol=1e-13)
+    f = OP.Op(n3, RG, np.float64, 3.0).rhs(p, q, 0.5)
     assert np.array_equal(f[1:-1, 1:-1, 1:-1], -(3.0 * p[1:-1, 1:-1, 1:-1]) - 0.5 * q[1:-1, 1:-1, 1:-1]) and not f[0].any()
 
 
