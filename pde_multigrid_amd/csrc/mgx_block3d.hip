@@ -30,6 +30,13 @@
 // iteration, double-buffered.  Loads requested at the top of an iteration are waited for behind its barrier; the stores of the
 // previous iteration's results go out at the top too.
 //
+// A run is head, steady state and tail.  The general iteration clamps every plane it addresses into the array, derives the range
+// predicates of its stores and selects from t and builds its descriptors from scratch; it runs the iterations before the first
+// store and those within three planes (CORR: six) of the far z-face.  In between, where none of that can bite, the steady iteration
+// runs in pairs: the bases of the planes of vin, f, vout and coarse are kept as 64-bit scalars and advanced by the plane pitch, the
+// range predicates are literals, and the lane masks of stores and selects, which do not depend on t, are formed once before the
+// loop.  A third of the general iteration's scalar instructions, the same vector instructions.
+//
 // CORR (way up, in place, COL = 0, red stored only): the launch stands for R', B, R -- the first red pass reads black THROUGH
 // the coarse-grid correction, as relax3d_xs_pipe_kernel<.., VAR = 2> does.  Every black value that arrives gets
 // e = Interpolate(coarse)(x, y, z) added if it is an interior point of the grid, once, before it is published to sY; stages 2
@@ -85,6 +92,17 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
         yin[o] = y >= 1 && y <= sy - 2;
         outrow[o] = 2 * w + o >= 3 && 2 * w + o < ROWS - 3;
     }
+    // none of these depends on the plane: the lanes that store row o's entry of half h, the lanes whose entry there is an
+    // interior point in x and y, the lanes whose even X entry is v on an x-face -- formed once, reused by every iteration
+    bool stm[2][2], sel[2][2];
+#pragma unroll
+    for (int o = 0; o < 2; o++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            sel[o][h] = yin[o] && xin(h);
+            stm[o][h] = outlane && outrow[o] && sel[o][h];
+        }
+    const bool xfm = wxface && xface0;
     const int wU = w > 0 ? w - 1 : 0, wD = w < TW - 1 ? w + 1 : TW - 1;
     auto zc = [&](int z) { return min(max(z, 0), sz - 1); };
     auto plane = [&](const real* a, int z) { return plane_rsrc<real>(a + (ptrdiff_t)zc(z) * (ptrdiff_t)g.PL, PL, 1); };
@@ -190,28 +208,45 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
         return relax3d_point<real>(O, E, N, S, D, U, fv, hx2, hy2, hz2);
     };
 
-    auto iteration = [&](auto parity, int t) __attribute__((always_inline)) {
+    // the planes an iteration t addresses, as base pointers: vout at t - 3 and t - 2, vin at t + 2 and t + 1, f at t + 1 and t,
+    // the coarse plane t / 2 + 3 (CORR, even t)
+    struct Streams {
+        real *o3, *o2;
+        const real *y, *xv, *fx, *fy, *kc;
+    };
+    auto streams_at = [&](int t) {  // any iteration: every plane clamped into its array
+        const ptrdiff_t pl = (ptrdiff_t)g.PL;
+        return Streams{vout + (ptrdiff_t)zc(t - 3) * pl, vout + (ptrdiff_t)zc(t - 2) * pl, vin + (ptrdiff_t)zc(t + 2) * pl,
+                       vin + (ptrdiff_t)zc(t + 1) * pl, f + (ptrdiff_t)zc(t + 1) * pl, f + (ptrdiff_t)zc(t) * pl,
+                       CORR ? coarse + (ptrdiff_t)min(max((t >> 1) + 3, 0), cz - 1) * (ptrdiff_t)gc.PL : nullptr};
+    };
+    auto rsrc = [&](const real* a) { return plane_rsrc<real>(a, PL, 1); };
+
+    // STEADY: the caller guarantees z0 + 3 <= t <= min(tlast, sz - 3) (CORR: sz - 6) -- every store is in its run, no plane of the iteration
+    // is a z-face or clamped, and S holds the planes' bases as the caller advanced them: no range logic, no address arithmetic
+    auto iteration = [&](auto parity, auto steady, int t, const Streams& S) __attribute__((always_inline)) {
         constexpr int PAR = decltype(parity)::value;  // t & 1
         constexpr int PB = PAR ^ 1;                  // LDS buffer written by the previous iteration
+        constexpr bool STEADY = decltype(steady)::value;
         // ---- stores of the previous iteration's results: X of plane t - 3, Y of plane t - 2 (both in half hx ^ 1)
-        const auto ro3 = plane(vout, t - 3), ro2 = plane(vout, t - 2);
+        const auto ro3 = rsrc(S.o3), ro2 = rsrc(S.o2);
         // ---- requests: Y of plane t + 2, f (v on a face) of X at t + 1, f of Y at t
-        const auto rY = plane(vin, t + 2), rXv = plane(vin, t + 1), rFx = plane(f, t + 1), rFy = plane(f, t);
-        const bool zf = t + 1 <= 0 || t + 1 >= sz - 1;
+        const auto rY = rsrc(S.y), rXv = rsrc(S.xv), rFy = rsrc(S.fy);
+        const bool zf = STEADY ? false : t + 1 <= 0 || t + 1 >= sz - 1;
+        const bool st3 = STEADY ? true : t - 3 >= z0 && t - 3 < z1, st2 = STEADY ? true : t - 2 >= z0 && t - 2 < z1;
         __builtin_amdgcn_s_setprio(3);
 #pragma unroll
         for (int o = 0; o < 2; o++) {
             const int hx = (COL + 1 + o + PAR) & 1;  // X half of row o at plane t (compile-time)
-            const bool sto = outlane && yin[o] && outrow[o];
-            if (t - 3 >= z0 && t - 3 < z1 && sto && xin(hx ^ 1)) buf_store_nt<real>(x3[o], ro3, off(hx ^ 1), roff[o]);
-            if (STORE_BOTH && t - 2 >= z0 && t - 2 < z1 && sto && xin(hx ^ 1)) buf_store_nt<real>(d_m[o], ro2, off(hx ^ 1), roff[o]);
+            if (st3 && stm[o][hx ^ 1]) buf_store_nt<real>(x3[o], ro3, off(hx ^ 1), roff[o]);
+            if (STORE_BOTH && st2 && stm[o][hx ^ 1]) buf_store_nt<real>(d_m[o], ro2, off(hx ^ 1), roff[o]);
             a_n[o] = buf_load<real>(rY, off(hx ^ 1), roff[o]);
-            fx_n[o] = buf_load<real>(zf || !yin[o] ? rXv : rFx, off(hx ^ 1), roff[o]);
+            fx_n[o] = buf_load<real>(rsrc(zf || !yin[o] ? S.xv : S.fx), off(hx ^ 1), roff[o]);
             if ((hx ^ 1) == 0 && wxface) xv_n[o] = buf_load<real>(rXv, off(0), roff[o]);
             fy_n[o] = buf_load<real>(rFy, off(hx ^ 1), roff[o]);
         }
         if constexpr (CORR && PAR == 0) {  // coarse plane K + 2 = t / 2 + 3: the last requests, still on their way at the iteration's end
-            const auto qnc = cplane((t >> 1) + 3);
+            const auto qnc = plane_rsrc<real>(S.kc, (int)gc.PL, 1);
             __builtin_amdgcn_sched_barrier(0);  // (the scheduler would move them up in front of the others)
 #pragma unroll
             for (int i = 0; i < 2; i++) c_n[i] = buf_load<real>(qnc, coff, croff[i]);
@@ -219,7 +254,7 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
         }
         __builtin_amdgcn_s_setprio(0);
         // ---- stage 1: X at plane t (half hx) from the loaded Y
-        const bool zin1 = t >= 1 && t <= sz - 2, zin2 = t - 1 >= 1 && t - 1 <= sz - 2;
+        const bool zin1 = STEADY ? true : t >= 1 && t <= sz - 2, zin2 = STEADY ? true : t - 1 >= 1 && t - 1 <= sz - 2;
         {
             const real nb = sY[PB][wU][1][lane], sb = sY[PB][wD][0][lane];
 #pragma unroll
@@ -228,7 +263,7 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
                                     ? relax(std::integral_constant<int, 0>{}, o, a_c, nb, sb, a_m[o], a_p[o], fx_c[o])
                                     : relax(std::integral_constant<int, 1>{}, o, a_c, nb, sb, a_m[o], a_p[o], fx_c[o]);
                 const int hx = (COL + 1 + o + PAR) & 1;
-                b_c[o] = zin1 && yin[o] && xin(hx) ? v1 : fx_c[o];
+                b_c[o] = zin1 && sel[o][hx] ? v1 : fx_c[o];
             }
         }
         // ---- stage 2: Y at plane t - 1 (half hx) from the stage-1 X
@@ -240,7 +275,7 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
                                     ? relax(std::integral_constant<int, 0>{}, o, b_m, nb, sb, b_mm[o], b_c[o], fy_c[o])
                                     : relax(std::integral_constant<int, 1>{}, o, b_m, nb, sb, b_mm[o], b_c[o], fy_c[o]);
                 const int hx = (COL + 1 + o + PAR) & 1;
-                d_c[o] = zin2 && yin[o] && xin(hx) ? v2 : a_m[o];
+                d_c[o] = zin2 && sel[o][hx] ? v2 : a_m[o];
             }
         }
         // ---- stage 3: X at plane t - 2 (half hx) from the stage-2 Y; stored in the next iteration
@@ -251,6 +286,9 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
                 x3[o] = (((COL + 1 + PAR) & 1) ^ o) == 0
                             ? relax(std::integral_constant<int, 0>{}, o, d_m, nb, sb, d_mm[o], d_c[o], fx_2[o])
                             : relax(std::integral_constant<int, 1>{}, o, d_m, nb, sb, d_mm[o], d_c[o], fx_2[o]);
+                // formed here: with a store mask that no longer depends on t the compiler would sink the whole stage into the next
+                // iteration's store, between its s_setprio(3) and its requests
+                asm volatile("" : "+v"(x3[o]));
             }
         }
         // ---- CORR: the correction of the Y of plane t + 2, formed while that Y is on its way
@@ -268,27 +306,56 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if constexpr (CORR && PAR == 0) __builtin_amdgcn_s_waitcnt(0x0F72);  // vmcnt(2): all but the two coarse requests
         else __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this iteration's requests have had the whole iteration
-        const bool zin3 = t + 2 >= 1 && t + 2 <= sz - 2;
+        const bool zin3 = STEADY ? true : t + 2 >= 1 && t + 2 <= sz - 2;
 #pragma unroll
         for (int o = 0; o < 2; o++) {
             a_m[o] = a_c[o]; a_c[o] = a_p[o];
-            a_p[o] = CORR && zin3 && yin[o] && xin((COL + o + PAR) & 1) ? a_n[o] + e_n[o] : a_n[o];
+            a_p[o] = CORR && zin3 && sel[o][(COL + o + PAR) & 1] ? a_n[o] + e_n[o] : a_n[o];
             if constexpr (CORR && PAR == 1) { c_0[o] = c_1[o]; c_1[o] = c_n[o]; }
             fx_2[o] = fx_1[o]; fx_1[o] = fx_c[o];
-            fx_c[o] = ((COL + 1 + o + PAR) & 1) == 1 && wxface && xface0 ? xv_n[o] : fx_n[o];  // x-face lanes: v of the even X entry
+            fx_c[o] = ((COL + 1 + o + PAR) & 1) == 1 && xfm ? xv_n[o] : fx_n[o];  // x-face lanes: v of the even X entry
             fy_c[o] = fy_n[o];
             b_mm[o] = b_m[o]; b_m[o] = b_c[o];
             d_mm[o] = d_m[o]; d_m[o] = d_c[o];
         }
     };
 
+    // head (the iterations before the first store, up to an even t), steady state (pairs of iterations with the planes'
+    // bases advanced by the plane pitch), tail (from three planes -- CORR: six -- before the far z-face, or the odd last one).
+    // The general iteration exists once per parity and serves head and tail; the steady one once per parity.
+    const int ts0 = (z0 + 4) & ~1, ts1 = min(tlast, sz - (CORR ? 6 : 3));  // steady: ts0 <= t <= ts1, begun at an even t
+    constexpr std::integral_constant<int, 0> even{};
+    constexpr std::integral_constant<int, 1> odd{};
     int t = t0;
-    if (t & 1) iteration(std::integral_constant<int, 1>{}, t++);
-    for (;; t += 2) {
-        iteration(std::integral_constant<int, 0>{}, t);
-        if (t == tlast) break;
-        iteration(std::integral_constant<int, 1>{}, t + 1);
-        if (t + 1 == tlast) break;
+#pragma nounroll
+    for (int phase = 0;; phase++) {
+        const int gend = phase == 0 ? min(ts0, tlast + 1) : tlast + 1;
+#pragma nounroll
+        for (; t < gend; t++) {
+            if (t & 1) iteration(odd, std::false_type{}, t, streams_at(t));
+            else iteration(even, std::false_type{}, t, streams_at(t));
+        }
+        if (phase == 1 || t > tlast) break;
+        if (t + 1 <= ts1) {
+            const ptrdiff_t pl = (ptrdiff_t)g.PL;
+            real* pO = vout + (ptrdiff_t)(t - 3) * pl;                                            // vout at t - 3
+            const real *pYm = vin + (ptrdiff_t)(t + 1) * pl, *pY = pYm + pl;                      // vin at t + 1, t + 2
+            const real *pFm = f + (ptrdiff_t)t * pl, *pF = pFm + pl;                              // f at t, t + 1
+            const real* pK = CORR ? coarse + (ptrdiff_t)((t >> 1) + 3) * (ptrdiff_t)gc.PL : nullptr;  // coarse at t / 2 + 3
+#pragma nounroll
+            for (; t + 1 <= ts1; t += 2) {
+                real* const pO1 = pO + pl;
+                real* const pO2 = pO1 + pl;
+                const real* const pYn = pY + pl;
+                const real* const pFn = pF + pl;
+                iteration(even, std::true_type{}, t, Streams{pO, pO1, pY, pYm, pF, pFm, pK});
+                iteration(odd, std::true_type{}, t + 1, Streams{pO1, pO2, pYn, pY, pFn, pF, pK});
+                pO = pO2;
+                pYm = pYn; pY = pYn + pl;
+                pFm = pFn; pF = pFn + pl;
+                if constexpr (CORR) pK += (ptrdiff_t)gc.PL;
+            }
+        }
     }
     // ---- the last X: plane z1 - 1 = tlast - 2
     {
@@ -296,7 +363,7 @@ __global__ void __launch_bounds__(64 * TW, 4)  // four waves per SIMD: 128 VGPRs
 #pragma unroll
         for (int o = 0; o < 2; o++) {
             const int hx = (COL + 1 + o + tlast) & 1;
-            if (outlane && yin[o] && outrow[o] && xin(hx)) buf_store_nt<real>(x3[o], ro3, off(hx), roff[o]);
+            if (stm[o][hx]) buf_store_nt<real>(x3[o], ro3, off(hx), roff[o]);
         }
     }
 }
