@@ -605,6 +605,48 @@ int mgMultiGrid3D_f64_PCG_mixed(mgMultiGrid3D_f64* mg, int v1, int v2, double to
 int mg3d_solve_pcg_mixed_f64(mgx_ctx* ctx, double* grid, const double* rhs, const int sizeXYZ[3], const double range[6], int nlevels,
                              int v1, int v2, double tol, int maxit, int krylov, int* iters, double* rel_res, int* converged);
 
+/* Eigen (an addition): the k smallest eigenvalues lambda_i and eigenvectors x_i of the hierarchy's operator,
+ *     -(div(a grad x_i)) [+ the wall diagonal of set_wall]  =  lambda_i c x_i      on the unknowns of the mask
+ * (a = 1, c = 1 where the hierarchy has none; the wall flux g is right-hand-side data and plays no part), by LOBPCG (Knyazev 2001)
+ * with block size k, 1 <= k <= MG_EIGEN_MAX_BLOCK, preconditioned by one VCycle(0, v1, v2) from zero per residual (captured and
+ * replayed with use_graph, the bits of the eager run).  It works in the inner product <u, v>_W = sum of W u v over the unknowns
+ * (W = 1/2 per wall an unknown lies on), in which -A_s = -(div(a grad .) - s c) is symmetric positive definite.  The hierarchy's
+ * shift s is a spectral shift only: the solver finds -A_s x = mu c x and returns lambda = mu - s, so the closed insulated box,
+ * whose lambda_1 is 0, is solved with any s > 0.  Everything the operator refuses stays refused with its message (all six faces
+ * walls with s = 0 and no lossy wall, Jacobi, ...), as do the natural layout and REF_COMPAT (MGX_ERR_INVALID); so are NULL
+ * arguments, k outside its range, tol <= 0 and maxit < 1, before anything is touched.
+ *   The basis of an iteration is [X, T, P]: T_i = M r_i the preconditioned residuals, P the T and P part of the previous Ritz
+ * combination (none in the first iteration).  The Rayleigh-Ritz problem (at most 24 x 24) is solved on the host by
+ * mg_sym_geneig, which scales every basis vector to unit c W norm; where its Cholesky factorization meets a non-positive pivot the
+ * iteration is repeated without P, and if that fails too the call returns MGX_OK with *converged = 0 and the last good iterate.
+ * A X and A P are carried along by the combination of X and P; only A T is applied: k operator applications per iteration.
+ *   Stopping: res_i = ||A_s x_i + mu_i c x_i||_W / (mu_i ||x_i||_W) < tol for all i, confirmed on a freshly applied A X after a
+ * Rayleigh-Ritz step on X alone (which also makes <x_i, c x_j>_W = delta_ij to rounding); if the confirmation fails the iteration
+ * goes on from there.  The same confirmation runs before a return at maxit, so lambda, res and the vectors always belong together.
+ *   lambda, res: k doubles each (ascending lambda); *iters: iterations done (each k V-cycles and k operator applications);
+ * host_vectors: NULL or k * vol doubles, vector i at i * vol in the reference layout, 0 at the Dirichlet points, sign
+ * unspecified; host_guess: NULL (pseudo-random start vectors from a fixed integer hash: a call gives the same bits on every
+ * run) or k * vol doubles, read at the unknowns only.  Start vectors that are linearly dependent in the c W inner product (to
+ * rounding: a pivot of their scaled mass Gram not above 64 eps) are MGX_ERR_INVALID: there is no iterate to return then.
+ *   The workspace (8 k + 2 level-0 arrays -- the basis, its images, two spare sets, and the copies of d_v[0] and d_f[0] -- and
+ * the partial sums) is allocated inside the call and freed before it returns on every
+ * way out.  On return d_v[0] and d_f[0] hold the bits they held on entry and the rim flags are as they were, but for
+ * e_rim_valid[0], cleared as PCG clears it; the coarser levels hold what the last V-cycle left, as after PCG. */
+#define MG_EIGEN_MAX_BLOCK 8
+int mgMultiGrid3D_f64_Eigen(mgMultiGrid3D_f64* mg, int k, int v1, int v2, double tol, int maxit, double* lambda, double* res, int* iters,
+                            int* converged, double* host_vectors, const double* host_guess);
+/* The dense solver of Eigen, pure host code: the n eigenpairs of G y = w B y for symmetric n x n G and symmetric positive definite
+ * B (row-major; the upper triangles are read), 1 <= n <= 24.  w ascending, Y[i * n + j] = component i of vector j, Y^T B Y = I.
+ * G and B are first scaled by D = diag(B)^(-1/2) (basis vectors of unit norm), then B = L L^T, a cyclic Jacobi eigensolver on
+ * L^-1 G L^-T, Y = D L^-T Z.  Returns MGX_OK, MGX_ERR_INVALID for NULL arguments or n outside 1 .. 24, and
+ * MG_GENEIG_NOT_SPD (w and Y untouched) when B has a non-positive or non-finite diagonal entry or a pivot of the scaled B not above
+ * 64 eps, or G a non-finite entry, and MG_GENEIG_NO_CONVERGENCE (w and Y untouched) when 64 Jacobi sweeps have not brought every
+ * off-diagonal entry below eps / 8 of its two diagonal entries (some ten sweeps do at n = 24).  Eigen treats both alike. */
+#define MG_GENEIG_MAX 24
+#define MG_GENEIG_NOT_SPD 100
+#define MG_GENEIG_NO_CONVERGENCE 101
+int mg_sym_geneig(int n, const double* G, const double* B, double* w, double* Y);
+
 /* numGrids = (int)log2(minSize - 1)            N3/MultiGrid3D.cpp:33-34 */
 int mg_num_grids(int minSize);
 /* coarse size = ((size-1)/2)+1                 N3/MultiGrid3D.cpp:40-42 */

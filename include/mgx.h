@@ -878,6 +878,35 @@ enum { MGX_CG_RZ = 0, MGX_CG_PQ = 1, MGX_CG_ALPHA = 2, MGX_CG_RR = 3, MGX_CG_ZR 
        MGX_CG_STATE = 8 };
 int mgx_cg_scalars(mgx_ctx* ctx, double* dev_state, int step);
 
+/* ---- block vector kernels of the eigensolver (mgMultiGrid3D_f64_Eigen), x-split layout, fp64 -------------------------------
+ * An addition: the reference has no eigensolver.  Vectors come in groups: U, V, S, out, AX, X and R are HOST arrays of device
+ * pointers, each to an array of mgx3dxs_elems_f64 doubles.  Every kernel runs over all grid points and forms a point's weight
+ * from its position and the face mask bc (bit k = face k, x-low, x-high, y-low, y-high, z-low, z-high): 0 at a Dirichlet point (a
+ * point on a face whose bit is clear), otherwise 1/2 per face it lies on -- the weights W of the _bc entries above, so one launch
+ * serves every mask.  Entries of Dirichlet points and pads are never read as data, and pads are never written.  Sums are
+ * accumulated in double in a fixed order (the same bits on every run); dev_work: mgx3dxs_block_work_elems_f64 doubles.
+ * MGX_ERR_INVALID for NULL arguments (a NULL entry of a pointer array included), counts outside their ranges and a bc outside
+ * 0 .. 63, checked before anything is launched; MGX_ERR_SIZE for bad sizes.  Asynchronous on the compute stream; the pointer
+ * arrays, Y and mu are read before the call returns. */
+size_t mgx3dxs_block_work_elems_f64(const int n[3]);
+/* block_gram: for 1 <= nu, nv <= 4: dev_out[i * nv + j] = <U_i, V_j>_W and, unless c is NULL,
+ * dev_out[nu * nv + i * nv + j] = <U_i, c V_j>_W (c: an array of the grid, the capacity) */
+int mgx3dxs_block_gram_f64(mgx_ctx* ctx, int nu, const double* const* U, int nv, const double* const* V, const double* c,
+                           const int n[3], int bc, double* dev_work, double* dev_out);
+/* block_combine: out_i = ((Y[0][i] S_0 + Y[1][i] S_1) + Y[2][i] S_2) + ... at the unknowns, for 1 <= nin <= 12 inputs and
+ * 1 <= nout <= 4 outputs; Y: nin x nout HOST doubles, row-major.  Products and sums are formed in exactly that order, none
+ * contracted.  An output may be one of the inputs (a thread reads all inputs of a point before it writes); entries of
+ * Dirichlet points and pads of the outputs stay as they are. */
+int mgx3dxs_block_combine_f64(mgx_ctx* ctx, int nin, const double* const* S, int nout, double* const* out, const double* Y,
+                              const int n[3], int bc);
+/* block_residual: for 1 <= nvec <= 4: R_i = AX_i + mu_i * (c * X_i) (c NULL: mu_i * X_i) at the unknowns and 0 at the
+ * Dirichlet points; dev_out[i] = <R_i, R_i>_W, dev_out[nvec + i] = <X_i, X_i>_W.  mu: nvec HOST doubles. */
+int mgx3dxs_block_residual_f64(mgx_ctx* ctx, int nvec, const double* const* AX, const double* const* X, const double* c,
+                               const double* mu, double* const* R, const int n[3], int bc, double* dev_work, double* dev_out);
+/* eigen_start: v = pseudo-random values in (-1, 1) at the unknowns, from a fixed integer hash of (index, x, y, z), and 0 at the
+ * Dirichlet points; index >= 0 */
+int mgx3dxs_eigen_start_f64(mgx_ctx* ctx, double* v, int index, const int n[3], int bc);
+
 /* ---- multi-GPU: z-slab halo exchange over RCCL (xGMI) ------------------------------
  * One process per GPU.  The unique id is created on rank 0 (mgx_comm_unique_id) and
  * handed to the other ranks by the launcher (bench.py broadcasts it with

@@ -112,3 +112,4 @@ static void mg_mixed3d_free(mgx_ctx* ctx, void* state);
 #undef MG_EXP
 
 #include "mg_mixed3d.inc"
+#include "mg_eigen3d.inc"

@@ -978,6 +978,77 @@ class _Ops3D(_Ops):
         (xo, po, _), _ = self._mixed(ctx, n, [x, p, z32], [float(alpha or 0.0), float(beta or 0.0)], call, 0)
         return xo, po
 
+    # ---- block vector kernels of the eigensolver (fp64 only, mgx3dxs_block_*_f64): arrays packed (x-split), as stored, so that
+    # a caller controls the pad and Dirichlet entries too; bc is the face mask the weights are formed from
+    def _block(self, ctx, n, arrays, nsum, call):
+        """upload the packed arrays, run call(work, sums, ptrs), return (arrays as stored afterwards, sums)"""
+        assert self.xsplit, "the block kernels exist for the x-split layout only"
+        fn = lib.mgx3dxs_block_work_elems_f64
+        fn.restype = C.c_size_t
+        work, welems = self._work_alloc(ctx, fn(_ip(n)))
+        dev, selems = self._work_alloc(ctx, nsum)  # (the sums with the same guards behind them)
+        ptrs = [ctx.to_device(np.ascontiguousarray(a, np.float64)) if a is not None else None for a in arrays]
+        try:
+            check(call(work, dev, ptrs))
+            self._work_check(ctx, work, welems)
+            self._work_check(ctx, dev, selems)
+            sums = ctx.to_host(dev, (selems,), np.float64)[:nsum]
+            return [ctx.to_host(p, a.shape, np.float64) if p is not None else None for p, a in zip(ptrs, arrays)], sums
+        finally:
+            for p in ptrs + [dev, work]:
+                if p is not None:
+                    ctx.free(p)
+
+    @staticmethod
+    def _pp(ptrs):
+        return (C.c_void_p * len(ptrs))(*[p.value if p is not None else None for p in ptrs])
+
+    def block_gram(self, ctx, U, V, c, n, bc):
+        """(<U_i, V_j>_W as an array of len(U) x len(V), <U_i, c V_j>_W likewise or None without c)"""
+        nu, nv = len(U), len(V)
+
+        def call(w, s, p):
+            return lib.mgx3dxs_block_gram_f64(ctx._h, C.c_int(nu), self._pp(p[:nu]), C.c_int(nv), self._pp(p[nu:nu + nv]), p[nu + nv], _ip(n),
+                                              C.c_int(bc), w, s)
+        _, sums = self._block(ctx, n, list(U) + list(V) + [c], 2 * nu * nv, call)
+        return sums[:nu * nv].reshape(nu, nv).copy(), (sums[nu * nv:].reshape(nu, nv).copy() if c is not None else None)
+
+    def block_combine(self, ctx, S, Y, n, bc, out=None, alias=None):
+        """out_i = sum_j Y[j][i] S_j at the unknowns.  out: the arrays written into (default zeros); alias = {i: j}: output i
+        IS input j on the device (out[i] is then ignored).  Returns the outputs as stored afterwards."""
+        Y = np.ascontiguousarray(Y, np.float64)
+        nin, nout = Y.shape
+        assert nin == len(S)
+        alias = alias or {}
+        out = [np.zeros_like(S[0]) for _ in range(nout)] if out is None else list(out)
+        own = [i for i in range(nout) if i not in alias]
+
+        def call(w, s, p):
+            outs = [p[alias[i]] if i in alias else p[nin + own.index(i)] for i in range(nout)]
+            return lib.mgx3dxs_block_combine_f64(ctx._h, C.c_int(nin), self._pp(p[:nin]), C.c_int(nout), self._pp(outs),
+                                                 Y.ctypes.data_as(C.c_void_p), _ip(n), C.c_int(bc))
+        res, _ = self._block(ctx, n, list(S) + [out[i] for i in own], 0, call)
+        return [res[alias[i]] if i in alias else res[nin + own.index(i)] for i in range(nout)]
+
+    def block_residual(self, ctx, AX, X, c, mu, n, bc, R=None):
+        """R_i = AX_i + mu_i (c X_i) at the unknowns, 0 at the Dirichlet points.  Returns (R, <R_i, R_i>_W, <X_i, X_i>_W)."""
+        k = len(X)
+        mu = np.ascontiguousarray(mu, np.float64)
+        R = [np.zeros_like(X[0]) for _ in range(k)] if R is None else list(R)
+
+        def call(w, s, p):
+            return lib.mgx3dxs_block_residual_f64(ctx._h, C.c_int(k), self._pp(p[:k]), self._pp(p[k:2 * k]), p[3 * k],
+                                                  mu.ctypes.data_as(C.c_void_p), self._pp(p[2 * k:3 * k]), _ip(n), C.c_int(bc), w, s)
+        res, sums = self._block(ctx, n, list(AX) + list(X) + R + [c], 2 * k, call)
+        return res[2 * k:3 * k], sums[:k].copy(), sums[k:].copy()
+
+    def eigen_start(self, ctx, index, n, bc, v=None):
+        """the start vector `index` of the eigensolver, as stored; v: the array written into (default zeros)"""
+        H, P_ = xs_geometry(n[0], 8)
+        v = np.zeros(_shape(n)[:-1] + (P_,), np.float64) if v is None else v
+        (vo,), _ = self._block(ctx, n, [v], 0, lambda w, s, p: lib.mgx3dxs_eigen_start_f64(ctx._h, p[0], C.c_int(index), _ip(n), C.c_int(bc)))
+        return vo
+
 
 class _Ops2D(_Ops):
     def __init__(self):
@@ -1518,6 +1589,36 @@ class MultiGrid3D(_MGBase):
                    C.c_int(min(mode, 1) if precond == "f32" else mode), C.byref(it), C.byref(rel), C.byref(conv), hist.ctypes.data_as(C.c_void_p),
                    C.c_int(len(hist)))
         return int(it.value), float(rel.value), bool(conv.value), hist[:it.value].copy()
+
+    def Eigen(self, k, tol=1e-8, maxit=200, v1=2, v2=2, vectors=True, guess=None):
+        """The k smallest eigenvalues and eigenvectors of the hierarchy's operator (mgMultiGrid3D_f64_Eigen):
+        -(div(a grad x)) [+ the walls' diagonal] = lambda c x on the unknowns, by LOBPCG with block size k (1 .. 8), one
+        V(v1, v2) cycle from zero per residual as the preconditioner.  The shift of the hierarchy is a spectral shift only
+        (lambda does not depend on it), so a closed insulated box, whose lowest eigenvalue is 0, is solved with any shift > 0.
+        fp64 hierarchies, x-split layout, residual_mode=CORRECT.
+
+        Returns (lam, X, info): lam ascending; X of shape (k, nz, ny, nx) with <x_i, c x_j>_W = delta_ij (sign unspecified), or
+        None with vectors=False; info = {"iterations", "residuals", "converged"}, the residuals being
+        ||A_s x + mu c x||_W / (mu ||x||_W) with mu = lambda + shift, each below tol when converged.  guess: k start vectors of
+        that shape (read at the unknowns only); the default start is pseudo-random and the same on every call.  v[0] and f[0]
+        are left as they were."""
+        if self.dtype != np.float64:
+            raise ValueError("Eigen needs an fp64 hierarchy (the eigensolver is fp64 only), not %s" % self.dtype)
+        k = int(k)
+        kk = max(1, min(k, 8))
+        shape = _shape(self.size(0))
+        gp = None
+        if guess is not None:
+            guess = np.ascontiguousarray(guess, np.float64)
+            if guess.shape != (k,) + shape:
+                raise ValueError("guess must have the shape %r, not %r" % ((k,) + shape, guess.shape))
+            gp = guess.ctypes.data_as(C.c_void_p)
+        lam, res = np.zeros(kk, np.float64), np.zeros(kk, np.float64)
+        X = np.zeros((kk,) + shape, np.float64) if vectors else None
+        it, conv = C.c_int(), C.c_int()
+        self._call("Eigen", C.c_int(k), C.c_int(v1), C.c_int(v2), C.c_double(tol), C.c_int(maxit), lam.ctypes.data_as(C.c_void_p),
+                   res.ctypes.data_as(C.c_void_p), C.byref(it), C.byref(conv), X.ctypes.data_as(C.c_void_p) if vectors else None, gp)
+        return lam, X, {"iterations": int(it.value), "residuals": res, "converged": bool(conv.value)}
 
     @property
     def pcg_removed_mean(self):
