@@ -133,6 +133,14 @@ typedef struct mgGraphFlags {
         union {                                                                                          \
             long long graph_key[MG_MAX_LEVELS - 3]; /* unused */                                         \
             int face_mean;                                                                               \
+            /* internal: the pinned interior nodes of _set_pinned (per level the list of their storage   */\
+            /* offsets and their values, on the device), or NULL (none).  Owned by _set_pinned, freed by */\
+            /* _destroy.  It takes the last eight bytes of the unused graph_key, in front of `wall`:     */\
+            /* every member keeps its offset and the struct its size.                                    */\
+            struct {                                                                                     \
+                long long graph_key_head_[MG_MAX_LEVELS - 4]; /* (face_mean and unused words) */         \
+                void* pin;                                                                               \
+            };                                                                                           \
         };                                                                                               \
         /* internal: the walls of _set_wall (beta and g of the six faces), or NULL (none).  Owned by     */\
         /* _set_wall, freed by _destroy.  Like cap below it takes eight bytes of the unused graph_key:   */\
@@ -245,6 +253,30 @@ typedef struct mgGraphFlags {
     int mgMultiGrid3D_##R##_set_wall(mgMultiGrid3D_##R* mg, const real beta[6], const real g[6]);        \
     int mgMultiGrid3D_##R##_get_wall(const mgMultiGrid3D_##R* mg, real beta[6], real g[6]);              \
     int mgMultiGrid3D_##R##_add_wall_flux(mgMultiGrid3D_##R* mg);                                        \
+    /* Pinned interior nodes (an addition; csrc/mgx_pin3d.hip).  mask[x + y sx + z sx sy]  */\
+    /* != 0 makes the interior point (x, y, z) of level 0 DATA with the value values[...] (values ==     */\
+    /* NULL: 0): it is no unknown, its neighbours read it as they read a Dirichlet face point, the       */\
+    /* smoother never changes it, and the residual, A p and every vector of PCG are exactly 0 there; the */\
+    /* operator on the other unknowns is the old one with rows and columns struck out.  A coarse point   */\
+    /* is pinned when its coincident fine point is, or one of that point's neighbours at +-1 along an    */\
+    /* axis that the step halves; coarse boundary points never are.  The values go down by injection.    */\
+    /* The level a cycle starts on (Relax, VCycle's gridID, every level in turn in FullMultiGridVCycle)  */\
+    /* holds the stored values at its pins, every level that holds a correction (below the top; level 0  */\
+    /* inside PCG's preconditioner) zeros.  Every level then takes the operator route (the plain         */\
+    /* Laplacian as the shifted operator with s = 0), the residual is stored, its pins zeroed, then      */\
+    /* restricted; ResidualNorm and PCG's stopping rule sum over the unknowns only, for one more read    */\
+    /* pass.  _set_pinned validates (a true entry on the boundary of the box is MGX_ERR_INVALID and      */\
+    /* names the first one), builds and uploads every level's list, puts the values into d_v of every    */\
+    /* level and drops every captured graph.  Blocking.  mask == NULL or all zero: no pins, and the      */\
+    /* hierarchy is launch for launch what it was without them.  Pins need layout = 1, smoother = 0,     */\
+    /* residual_mode = MGX_RESIDUAL_CORRECT (else MGX_ERR_INVALID, here and where they are used);        */\
+    /* PCG_mixed and Eigen return MGX_ERR_INVALID with pins, and so does every operator of a closed box  */\
+    /* (all six faces walls, shift == 0, no beta > 0), PCG(krylov = 2) included.                         */\
+    /* _get_pinned: level gridID's mask in the reference layout (0 / 1); _pinned_count: its count.       */\
+    int mgMultiGrid3D_##R##_set_pinned(mgMultiGrid3D_##R* mg, const unsigned char* mask,                 \
+                                       const real* values);                                              \
+    int mgMultiGrid3D_##R##_get_pinned(const mgMultiGrid3D_##R* mg, int gridID, unsigned char* mask);    \
+    int mgMultiGrid3D_##R##_pinned_count(const mgMultiGrid3D_##R* mg, int gridID, size_t* count);        \
     /* shift must be finite and >= 0, and a non-zero one needs the settings named at the member          */ \
     int mgMultiGrid3D_##R##_set_shift(mgMultiGrid3D_##R* mg, real shift);                                \
     size_t mgMultiGrid3D_##R##_sizeof(void); /* sizeof(mgMultiGrid3D_<r>): for mirrors of the struct */  \

@@ -708,6 +708,10 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     int mgx3dxs_cg_update_bc_##SFX(mgx_ctx* ctx, real* x, const real* p, real* r, const real* q,        \
                                    const int n[3], const double* dev_alpha, double* dev_work,           \
                                    double* dev_sum, int bc);                                            \
+    /* sumsq_bc: *dev_sum = the UNWEIGHTED sum of a^2 over all unknowns, the norm of a stored residual */ \
+    /*   (bc = 0: mgx3dxs_dot2(a, a)'s bits); dev_work as for the entries above.                        */ \
+    int mgx3dxs_sumsq_bc_##SFX(mgx_ctx* ctx, const real* a, const int n[3], double* dev_work,           \
+                               double* dev_sum, int bc);                                                \
     int mgx3dxs_dot2_bc_##SFX(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3],\
                               double* dev_work, double* dev_sum, int bc);                               \
     int mgx3dxs_cg_direction_bc_##SFX(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3],    \
@@ -824,7 +828,44 @@ int mgx_event_elapsed_ms(mgx_ctx* ctx, mgx_event* start, mgx_event* stop, float*
     int mgx3dxs_apply_hmean_dot_wall_##SFX(mgx_ctx* ctx, const real* p, const real* a, const real* c,   \
                                            real* q, const int n[3], const real h[3], real s,            \
                                            double* dev_work, double* dev_sum, int bc,                   \
-                                           const real beta[6]);
+                                           const real beta[6]);                                         \
+    /* Pinned interior nodes (csrc/mgx_pin3d.hip; x-split only): interior points whose    */ \
+    /* value is data.  A level's pinned points are a LIST of 32-bit storage offsets into the x-split    */ \
+    /* array (device memory): the red points ((x + y + z) even) first, then the black ones, each colour */ \
+    /* sorted by offset; end[0] = the number of red points, end[1] = the number of all; the values, one */ \
+    /* per entry in list order, in a device array val (NULL: zeros).                                    */ \
+    /* pin_list (host only, no launch): the list of a mask in the reference layout (mask[x + y sx +     */ \
+    /*   z sx sy] != 0: pinned) into idx (host memory; NULL: only end[] is filled, to size it); with    */ \
+    /*   val, val[t] = values[point t] (values: reference layout, all points; NULL: zeros).             */ \
+    /*   MGX_ERR_INVALID for a true entry on the boundary of the box, naming the first one;             */ \
+    /*   MGX_ERR_SIZE for bad sizes and for a level whose storage does not fit 32-bit offsets.          */ \
+    /* pin_put: v[idx[t]] = val ? val[t] : 0 for t in [first, first + count): plain stores, one thread  */ \
+    /*   per entry, nothing else of v is touched; count == 0 launches nothing.  The offsets are not     */ \
+    /*   checked here: they have to lie inside v (pin_list's do).                                       */ \
+    /* relax_*_pin: the _wall entry, argument for argument, plus the list: after the interior launch    */ \
+    /*   (and the face launch) of a colour pass that colour's pinned entries of v are put back to val   */ \
+    /*   (zeros), so that no pass ever reads an updated pinned point and v holds the data on return.    */ \
+    /*   With end[1] == 0 it is the _wall entry, launch for launch.  v should hold the data at the pins */ \
+    /*   on entry (the first red pass reads the black ones).  hmean: c == NULL means no capacity.       */ \
+    int mgx3dxs_pin_list_##SFX(const int n[3], const unsigned char* mask, const real* values,           \
+                               unsigned* idx, real* val, unsigned end[2]);                              \
+    int mgx3dxs_pin_put_##SFX(mgx_ctx* ctx, real* v, const unsigned* idx, const real* val,              \
+                              unsigned first, unsigned count);                                          \
+    int mgx3dxs_relax_shift_pin_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3],             \
+                                      const real h[3], real s, int ncycles, int bc, const real beta[6], \
+                                      const unsigned* idx, const unsigned end[2], const real* val);     \
+    int mgx3dxs_relax_coef_pin_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,               \
+                                     const int n[3], const real h[3], real s, int ncycles, int bc,      \
+                                     const real beta[6], const unsigned* idx, const unsigned end[2],    \
+                                     const real* val);                                                  \
+    int mgx3dxs_relax_cap_pin_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c, \
+                                    const int n[3], const real h[3], real s, int ncycles, int bc,       \
+                                    const real beta[6], const unsigned* idx, const unsigned end[2],     \
+                                    const real* val);                                                   \
+    int mgx3dxs_relax_hmean_pin_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a,              \
+                                      const real* c, const int n[3], const real h[3], real s,           \
+                                      int ncycles, int bc, const real beta[6], const unsigned* idx,     \
+                                      const unsigned end[2], const real* val);
 
 MGX_DECLARE_OPS(f32, float)
 MGX_DECLARE_OPS(f64, double)

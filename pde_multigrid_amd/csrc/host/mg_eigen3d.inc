@@ -365,6 +365,7 @@ int mgMultiGrid3D_f64_Eigen(mgMultiGrid3D_f64* mg, int k, int v1, int v2, double
     MG_REQUIRE(mg->grids3D && mg->grids3D[0] && mg->ctx, MGX_ERR_INVALID, "Eigen: the hierarchy has no levels");
     MG_REQUIRE(mg->numGrids >= 1 && mg->numGrids <= mg->maxGrids, MGX_ERR_INVALID, "Eigen: numGrids = %d outside [1,%d]", mg->numGrids,
                mg->maxGrids);
+    MG_REQUIRE(!mg->pin, MGX_ERR_INVALID, "Eigen: a hierarchy with pinned nodes (set_pinned) is not supported");
     MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "Eigen: needs the x-split layout (layout = 1)");
     MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "Eigen: needs residual_mode = MGX_RESIDUAL_CORRECT");
     mgGrid3D_f64* g = mg->grids3D[0];

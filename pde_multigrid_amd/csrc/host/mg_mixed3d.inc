@@ -212,6 +212,7 @@ int mgMultiGrid3D_f64_PCG_mixed(mgMultiGrid3D_f64* mg, int v1, int v2, double to
                mg->numGrids, mg->maxGrids);
     MG_REQUIRE(!mg->cap, MGX_ERR_INVALID, "PCG_mixed: a hierarchy with a capacity is not supported");
     MG_REQUIRE(!mg->wall, MGX_ERR_INVALID, "PCG_mixed: a hierarchy with wall data (set_wall) is not supported");
+    MG_REQUIRE(!mg->pin, MGX_ERR_INVALID, "PCG_mixed: a hierarchy with pinned nodes (set_pinned) is not supported: precond = f32 is not available");
     MG_REQUIRE(mg->shift == 0, MGX_ERR_INVALID, "PCG_mixed: a shifted hierarchy (shift = %g) is not supported", mg->shift);
     MG_REQUIRE(!(mg->grids3D && mg->grids3D[0] && mg->grids3D[0]->d_a), MGX_ERR_INVALID,
                "PCG_mixed: a hierarchy with a coefficient is not supported");

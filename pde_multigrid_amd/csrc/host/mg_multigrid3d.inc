@@ -222,8 +222,46 @@ static const REAL* MG_CAT(wall_beta3_, R)(const MGRID* mg) {
 }
 static const REAL MG_CAT(no_wall3_, R)[6] = {0, 0, 0, 0, 0, 0};
 
+/* the pinned interior nodes of DESIGN.md 22: mg->pin points to this table, or is NULL (no point is pinned).  Per level the list of
+ * mgx.h (device: storage offsets, red first, and the values in list order; both NULL where the level has no pinned point), its two
+ * counts, and the level's mask in the reference layout on the host (what _get_pinned returns) */
+typedef struct MG_CAT(mgPinTable3_, R) {
+    unsigned* d_idx[MG_MAX_LEVELS];
+    REAL* d_val[MG_MAX_LEVELS];
+    unsigned end[MG_MAX_LEVELS][2];
+    unsigned char* h_mask[MG_MAX_LEVELS];
+} MG_CAT(mgPinTable3_, R);
+#define PINTAB MG_CAT(mgPinTable3_, R)
+
+static void MG_CAT(pin_table_free3_, R)(MGRID* mg) {
+    PINTAB* t = (PINTAB*)mg->pin;
+    if (!t) return;
+    for (int i = 0; i < MG_MAX_LEVELS; i++) {
+        mgx_free(mg->ctx, t->d_idx[i]);
+        mgx_free(mg->ctx, t->d_val[i]);
+        free(t->h_mask[i]);
+    }
+    free(t);
+    mg->pin = NULL;
+}
+
+/* the level of grid g, -1 where it is none of the hierarchy's */
+static int MG_CAT(level_of3_, R)(const MGRID* mg, const GRID* g) {
+    for (int i = 0; i < mg->maxGrids; i++)
+        if (mg->grids3D[i] == g) return i;
+    return -1;
+}
+
+/* dev (an array of level lvl) := the level's values (values != 0) or zeros at its pinned points; nothing without pins */
+static int MG_CAT(pin_put3_, R)(MGRID* mg, int lvl, REAL* dev, int values) {
+    const PINTAB* t = (const PINTAB*)mg->pin;
+    if (!t || lvl < 0 || !t->end[lvl][1]) return MGX_OK;
+    return MG_CAT(mgx3dxs_pin_put_, R)(mg->ctx, dev, t->d_idx[lvl], values ? t->d_val[lvl] : NULL, 0u, t->end[lvl][1]);
+}
+
 void FN(destroy)(MGRID* mg) {
     if (!mg) return;
+    MG_CAT(pin_table_free3_, R)(mg);
     MG_CAT(cap_table_free3_, R)(mg);
     free(mg->wall);
     mg->wall = NULL;
@@ -353,7 +391,23 @@ static int MG_CAT(cap_singular3_, R)(const MGRID* mg, const char* what) {
 /* The operators other than the plain Laplacian: the variable-coefficient one where the hierarchy has a coefficient (with any
  * shift), else the shifted one where shift != 0.  What the hierarchy's operator needs of the hierarchy and of the grid g it is
  * applied to (nothing for the plain one). */
+/* what pinned nodes need of the hierarchy (the members are public: checked by set_pinned and where the pins are used).  The closed
+ * box without a shift is refused whatever the pins: its projection would be wrong and a coarse level may lose the last pin. */
+static int MG_CAT(pin_ok3_, R)(const MGRID* mg, const char* what) {
+    if (!mg->pin) return MGX_OK;
+    MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "%s: a hierarchy with pinned nodes needs the x-split layout (layout = 1, not natural)", what);
+    MG_REQUIRE(mg->smoother == 0, MGX_ERR_INVALID,
+               "%s: a hierarchy with pinned nodes needs the red-black smoother (smoother = 0): the Jacobi smoother is not available", what);
+    MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID,
+               "%s: a hierarchy with pinned nodes needs residual_mode = MGX_RESIDUAL_CORRECT", what);
+    MG_REQUIRE(!(mg->bc == 63 && mg->shift == 0 && !MG_CAT(wall_beta3_, R)(mg)), MGX_ERR_INVALID,
+               "%s: pinned nodes are not available in the closed box (walls on all six faces, shift = 0, no beta > 0), krylov = 2 "
+               "included: keep a Dirichlet face, set a shift > 0 or a beta > 0", what);
+    return MGX_OK;
+}
+
 static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) {
+    MG_TRY(MG_CAT(pin_ok3_, R)(mg, what));
     MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, what));
     MG_TRY(MG_CAT(bc_singular3_, R)(mg, what));
     MG_TRY(MG_CAT(cap_singular3_, R)(mg, what));
@@ -366,11 +420,11 @@ static int MG_CAT(op_ok3_, R)(const MGRID* mg, const GRID* g, const char* what) 
 
 /* r = f - A v on grid g by the hierarchy's operator, 0 on the boundary (r == NULL: not stored), and its sum of squares into
  * *dev_sumsq (NULL: none; dev_work: the partials).  The plain operator takes mg->residual_mode and sums in a launch of its own. */
-static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, const REAL* f, REAL* r, double* dev_work, double* dev_sumsq) {
+static int MG_CAT(op_residual_all3_, R)(MGRID* mg, const GRID* g, const REAL* v, const REAL* f, REAL* r, double* dev_work, double* dev_sumsq) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
     const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
     const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R); /* the _wall entries with the level's own spacings (DESIGN.md 18) */
-    const int faces = mg->bc || wall;                    /* (betas without a mask: the entry refuses them) */
+    const int faces = mg->bc || wall || mg->pin;         /* (betas without a mask: the entry refuses them; pins: the op route) */
     if (MG_CAT(harm3_, R)(mg))
         return MG_CAT(mgx3dxs_residual_hmean_wall_, R)(mg->ctx, v, f, g->d_a, MG_CAT(harm_cap3_, R)(mg, g), r, g->sizeXYZ, h, mg->shift, dev_work,
                                                        dev_sumsq, mg->bc, wb);
@@ -385,13 +439,31 @@ static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, con
     return dev_sumsq ? MG_CAT(mgx3dxs_dot2_, R)(mg->ctx, r, r, NULL, g->sizeXYZ, dev_work, dev_sumsq) : MGX_OK;
 }
 
+/* ... and with pinned nodes: the fused sum would include what the kernels compute at the pins, so the residual is stored (into the
+ * level's d_r where the caller passes none), its pins zeroed, and the sum taken over the stored array in a pass of its own
+ * (without a mask: mgx3dxs_dot2's bits) */
+static int MG_CAT(op_residual3_, R)(MGRID* mg, const GRID* g, const REAL* v, const REAL* f, REAL* r, double* dev_work, double* dev_sumsq) {
+    const int lvl = mg->pin ? MG_CAT(level_of3_, R)(mg, g) : -1;
+    if (lvl < 0) return MG_CAT(op_residual_all3_, R)(mg, g, v, f, r, dev_work, dev_sumsq);
+    if (!r) r = g->d_r;
+    MG_TRY(MG_CAT(op_residual_all3_, R)(mg, g, v, f, r, NULL, NULL));
+    MG_TRY(MG_CAT(pin_put3_, R)(mg, lvl, r, 0));
+    return dev_sumsq ? MG_CAT(mgx3dxs_sumsq_bc_, R)(mg->ctx, r, g->sizeXYZ, dev_work, dev_sumsq, mg->bc) : MGX_OK;
+}
+
 /* q = A p on grid g by the hierarchy's operator (x-split, CORRECT mode), *dev_sum = <p, q>; with a mask at all unknowns and in the
- * weighted inner product (the plain Laplacian is then the shifted operator with s = 0) */
+ * weighted inner product (the plain Laplacian is then the shifted operator with s = 0).  With pinned nodes p is 0 there, so the
+ * fused <p, q> is right as it is, and q's pins are zeroed afterwards */
+static int MG_CAT(op_apply_dot_all3_, R)(MGRID* mg, const GRID* g, const REAL* p, REAL* q, double* dev_work, double* dev_sum);
 static int MG_CAT(op_apply_dot3_, R)(MGRID* mg, const GRID* g, const REAL* p, REAL* q, double* dev_work, double* dev_sum) {
+    MG_TRY(MG_CAT(op_apply_dot_all3_, R)(mg, g, p, q, dev_work, dev_sum));
+    return mg->pin ? MG_CAT(pin_put3_, R)(mg, MG_CAT(level_of3_, R)(mg, g), q, 0) : MGX_OK;
+}
+static int MG_CAT(op_apply_dot_all3_, R)(MGRID* mg, const GRID* g, const REAL* p, REAL* q, double* dev_work, double* dev_sum) {
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
     const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
     const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R);
-    const int faces = mg->bc || wall; /* (betas without a mask: the entry refuses them) */
+    const int faces = mg->bc || wall || mg->pin; /* (betas without a mask: the entry refuses them; pins: the op route, s = 0 too) */
     if (MG_CAT(harm3_, R)(mg)) /* (with bc = 0 the entry is the interior entry) */
         return MG_CAT(mgx3dxs_apply_hmean_dot_wall_, R)(mg->ctx, p, g->d_a, MG_CAT(harm_cap3_, R)(mg, g), q, g->sizeXYZ, h, mg->shift, dev_work,
                                                         dev_sum, mg->bc, wb);
@@ -652,6 +724,117 @@ int FN(add_wall_flux)(MGRID* mg) {
     return MG_CAT(mgx3dxs_wall_rhs_, R)(mg->ctx, g0->d_f, g0->sizeXYZ, h, t->g, mg->bc);
 }
 
+/* the pinned nodes (mg_multigrid.h).  Every call drops the captured graphs: their launches hold the lists. */
+int FN(set_pinned)(MGRID* mg, const unsigned char* mask, const REAL* values) {
+    MG_REQUIRE(mg && mg->grids3D && mg->maxGrids >= 1, MGX_ERR_INVALID, "set_pinned: NULL");
+    const GRID* g0 = mg->grids3D[0];
+    const size_t vol0 = MG_CAT(vol3_, R)(g0);
+    size_t count0 = 0;
+    for (size_t i = 0; mask && i < vol0; i++) count0 += mask[i] != 0;
+    if (!count0) { /* no pins: the hierarchy is one that never had any */
+        if (!mg->pin) return MGX_OK;
+        MG_TRY(mgx_ctx_sync(mg->ctx));
+        MG_CAT(coef_drop_graphs3_, R)(mg);
+        MG_CAT(pin_table_free3_, R)(mg);
+        return MGX_OK;
+    }
+    MG_REQUIRE(mg->layout == 1, MGX_ERR_INVALID, "set_pinned: pinned nodes need the x-split layout (layout = 1, not natural)");
+    MG_REQUIRE(mg->smoother == 0, MGX_ERR_INVALID,
+               "set_pinned: pinned nodes need the red-black smoother (smoother = 0): the Jacobi smoother is not available");
+    MG_REQUIRE(mg->residual_mode == MGX_RESIDUAL_CORRECT, MGX_ERR_INVALID, "set_pinned: pinned nodes need residual_mode = MGX_RESIDUAL_CORRECT");
+    for (size_t i = 0; values && i < vol0; i++)
+        MG_REQUIRE(!mask[i] || isfinite((double)values[i]), MGX_ERR_INVALID, "set_pinned: values[%zu] = %g is not finite", i, (double)values[i]);
+    unsigned end0[2];
+    MG_TRY(MG_CAT(mgx3dxs_pin_list_, R)(g0->sizeXYZ, mask, NULL, NULL, NULL, end0)); /* refuses a boundary point, naming the first one */
+    PINTAB* t = (PINTAB*)calloc(1, sizeof(PINTAB));
+    MG_REQUIRE(t, MGX_ERR_NOMEM, "set_pinned: out of host memory");
+    /* per level on the host: the mask by the coarse rule, the values by injection, the list; then the upload */
+    int st = MGX_OK;
+    REAL* val_f = NULL; /* the values of the level above at ALL its points */
+    for (int l = 0; !st && l < mg->maxGrids; l++) {
+        const GRID* g = mg->grids3D[l];
+        const int sx = g->sizeX, sy = g->sizeY, sz = g->sizeZ;
+        const size_t vol = MG_CAT(vol3_, R)(g);
+        unsigned char* m = (unsigned char*)calloc(vol, 1);
+        REAL* val = (REAL*)calloc(vol, sizeof(REAL));
+        unsigned* idx = NULL;
+        REAL* lv = NULL;
+        if (!m || !val) st = mg_fail(MGX_ERR_NOMEM, "set_pinned: out of host memory");
+        if (!st && l == 0) {
+            for (size_t i = 0; i < vol; i++) m[i] = mask[i] != 0;
+            if (values) memcpy(val, values, vol * sizeof(REAL));
+        } else if (!st) {
+            const GRID* gf = mg->grids3D[l - 1];
+            const unsigned char* mf = t->h_mask[l - 1];
+            const int ax = mg->coarsen[l - 1], fx = gf->sizeX, fy = gf->sizeY;
+            const int kx = ax & 1 ? 2 : 1, ky = ax & 2 ? 2 : 1, kz = ax & 4 ? 2 : 1;
+            for (int z = 0; z < sz; z++)
+                for (int y = 0; y < sy; y++)
+                    for (int x = 0; x < sx; x++) {
+                        const size_t c = ((size_t)z * sy + y) * sx + x, f = ((size_t)(kz * z) * fy + (size_t)(ky * y)) * fx + (size_t)(kx * x);
+                        val[c] = val_f[f];
+                        if (x == 0 || x == sx - 1 || y == 0 || y == sy - 1 || z == 0 || z == sz - 1) continue; /* (an interior coarse */
+                        int on = mf[f];                                          /* point's fine neighbours are inside the fine grid) */
+                        if (ax & 1) on |= mf[f - 1] | mf[f + 1];
+                        if (ax & 2) on |= mf[f - (size_t)fx] | mf[f + (size_t)fx];
+                        if (ax & 4) on |= mf[f - (size_t)fx * fy] | mf[f + (size_t)fx * fy];
+                        m[c] = on != 0;
+                    }
+        }
+        if (!st) st = MG_CAT(mgx3dxs_pin_list_, R)(g->sizeXYZ, m, NULL, NULL, NULL, t->end[l]);
+        const unsigned cnt = t->end[l][1];
+        if (!st && cnt) {
+            idx = (unsigned*)malloc((size_t)cnt * sizeof(unsigned));
+            lv = (REAL*)malloc((size_t)cnt * sizeof(REAL));
+            if (!idx || !lv) st = mg_fail(MGX_ERR_NOMEM, "set_pinned: out of host memory");
+            if (!st) st = MG_CAT(mgx3dxs_pin_list_, R)(g->sizeXYZ, m, val, idx, lv, t->end[l]); /* (the values in list order) */
+            if (!st) st = mgx_malloc(mg->ctx, (size_t)cnt * sizeof(unsigned), (void**)&t->d_idx[l]);
+            if (!st) st = mgx_malloc(mg->ctx, (size_t)cnt * sizeof(REAL), (void**)&t->d_val[l]);
+            if (!st) st = mgx_memcpy_h2d(mg->ctx, t->d_idx[l], idx, (size_t)cnt * sizeof(unsigned));
+            if (!st) st = mgx_memcpy_h2d(mg->ctx, t->d_val[l], lv, (size_t)cnt * sizeof(REAL));
+        }
+        free(idx);
+        free(lv);
+        free(val_f);
+        val_f = val;
+        t->h_mask[l] = m;
+    }
+    free(val_f);
+    if (!st) st = mgx_ctx_sync(mg->ctx); /* (nothing of a captured cycle is in flight any more; the uploads are done) */
+    PINTAB* old = (PINTAB*)mg->pin;
+    mg->pin = t;
+    if (st) { /* nothing half-built stays behind: the hierarchy keeps the pins it had */
+        MG_CAT(pin_table_free3_, R)(mg);
+        mg->pin = old;
+        return st;
+    }
+    MG_CAT(coef_drop_graphs3_, R)(mg);
+    mg->pin = old;
+    MG_CAT(pin_table_free3_, R)(mg);
+    mg->pin = t;
+    for (int l = 0; !st && l < mg->maxGrids; l++) st = MG_CAT(pin_put3_, R)(mg, l, mg->grids3D[l]->d_v, 1); /* v = g at the pins */
+    if (!st) st = mgx_ctx_sync(mg->ctx);
+    return st;
+}
+
+int FN(get_pinned)(const MGRID* mg, int gridID, unsigned char* mask) {
+    MG_REQUIRE(mg && gridID >= 0 && gridID < mg->maxGrids, MGX_ERR_INVALID, "get_pinned: bad gridID %d", gridID);
+    MG_REQUIRE(mask, MGX_ERR_INVALID, "get_pinned: NULL");
+    const PINTAB* t = (const PINTAB*)mg->pin;
+    const size_t vol = MG_CAT(vol3_, R)(mg->grids3D[gridID]);
+    if (t) memcpy(mask, t->h_mask[gridID], vol);
+    else memset(mask, 0, vol);
+    return MGX_OK;
+}
+
+int FN(pinned_count)(const MGRID* mg, int gridID, size_t* count) {
+    MG_REQUIRE(mg && gridID >= 0 && gridID < mg->maxGrids, MGX_ERR_INVALID, "pinned_count: bad gridID %d", gridID);
+    MG_REQUIRE(count, MGX_ERR_INVALID, "pinned_count: NULL");
+    const PINTAB* t = (const PINTAB*)mg->pin;
+    *count = t ? (size_t)t->end[gridID][1] : 0;
+    return MGX_OK;
+}
+
 int FN(Restrict)(MGRID* mg, const REAL* fine, const int fsizeXYZ[3], REAL* coarse, const int csizeXYZ[3]) {
     MG_REQUIRE(mg, MGX_ERR_INVALID, "Restrict: NULL");
     MG_CAT(f_touched3_, R)(mg, coarse); /* boundary = injection of the fine boundary (:113-119) */
@@ -678,13 +861,49 @@ int FN(Interpolate)(MGRID* mg, REAL* fine, const int fsizeXYZ[3], const REAL* co
     return MGXL(mg, interpolate)(mg->ctx, fine, fsizeXYZ, coarse, csizeXYZ);
 }
 
+/* Relax on a hierarchy with pinned nodes: the hierarchy's operator through the _pin entries, which put the level's values (zeros:
+ * the level holds a correction) back after every colour pass */
+static int MG_CAT(relax_pin3_, R)(MGRID* mg, GRID* curGrid, int lvl, int ncycles, int zeros) {
+    const PINTAB* t = (const PINTAB*)mg->pin;
+    const REAL h[3] = {curGrid->h_x, curGrid->h_y, curGrid->h_z};
+    const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
+    const REAL* wb = wall ? wall : MG_CAT(no_wall3_, R);
+    const unsigned none[2] = {0, 0};
+    const unsigned* idx = lvl >= 0 ? t->d_idx[lvl] : NULL;
+    const unsigned* end = lvl >= 0 ? t->end[lvl] : none;
+    const REAL* val = lvl >= 0 && !zeros ? t->d_val[lvl] : NULL;
+    if (mg->bc) MG_CAT(v_touched3_, R)(mg, curGrid->d_v);
+    if (MG_CAT(harm3_, R)(mg))
+        return MG_CAT(mgx3dxs_relax_hmean_pin_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(harm_cap3_, R)(mg, curGrid),
+                                                   curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb, idx, end, val);
+    if (MG_CAT(has_cap3_, R)(mg))
+        return MG_CAT(mgx3dxs_relax_cap_pin_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, MG_CAT(cap_of3_, R)(mg, curGrid),
+                                                 curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb, idx, end, val);
+    if (MG_CAT(has_coef3_, R)(mg))
+        return MG_CAT(mgx3dxs_relax_coef_pin_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->d_a, curGrid->sizeXYZ, h, mg->shift, ncycles,
+                                                  mg->bc, wb, idx, end, val);
+    return MG_CAT(mgx3dxs_relax_shift_pin_, R)(mg->ctx, curGrid->d_v, curGrid->d_f, curGrid->sizeXYZ, h, mg->shift, ncycles, mg->bc, wb, idx,
+                                               end, val);
+}
+
+static int MG_CAT(relax_lvl3_, R)(MGRID* mg, GRID* curGrid, int ncycles, int zeros);
+
+/* the public Relax: the level is the top of a cycle, its pinned points hold the stored values */
 int FN(Relax)(MGRID* mg, GRID* curGrid, int ncycles) {
+    MG_REQUIRE(mg && curGrid, MGX_ERR_INVALID, "Relax: NULL");
+    if (mg->pin) MG_TRY(MG_CAT(pin_put3_, R)(mg, MG_CAT(level_of3_, R)(mg, curGrid), curGrid->d_v, 1)); /* (as VCycle does) */
+    return MG_CAT(relax_lvl3_, R)(mg, curGrid, ncycles, 0);
+}
+
+/* zeros: the level holds a correction (its pinned points are zeros); counts only with pinned nodes */
+static int MG_CAT(relax_lvl3_, R)(MGRID* mg, GRID* curGrid, int ncycles, int zeros) {
     MG_REQUIRE(mg && curGrid, MGX_ERR_INVALID, "Relax: NULL");
     const REAL h[3] = {curGrid->h_x, curGrid->h_y, curGrid->h_z};
     int lvl = -1;
     for (int i = 0; i < mg->maxGrids; i++)
         if (mg->grids3D[i] == curGrid) lvl = i;
     MG_TRY(MG_CAT(op_ok3_, R)(mg, curGrid, "Relax"));
+    if (mg->pin) return MG_CAT(relax_pin3_, R)(mg, curGrid, lvl, ncycles, zeros);
     /* the coefficient and the shifted operator: one launch per colour pass; d_e is not used */
     if (mg->bc) MG_CAT(v_touched3_, R)(mg, curGrid->d_v); /* with a mask each colour pass is followed by its launch over the face unknowns */
     const REAL* wall = MG_CAT(wall_beta3_, R)(mg);
@@ -828,7 +1047,8 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
     const int coef = MG_CAT(has_coef3_, R)(mg);
     const REAL h[3] = {fine->h_x, fine->h_y, fine->h_z};
     const int bc = mg->bc; /* Neumann faces: no from-zero shortcut (v := 0 on all points, then Relax), the stored-residual route */
-    if (!bc && v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
+    const int pins = mg->pin != NULL; /* pinned nodes: likewise; v_zero says whether the level's pins hold zeros or the values */
+    if (!bc && !pins && v_zero && mg->fuse && v1 > 0) { /* :634 + :626: no fill, the first red pass does not read v */
         if (!mg->v_rim_zero[gridID]) mg->e_rim_valid[gridID] = 0; /* the zero fill changes v's boundary: d_e's copy is stale */
         if (MG_CAT(harm3_, R)(mg))
             MG_TRY(MG_CAT(mgx3dxs_relax_hmean_from_zero_, R)(mg->ctx, fine->d_v, fine->d_f, fine->d_a, MG_CAT(harm_cap3_, R)(mg, fine),
@@ -844,15 +1064,15 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
         mg->v_rim_zero[gridID] = 1;
     } else {
         if (v_zero) MG_TRY(FN(setToValue)(mg, fine->d_v, fine->sizeXYZ, (REAL)0, 1)); /* :634 */
-        MG_TRY(FN(Relax)(mg, fine, v1));                                              /* :626 */
+        MG_TRY(MG_CAT(relax_lvl3_, R)(mg, fine, v1, v_zero));                         /* :626 */
     }
     if (gridID != mg->numGrids - 1) {
         GRID* coarse = mg->grids3D[gridID + 1];
         const int semi = mg->coarsen[gridID] != 7;
-        if (bc) {
+        if (bc) { /* (with pinned nodes op_residual3_ zeroes d_r there before it is restricted) */
             MG_TRY(MG_CAT(op_residual3_, R)(mg, fine, fine->d_v, fine->d_f, fine->d_r, NULL, NULL)); /* :629 */
             MG_TRY(MG_CAT(mgx3dxs_restrict_bc_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ, bc)); /* :632 */
-        } else if (coef) {
+        } else if (coef || pins) {
             MG_TRY(MG_CAT(op_residual3_, R)(mg, fine, fine->d_v, fine->d_f, fine->d_r, NULL, NULL)); /* :629 */
             if (semi) MG_TRY(MG_CAT(mgx3dxs_restrict_axes_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ));
             else MG_TRY(MG_CAT(mgx3dxs_restrict_, R)(mg->ctx, fine->d_r, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ)); /* :632 */
@@ -867,14 +1087,15 @@ static int MG_CAT(vcycle_op_step3_, R)(MGRID* mg, int gridID, int v1, int v2, in
             MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_bc_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ, bc));
         } else if (semi) MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_axes_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ));
         else MG_TRY(MG_CAT(mgx3dxs_interpolate_correct_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :638-642 */
+        if (pins) MG_TRY(MG_CAT(pin_put3_, R)(mg, gridID, fine->d_v, !v_zero)); /* the correction has moved the pinned entries */
     }
-    return FN(Relax)(mg, fine, v2); /* :645 */
+    return MG_CAT(relax_lvl3_, R)(mg, fine, v2, v_zero); /* :645 */
 }
 
 /* VCycle from level gridID down.  v_zero: the level's v counts as all zeros (the coarse error of :634) but has not been
  * zeroed in memory yet -- the one-workgroup tail kernel never reads it, the other levels zero it first. */
 static int MG_CAT(vcycle_body3_, R)(MGRID* mg, int gridID, int v1, int v2, int v_zero) {
-    if (MG_CAT(has_coef3_, R)(mg) || mg->shift != 0 || mg->bc) return MG_CAT(vcycle_op_step3_, R)(mg, gridID, v1, v2, v_zero);
+    if (MG_CAT(has_coef3_, R)(mg) || mg->shift != 0 || mg->bc || mg->pin) return MG_CAT(vcycle_op_step3_, R)(mg, gridID, v1, v2, v_zero);
     GRID* fine = mg->grids3D[gridID];
     const int nlev = mg->numGrids - gridID;
     if (mg->fuse && mg->smoother == 0 && nlev <= 6 && !MG_CAT(semi_below3_, R)(mg, gridID)) { /* levels of at most 17^3: the rest of the cycle in ONE launch */
@@ -976,6 +1197,9 @@ int FN(VCycle)(MGRID* mg, int gridID, int v1, int v2) {
     if (mg->use_graph && !mg->capturing)
         return MG_CAT(vcycle_graph3_, R)(mg, gridID, v1, v2, FN(VCycle), &mg->graph_exec[gridID], &mg->graph_rec[gridID],
                                          &mg->graph_post[gridID], MG_GRAPH_3D, 0);
+    /* the level is the top of a cycle: its pinned points hold the stored values, whatever an earlier cycle that used the level for a
+     * correction has left there (nothing without pins) */
+    MG_TRY(MG_CAT(pin_put3_, R)(mg, gridID, mg->grids3D[gridID]->d_v, 1));
     return MG_CAT(vcycle_body3_, R)(mg, gridID, v1, v2, 0);
 }
 
@@ -990,6 +1214,7 @@ int FN(FullMultiGridVCycle)(MGRID* mg, int gridID, int v0, int v1, int v2) {
         MG_TRY(FN(Restrict)(mg, fine->d_f, fine->sizeXYZ, coarse->d_f, coarse->sizeXYZ));    /* :575 */
         MG_TRY(FN(FullMultiGridVCycle)(mg, gridID + 1, v0, v1, v2));                         /* :576 */
         MG_TRY(FN(Interpolate)(mg, fine->d_v, fine->sizeXYZ, coarse->d_v, coarse->sizeXYZ)); /* :577 */
+        MG_TRY(MG_CAT(pin_put3_, R)(mg, gridID, fine->d_v, 1)); /* the level's pinned values back (nothing without pins) */
     } else {
         MG_TRY(FN(setToValue)(mg, fine->d_v, fine->sizeXYZ, (REAL)0, 0)); /* :581 */
         if (mg->bc) { /* the unknowns on Neumann faces start from zero like the interior; Dirichlet entries stay */
@@ -997,6 +1222,7 @@ int FN(FullMultiGridVCycle)(MGRID* mg, int gridID, int v0, int v1, int v2) {
             MG_CAT(v_touched3_, R)(mg, fine->d_v);
             MG_TRY(MG_CAT(mgx3dxs_set_rim_bc_, R)(mg->ctx, fine->d_v, fine->sizeXYZ, (REAL)0, mg->bc));
         }
+        MG_TRY(MG_CAT(pin_put3_, R)(mg, gridID, fine->d_v, 1)); /* (the fill has zeroed them) */
     }
     for (int i = 0; i < v0; i++) MG_TRY(FN(VCycle)(mg, gridID, v1, v2)); /* :583-584 */
     return MGX_OK;
@@ -1037,7 +1263,8 @@ int FN(upload_v)(MGRID* mg, int gridID, const REAL* host) {
     MG_REQUIRE(host, MGX_ERR_INVALID, "upload_v: NULL");
     mg->v_rim_zero[gridID] = 0;
     mg->e_rim_valid[gridID] = 0;
-    return MG_CAT(put3_, R)(mg, g, g->d_v, host);
+    MG_TRY(MG_CAT(put3_, R)(mg, g, g->d_v, host));
+    return MG_CAT(pin_put3_, R)(mg, gridID, g->d_v, 1); /* a pinned point keeps its value (nothing without pins) */
 }
 int FN(upload_f)(MGRID* mg, int gridID, const REAL* host) {
     GRID* g = NULL; MG_TRY(MG_CAT(lvl3_, R)(mg, gridID, &g));
@@ -1121,7 +1348,7 @@ static int MG_CAT(pcg_precond3_, R)(MGRID* mg, int v1, int v2) {
 static int MG_CAT(pcg_true_sumsq3_, R)(MGRID* mg, const REAL* x, const REAL* b, double* ss) {
     GRID* g = mg->grids3D[0];
     const REAL h[3] = {g->h_x, g->h_y, g->h_z};
-    if (MG_CAT(wall_beta3_, R)(mg)) /* walls: the hierarchy's residual, not stored */
+    if (MG_CAT(wall_beta3_, R)(mg) || mg->pin) /* walls: the hierarchy's residual, not stored; pins: stored in d_r, over the unknowns only */
         MG_TRY(MG_CAT(op_residual3_, R)(mg, g, x, b, NULL, mg->pcg_work, mg->pcg_state + MGX_CG_RR));
     else if (MG_CAT(harm3_, R)(mg))
         MG_TRY(MG_CAT(mgx3dxs_residual_hmean_wall_, R)(mg->ctx, x, b, g->d_a, MG_CAT(harm_cap3_, R)(mg, g), NULL, g->sizeXYZ, h, mg->shift,
@@ -1297,6 +1524,7 @@ int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* i
     MG_REQUIRE(!MG_CAT(has_cap3_, R)(mg) || MG_CAT(has_coef3_, R)(mg), MGX_ERR_INVALID, "PCG: a capacity needs a coefficient (set_coefficient)");
     MG_TRY(MG_CAT(cap_singular3_, R)(mg, "PCG")); /* (not solved in the projected sense: its null space is not the shift's) */
     MG_TRY(MG_CAT(bc_ok3_, R)(mg, mg->bc, "PCG"));
+    MG_TRY(MG_CAT(pin_ok3_, R)(mg, "PCG")); /* (the closed box is refused with pins, krylov = 2 included) */
     const int weighted = krylov == MG_KRYLOV_WEIGHTED;
     if (!weighted) MG_TRY(MG_CAT(bc_singular3_, R)(mg, "PCG")); /* (krylov = 2 solves the closed box without a shift, projected) */
     MG_REQUIRE(!mg->bc || !krylov || weighted, MGX_ERR_INVALID,
@@ -1307,6 +1535,7 @@ int FN(PCG)(MGRID* mg, int v1, int v2, double tol, int maxit, int krylov, int* i
     *converged = 0;
     MG_TRY(MG_CAT(pcg_alloc3_, R)(mg));
     MG_TRY(mgx_memset_zero(mg->ctx, mg->pcg_state + MGX_CG_FMEAN, sizeof(double)));
+    MG_TRY(MG_CAT(pin_put3_, R)(mg, 0, mg->grids3D[0]->d_v, 1)); /* the iterate holds the pinned values before the first residual */
     if (!krylov) return MG_CAT(pcg_plain3_, R)(mg, v1, v2, tol, maxit, iters, rel_res, converged, host_hist, hist_cap);
     const int singular = mg->bc == 63 && mg->shift == 0 && !MG_CAT(wall_beta3_, R)(mg); /* (a lossy wall: regular, nothing projected) */
     mg->bc_reserved = singular; /* "inside a projected solve": cleared on every way out */
@@ -1410,6 +1639,7 @@ int MG_CAT(mg3d_solve_from_zero_, R)(mgx_ctx* ctx, REAL* grid_out, const REAL* r
 }
 
 #undef CAPTAB
+#undef PINTAB
 #undef WALLTAB
 #undef GRID
 #undef MGRID

@@ -129,6 +129,12 @@ static int cap_rhs3d(mgx_ctx* ctx, const real* u, const real* c, const real* q, 
                                                 const real h[3], real s, int ncycles, int bc, const real beta[6]) {                          \
         return mgx::relax_op3d_bc<mgx::CapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_cap_wall", c);                    \
     }                                                                                                                                        \
+    extern "C" int mgx3dxs_relax_cap_pin_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c, const int n[3], const real h[3], real s, int ncycles, int bc, const real beta[6], const unsigned* idx, \
+            const unsigned end[2], const real* val) {                                                                                        \
+        MGX_REQUIRE(end, MGX_ERR_INVALID, "relax_cap_pin: NULL argument");                                                                   \
+        const mgx::PinList<real> pin = {idx, {end[0], end[1]}, val};                                                                         \
+        return mgx::relax_op3d_bc<mgx::CapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_cap_pin", c, &pin);               \
+    }                                                                                                                                        \
     extern "C" int mgx3dxs_residual_cap_wall_##SFX(mgx_ctx* ctx, const real* v, const real* f, const real* a, const real* c, real* r,        \
                                                    const int n[3], const real h[3], real s, double* dev_work, double* dev_sumsq, int bc,     \
                                                    const real beta[6]) {                                                                     \

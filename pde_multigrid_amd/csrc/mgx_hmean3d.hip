@@ -29,6 +29,13 @@
         if (c) return mgx::relax_op3d_bc<mgx::HarmCapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_hmean_wall", c);       \
         return mgx::relax_op3d_bc<mgx::HarmOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_hmean_wall");                    \
     }                                                                                                                                        \
+    extern "C" int mgx3dxs_relax_hmean_pin_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c, const int n[3], const real h[3], real s, int ncycles, int bc, const real beta[6], const unsigned* idx, \
+            const unsigned end[2], const real* val) {                                                                                        \
+        MGX_REQUIRE(end, MGX_ERR_INVALID, "relax_hmean_pin: NULL argument");                                                                 \
+        const mgx::PinList<real> pin = {idx, {end[0], end[1]}, val};                                                                         \
+        if (c) return mgx::relax_op3d_bc<mgx::HarmCapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_hmean_pin", c, &pin);  \
+        return mgx::relax_op3d_bc<mgx::HarmOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_hmean_pin", nullptr, &pin);      \
+    }                                                                                                                                        \
     extern "C" int mgx3dxs_relax_hmean_from_zero_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const real* c, const int n[3],   \
                                                        const real h[3], real s, int ncycles, int rim_is_zero) {                              \
         if (c) return mgx::relax_op3d<mgx::HarmCapOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, 1, rim_is_zero, "relax_hmean_from_zero", c); \

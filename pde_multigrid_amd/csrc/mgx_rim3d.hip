@@ -114,6 +114,19 @@ __global__ void __launch_bounds__(RIM_THREADS) rim_dot2_3d_xs_kernel(const real*
     if (TWO) rim_block_sum(ac, part[1], pac + blockIdx.x);
 }
 
+// partials of the UNWEIGHTED sum of a^2 over the face unknowns (the stopping rule's norm of a stored residual)
+template <class real>
+__global__ void __launch_bounds__(RIM_THREADS) rim_sumsq3d_xs_kernel(const real* __restrict__ a, Rim R, double* __restrict__ partial) {
+    const Geo<XSplit, real> g(R.sx, R.sy);
+    double acc = 0.0;
+    RIM_FOR_EACH_POINT(R, g, x, y, z) {
+        const double av = (double)a[g.row(y, z) + g.pos(x)];
+        acc += av * av;
+    }
+    __shared__ double part[RIM_THREADS / 64];
+    rim_block_sum(acc, part, partial + blockIdx.x);
+}
+
 // X: x += alpha p (the old p); P_: p = z + beta p (BETA) or p = z
 template <class real, bool X, bool P_, bool BETA>
 __global__ void __launch_bounds__(RIM_THREADS) rim_cg_direction3d_xs_kernel(real* __restrict__ xv, real* __restrict__ p,
@@ -305,6 +318,24 @@ static int dot2_3d_bc(mgx_ctx* ctx, const real* a, const real* b, const real* c,
     return MGX_OK;
 }
 
+// *dev_sum = the unweighted sum of a^2 over all unknowns (bc = 0: dot2(a, a)'s bits)
+template <class real>
+static int sumsq3d_bc(mgx_ctx* ctx, const real* a, const int n[3], double* dev_work, double* dev_sum, int bc) {
+    MGX_REQUIRE(ctx && a && n && dev_work && dev_sum, MGX_ERR_INVALID, "sumsq_bc: NULL argument");
+    RIM_BC_CHECK(bc, "sumsq_bc");
+    if (!bc) return dot2_3d<real>(ctx, a, a, nullptr, n, dev_work, dev_sum, true);
+    MGX_TRY_RET(rows_check(n, "sumsq_bc"));
+    Rim R;
+    MGX_TRY_RET(rim_list<real>(n, bc, "sumsq_bc", R));
+    MGX_TRY_RET(dot2_3d<real>(ctx, a, a, nullptr, n, dev_work, dev_sum, false));
+    const dim3 g = krylov_grid(n);
+    const size_t interior = (size_t)g.x * g.y;
+    const unsigned nb = rim_blocks(R);
+    MGX_LAUNCH((rim_sumsq3d_xs_kernel<real>), dim3(nb), dim3(RIM_THREADS), 0, ctx->compute, a, R, dev_work + interior);
+    MGX_LAUNCH_CHECK();
+    return krylov_final(ctx, dev_work, interior + nb, 1, dev_sum);
+}
+
 template <class real>
 static int cg_direction3d_bc(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3], const double* dev_alpha, const double* dev_beta,
                              int bc) {
@@ -393,6 +424,18 @@ static int project3d_bc(mgx_ctx* ctx, real* a, const int n[3], double* dev_work,
                                                     const real h[3], real s, double* dev_work, double* dev_sumsq, int bc,                    \
                                                     const real beta[6]) {                                                                    \
         return mgx::residual_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, r, n, h, s, dev_work, dev_sumsq, bc, beta, "residual_coef_wall");  \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_relax_shift_pin_##SFX(mgx_ctx* ctx, real* v, const real* f, const int n[3], const real h[3], real s, int ncycles, int bc, const real beta[6], const unsigned* idx, \
+            const unsigned end[2], const real* val) {                                                                                        \
+        MGX_REQUIRE(end, MGX_ERR_INVALID, "relax_shift_pin: NULL argument");                                                                 \
+        const mgx::PinList<real> pin = {idx, {end[0], end[1]}, val};                                                                         \
+        return mgx::relax_op3d_bc<mgx::ShiftOp<real>, real>(ctx, v, f, nullptr, n, h, s, ncycles, bc, beta, "relax_shift_pin", nullptr, &pin); \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_relax_coef_pin_##SFX(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int bc, const real beta[6], const unsigned* idx, \
+            const unsigned end[2], const real* val) {                                                                                        \
+        MGX_REQUIRE(end, MGX_ERR_INVALID, "relax_coef_pin: NULL argument");                                                                  \
+        const mgx::PinList<real> pin = {idx, {end[0], end[1]}, val};                                                                         \
+        return mgx::relax_op3d_bc<mgx::CoefOp<real>, real>(ctx, v, f, a, n, h, s, ncycles, bc, beta, "relax_coef_pin", nullptr, &pin);       \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_restrict_bc_##SFX(mgx_ctx* ctx, const real* fine, const int fn[3], real* coarse, const int cn[3], int bc) {        \
         MGX_REQUIRE(ctx && fine && fn && coarse && cn, MGX_ERR_INVALID, "restrict_bc: NULL argument");                                       \
@@ -486,6 +529,9 @@ MGX_RIM3D_API(f64, double)
     extern "C" int mgx3dxs_dot2_bc_##SFX(mgx_ctx* ctx, const real* a, const real* b, const real* c, const int n[3], double* dev_work,         \
                                          double* dev_sum, int bc) {                                                                          \
         return mgx::dot2_3d_bc<real>(ctx, a, b, c, n, dev_work, dev_sum, bc);                                                                \
+    }                                                                                                                                        \
+    extern "C" int mgx3dxs_sumsq_bc_##SFX(mgx_ctx* ctx, const real* a, const int n[3], double* dev_work, double* dev_sum, int bc) {            \
+        return mgx::sumsq3d_bc<real>(ctx, a, n, dev_work, dev_sum, bc);                                                                      \
     }                                                                                                                                        \
     extern "C" int mgx3dxs_cg_direction_bc_##SFX(mgx_ctx* ctx, real* x, real* p, const real* z, const int n[3], const double* dev_alpha,      \
                                                  const double* dev_beta, int bc) {                                                           \

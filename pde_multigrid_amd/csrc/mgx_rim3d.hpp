@@ -159,27 +159,47 @@ static WallD<real> wall_diagonal(const real beta[6], const real h[3]) {
     return w;
 }
 
+// ------------------------------------------------------------------ pinned interior nodes (section 22)
+// the list of a level's pinned points (device arrays): 32-bit storage offsets, the red points first, each colour sorted by offset,
+// end[0] = the red ones, end[1] = all; val in list order, NULL = zeros.  The kernel and its launch: mgx_pin3d.hip, their one home.
+template <class real>
+struct PinList {
+    const unsigned* idx;
+    unsigned end[2];
+    const real* val;
+};
+template <class real>
+void pin_put_launch(mgx_ctx* ctx, real* v, const unsigned* idx, const real* val, unsigned first, unsigned count);
+
 // ---- the drivers of the entries with a mask: one per operation, for the _bc entries (beta = NO_WALL) and the _wall entries alike.
 // With bc = 0 (no beta can be non-zero then) nothing but the interior driver runs.
-// ncycles red+black sweeps, each colour pass the interior launch and the face launch of that colour
+// ncycles red+black sweeps, each colour pass the interior launch and the face launch of that colour -- and, with a pin list, the
+// launch that puts that colour's pinned values back, which the interior launch has overwritten and the next pass reads
 template <class Op, class real>
 static int relax_op3d_bc(mgx_ctx* ctx, real* v, const real* f, const real* a, const int n[3], const real h[3], real s, int ncycles, int bc,
-                         const real beta[6], const char* what, const real* c = nullptr) {
+                         const real beta[6], const char* what, const real* c = nullptr, const PinList<real>* pin = nullptr) {
     MGX_REQUIRE(ctx && v && f && (a || !Op::HAS_A) && (c || !Op::HAS_C) && n && h && beta, MGX_ERR_INVALID, "%s: NULL argument", what);
     RIM_BC_CHECK(bc, what);
     MGX_TRY_RET(wall_data_check<real>(beta, h, bc, false, what));
-    if (!bc) return relax_op3d<Op, real>(ctx, v, f, a, n, h, s, ncycles, 0, 0, what, c);
+    if (pin && !pin->end[1]) pin = nullptr;  // an empty list: the entry without one
+    MGX_REQUIRE(!pin || (pin->idx && pin->end[0] <= pin->end[1]), MGX_ERR_INVALID, "%s: bad pin list (idx %p, end %u, %u)", what,
+                pin ? (const void*)pin->idx : nullptr, pin ? pin->end[0] : 0u, pin ? pin->end[1] : 0u);
+    if (!bc && !pin) return relax_op3d<Op, real>(ctx, v, f, a, n, h, s, ncycles, 0, 0, what, c);
     const double sd = (double)s;
     MGX_TRY_RET(rows_check(n, what, &sd, false));
     MGX_REQUIRE(ncycles >= 0, MGX_ERR_INVALID, "%s: ncycles = %d < 0", what, ncycles);
     MGX_USE(ctx);
     const Op op = make_op<Op, real>(ctx, h, s, c);
     const WallD<real> w = wall_diagonal<real>(beta, h);
-    Rim R;
-    MGX_TRY_RET(rim_list<real>(n, bc, what, R));
+    Rim R = {};
+    if (bc) MGX_TRY_RET(rim_list<real>(n, bc, what, R));
     for (int p = 0; p < 2 * ncycles; p++) {
         relax_op3d_pass<Op, real>(ctx, v, f, a, n, op, p & 1);
-        face_relax_launch<Op, real>(ctx, v, f, a, R, op, w, p & 1);
+        if (bc) face_relax_launch<Op, real>(ctx, v, f, a, R, op, w, p & 1);
+        if (pin) {
+            const unsigned first = (p & 1) ? pin->end[0] : 0u;
+            pin_put_launch<real>(ctx, v, pin->idx, pin->val, first, ((p & 1) ? pin->end[1] : pin->end[0]) - first);
+        }
     }
     MGX_LAUNCH_CHECK();
     return MGX_OK;

@@ -724,6 +724,59 @@ class _Ops3D(_Ops):
         h = _rp(grid_spacing(n, rng, dtype), ct)
         return self._run(ctx, [f], lambda fp: fn(ctx._h, fp, _ip(n), h, _rp(g, ct), C.c_int(bc)), 0, _shape(n), dtype)
 
+    # ---- pinned interior nodes (x-split only, mgx3dxs_pin_*): mask in the reference layout, values an array over the grid
+    def pin_list(self, n, mask, values=None, dtype=np.float64):
+        """(idx, val, end): the list of a mask as the library builds it (host arrays)"""
+        s, ct = _ct(dtype)
+        fn = getattr(lib, "mgx3dxs_pin_list_" + s)
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        assert mask.shape == _shape(n), (mask.shape, n)
+        end = (C.c_uint * 2)()
+        check(fn(_ip(n), mask.ctypes.data_as(C.c_void_p), None, None, None, end))
+        idx, val = np.zeros(max(end[1], 1), np.uint32), np.zeros(max(end[1], 1), dtype)
+        vals = None if values is None else np.ascontiguousarray(values, dtype)
+        check(fn(_ip(n), mask.ctypes.data_as(C.c_void_p), None if vals is None else vals.ctypes.data_as(C.c_void_p),
+                 idx.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p), end))
+        return idx[:end[1]], val[:end[1]], (int(end[0]), int(end[1]))
+
+    def pin_put(self, ctx, v, n, mask, values=None, first=None, count=None, dtype=None):
+        """v with the values (None: zeros) at the list entries [first, first + count) of the mask's pinned points (default: all)"""
+        dtype = dtype or v.dtype
+        fn, ct = self._fn("pin_put", dtype)
+        idx, val, end = self.pin_list(n, mask, values, dtype)
+        first = 0 if first is None else int(first)
+        count = end[1] - first if count is None else int(count)
+        assert 0 <= first and first + count <= end[1], (first, count, end)
+        di = ctx.to_device(idx) if len(idx) else None
+        dv = ctx.to_device(val) if values is not None and len(val) else None
+        try:
+            return self._run(ctx, [v], lambda a: fn(ctx._h, a, di, dv, C.c_uint(first), C.c_uint(count)), 0, _shape(n), dtype)
+        finally:
+            for p in (di, dv):
+                if p is not None:
+                    ctx.free(p)
+
+    def relax_pin(self, ctx, v, f, n, rng, s, ncycles, mask, values=None, a=None, c=None, mean=None, bc=0, beta=None, dtype=None):
+        """ncycles sweeps of the operator that a, c and mean say (a None: shifted; mean "harmonic": the _hmean entry) with the mask's
+        points pinned to values (None: zeros); v should hold them on entry"""
+        dtype = dtype or v.dtype
+        harm = mean == "harmonic"
+        assert mean in (None, "arithmetic", "harmonic") and not (harm and a is None)
+        name = "relax_hmean_pin" if harm else "relax_cap_pin" if c is not None else "relax_coef_pin" if a is not None else "relax_shift_pin"
+        fn, ct = self._fn(name, dtype)
+        h, b = _rp(grid_spacing(n, rng, dtype), ct), _rp(beta if beta is not None else [0.0] * 6, ct)
+        idx, val, end = self.pin_list(n, mask, values, dtype)
+        di = ctx.to_device(idx) if len(idx) else None
+        dv = ctx.to_device(val) if values is not None and len(val) else None
+        arrays = [v, f] + ([a, c] if harm else [x for x in (a, c) if x is not None])
+        try:
+            return self._run(ctx, arrays, lambda vp, fp, *ac: fn(ctx._h, vp, fp, *ac, _ip(n), h, ct(s), C.c_int(ncycles), C.c_int(bc), b, di,
+                                                                  (C.c_uint * 2)(*end), dv), 0, _shape(n), dtype)
+        finally:
+            for p in (di, dv):
+                if p is not None:
+                    ctx.free(p)
+
     # ---- harmonic-mean face coefficients (x-split only, mgx3dxs_*_hmean): views of the four entries, which take the _wall form;
     # c: None = no capacity, bc: None = the interior alone, beta: None = six zeros (homogeneous Neumann faces)
     def relax_hmean(self, ctx, v, f, a, n, rng, s, ncycles, c=None, bc=None, beta=None, dtype=None):
@@ -1162,9 +1215,15 @@ def face_mean_mode(name):
     return FACE_MEANS[name]
 
 
+class _PinSlot(C.Structure):
+    """the last eight bytes of the unused graph_key: the table of the pinned nodes"""
+    _fields_ = [("graph_key_head_", C.c_longlong * 28), ("pin", C.c_void_p)]
+
+
 class _GraphKey(C.Union):
-    """the unused graph_key of mgMultiGrid3D_<r>, whose first four bytes hold face_mean"""
-    _fields_ = [("graph_key", C.c_longlong * 29), ("face_mean", C.c_int)]
+    """the unused graph_key of mgMultiGrid3D_<r>, whose first four bytes hold face_mean and whose last eight the pin table"""
+    _anonymous_ = ("pin_",)
+    _fields_ = [("graph_key", C.c_longlong * 29), ("face_mean", C.c_int), ("pin_", _PinSlot)]
 
 
 def _grid3_struct(ct):
@@ -1287,7 +1346,7 @@ class MultiGrid3D(_MGBase):
 
     def __init__(self, ctx, finestGridSizeXYZ, rng, dtype=np.float64, nlevels=0, residual_mode=REF_COMPAT, fuse=True,
                  layout="xsplit", coarsening="full", shift=0.0, coefficient=None, neumann=None, capacity=None, robin=None,
-                 wall_flux=None, face_mean="arithmetic"):
+                 wall_flux=None, face_mean="arithmetic", pinned=None, pinned_values=None):
         """coarsening="semi": every level halves only the axes with the smallest spacing (semi_plan, mg_multigrid.h) -- the
         hierarchy for grids whose spacings differ; always x-split; nlevels caps its level count.
         shift = s >= 0: the hierarchy of (Laplacian - s) u = f (the `shift` property).
@@ -1297,7 +1356,9 @@ class MultiGrid3D(_MGBase):
         a coefficient).
         robin, wall_flux = six numbers each (the faces' order): beta >= 0 and g of the wall law a du/dn + beta u = g on the
         faces of `neumann` (set_wall).
-        face_mean = "arithmetic" or "harmonic": the mean of the two nodes' coefficients a face carries (set_face_mean)."""
+        face_mean = "arithmetic" or "harmonic": the mean of the two nodes' coefficients a face carries (set_face_mean).
+        pinned, pinned_values = a boolean mask over level 0 and the values of its true points: interior points whose value is data
+        (set_pinned)."""
         mean = face_mean_mode(face_mean)
         self.ctx = ctx
         self.dtype = np.dtype(dtype)
@@ -1355,6 +1416,52 @@ class MultiGrid3D(_MGBase):
             except Exception:
                 self.close()
                 raise
+        if pinned is not None:
+            try:
+                self.set_pinned(pinned, pinned_values)
+            except Exception:
+                self.close()
+                raise
+
+    def set_pinned(self, mask, values=None):
+        """mask: booleans over level 0 (reference layout), True at the interior points whose value is DATA: an electrode or a
+        thermostat inside the volume, everything outside a body that is no box, a pressure pinned at one point.  values: their
+        values, an array over level 0 read at the true points (None: zeros).  A pinned point is no unknown: v holds its value before
+        and after every call, its neighbours read it as they read a Dirichlet face point, the smoother never changes it, the residual
+        and every vector of PCG are exactly 0 there, and ResidualNorm and PCG's stopping rule sum over the remaining unknowns.  The
+        operator on those is the old one with rows and columns struck out: still symmetric, in the weighted product too.  A coarse
+        point is pinned when its coincident fine point is, or one of that point's two neighbours along an axis the step halves; the
+        values go down by injection.  Works with every operator of the hierarchy (shift, coefficient with either face mean,
+        capacity, walls), on full and semi-coarsened hierarchies, in cycles, PCG (every krylov), BackwardEuler and use_graph.  A True
+        on the boundary of the box is refused (Dirichlet face points are data already; a wall unknown cannot be pinned).  Needs
+        layout="xsplit", the red-black smoother and residual_mode=CORRECT; PCG(precond="f32") and Eigen are not available, nor is
+        the closed box (all six faces walls, no shift, no robin > 0).  None or all False: no pins -- the hierarchy is then, launch for
+        launch, one that never had any."""
+        if mask is None:
+            self._call("set_pinned", None, None)
+            return
+        shape = _shape(self.size(0))
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        if mask.shape != shape:
+            raise ValueError("the mask of the pinned nodes has shape %r, level 0 has %r" % (mask.shape, shape))
+        vp = None
+        if values is not None:
+            values = np.ascontiguousarray(values, self.dtype)
+            if values.shape != shape:
+                raise ValueError("the values of the pinned nodes have shape %r, level 0 has %r" % (values.shape, shape))
+            vp = values.ctypes.data_as(C.c_void_p)
+        self._call("set_pinned", mask.ctypes.data_as(C.c_void_p), vp)
+
+    def pinned(self, gridID=0):
+        """the mask of level gridID's pinned points (booleans, reference layout)"""
+        out = np.zeros(_shape(self.size(gridID)), np.uint8)
+        self._call("get_pinned", C.c_int(gridID), out.ctypes.data_as(C.c_void_p))
+        return out.astype(bool)
+
+    def pinned_count(self, gridID=0):
+        out = C.c_size_t()
+        self._call("pinned_count", C.c_int(gridID), C.byref(out))
+        return int(out.value)
 
     def set_wall(self, robin=None, flux=None):
         """robin, flux: six numbers each, one per face in the order x-low, x-high, y-low, y-high, z-low, z-high (None: zeros):
@@ -1952,7 +2059,8 @@ def solve3d_from_zero(ctx, n, rng, dtype=np.float64, rhs=None, nlevels=0, fmg=Fa
 
 
 def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100, krylov=True, precond="f64", coarsening="full",
-                shift=0.0, coefficient=None, neumann=None, capacity=None, robin=None, wall_flux=None, face_mean="arithmetic"):
+                shift=0.0, coefficient=None, neumann=None, capacity=None, robin=None, wall_flux=None, face_mean="arithmetic",
+                pinned=None, pinned_values=None):
     """mg3d_solve_pcg: grid = guess with its Dirichlet boundary; returns (solution, iters, rel_res, converged).
     precond="f32" (fp64 grids only): mg3d_solve_pcg_mixed, the V-cycle in fp32 (MultiGrid3D.PCG).
     coarsening="semi": the same solve on a semi-coarsened hierarchy (MultiGrid3D(coarsening="semi")) built here for the call.
@@ -1962,7 +2070,9 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
     krylov="weighted" (MultiGrid3D.PCG).
     capacity = c >= 0 at every point, with a coefficient: the solve of div(a grad u) - (shift c) u = rhs, likewise.
     robin, wall_flux = six numbers each: the walls' beta and g (MultiGrid3D.set_wall); the flux is folded into rhs here.
-    face_mean = "arithmetic" or "harmonic": the face coefficients of a solve with a coefficient (MultiGrid3D.set_face_mean)."""
+    face_mean = "arithmetic" or "harmonic": the face coefficients of a solve with a coefficient (MultiGrid3D.set_face_mean).
+    pinned, pinned_values = the mask and the values of interior points whose value is data (MultiGrid3D.set_pinned); the solution
+    holds the values there."""
     face_mean_mode(face_mean)
     grid = np.ascontiguousarray(grid).copy()
     s, ct = _ct(grid.dtype)
@@ -1973,10 +2083,10 @@ def solve3d_pcg(ctx, grid, rhs, rng, nlevels=0, v1=2, v2=2, tol=1e-10, maxit=100
     if coarsening not in ("full", "semi"):
         raise ValueError("coarsening must be 'full' or 'semi', not %r" % (coarsening,))
     if coarsening == "semi" or shift != 0 or coefficient is not None or capacity is not None or (neumann is not None and any(neumann)) or \
-            robin is not None or wall_flux is not None:
+            robin is not None or wall_flux is not None or pinned is not None:
         mg = MultiGrid3D(ctx, tuple(reversed(grid.shape)), rng, grid.dtype, nlevels=nlevels, residual_mode=CORRECT, coarsening=coarsening,
                          shift=shift, coefficient=coefficient, neumann=neumann, capacity=capacity, robin=robin, wall_flux=wall_flux,
-                         face_mean=face_mean)
+                         face_mean=face_mean, pinned=pinned, pinned_values=pinned_values)
         try:
             mg.upload_v(0, grid)
             if rhs is not None:
