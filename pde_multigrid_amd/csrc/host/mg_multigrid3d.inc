@@ -1495,14 +1495,16 @@ static int MG_CAT(pcg_krylov3_, R)(MGRID* mg, int v1, int v2, double tol, int ma
     } else if (!st && rr0 != 0.0) {
         *rel_res = rr0; /* NaN: the initial residual is not finite */
     }
-    /* d_v[0] := x (its boundary is the guess's), d_f[0] := b; their flags as they were (same boundary contents); d_e's */
+    /* d_v[0] := x (its boundary is the guess's), d_f[0] := b; their flags as they were (same boundary contents) -- but with a */
+    /* mask x's face unknowns are the solution's, not the guess's: v_rim_zero is then no longer known (a zero guess solved    */
+    /* under a mask, the mask cleared, and the next preconditioner would take the rim of its correction for zeros); d_e's     */
     /* boundary copy no longer matches d_v's */
     const int st2 = mgx_memcpy_d2d(ctx, g->d_v, x, bytes);
     const int st3 = mgx_memcpy_d2d(ctx, g->d_f, b, bytes);
     /* the face unknowns of p and q back to the zeros a solve without a mask reads as Dirichlet data */
     const int st4 = MG_CAT(mgx3dxs_set_rim_bc_, R)(ctx, p, n, (REAL)0, bc);
     const int st5 = MG_CAT(mgx3dxs_set_rim_bc_, R)(ctx, q, n, (REAL)0, bc);
-    mg->v_rim_zero[0] = v_rim0;
+    mg->v_rim_zero[0] = bc ? 0 : v_rim0;
     mg->f_rim_zero[0] = f_rim0;
     mg->e_rim_valid[0] = 0;
     if (!st) st = st2 ? st2 : st3 ? st3 : st4 ? st4 : st5;
